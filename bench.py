@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — PLUME V1 verifies/s on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--config 2|3|4] [--log2-batch 20] [--version 1] [--multi-ctx]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--config 2|3|4] [--log2-batch 20] [--version 1] [--multi-ctx] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times --steps steps and prints the line with the contract's keys (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...) and nothing else.  --full adds everything below "Objects on the line": the serial pass after an in-flight timed region, the
+probes and roofline views, the CPU baseline, the secondary workloads and the checks against the setup pass and the CPU oracle.  PLUME_BENCH_FULL=1
+in the environment does the same as --full (for the profiling scripts, which run the bench many times).
+  --dump-outputs DIR  after the timed steps, what the LAST timed step computed, as DIR/<name>.npy in float32: the verdicts (`ok`) of a verify step, the
+                   seven output arrays of a sign step.  Above 64 MB in all, a fixed seeded sample of the items is written, with its indices in
+                   DIR/sample_index.npy (float64).  Under torch.distributed.run every rank writes its own slice as DIR/rank<r>_<name>.npy.
 
 A "step" is one pass of the verify pipeline (ingest+h2c -> window tables -> multi-scalar loop -> finalize) over one batch of synthetic
 signatures, inputs already resident in HBM, through the C ABI's device-resident entry point (plume_verify_batch_device) on torch's
@@ -75,7 +83,10 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-probe", action="store_true", help="skip the issue-rate probe kernels (profiling runs: they would bury the trace); the roofline then prices against the pool's reference rate and says so")
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary workloads (V2 verify, V1 sign, SEC1 ingest, e2e) reported at N=1")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: serial pass, probes, roofline views, CPU baseline, secondary workloads, oracle checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32; a seeded sample above 64 MB)")
     a = ap.parse_args()
+    a.full = a.full or os.environ.get("PLUME_BENCH_FULL") == "1"
     a.workload = "verify"
     preset_log2 = 20
     if a.config == 4:
@@ -183,6 +194,28 @@ def plan(scaling: str, log2_batch: int, world: int, rank: int):
     total = (1 << log2_batch) * (world if scaling == "weak" else 1)
     start, stop = shard_bounds(total, rank, world)
     return total, start, stop
+
+
+DUMP_BUDGET = 60_000_000                          # --dump-outputs: bytes of .npy data over all ranks (under 64 MB whichever way a megabyte is counted)
+DUMP_SEED = 0x504C554D45
+
+
+def dump_outputs(out_dir, arrays: dict, rank: int = 0, world: int = 1):
+    """--dump-outputs: `arrays` (name -> host array, one row per item) as DIR/<name>.npy in float32 (the bytes are exact in it).  When all rows do not fit this rank's share of
+    the budget, the same rows of every array are written: a sorted sample drawn with a fixed seed, its indices in DIR/sample_index.npy, so two runs write the same items."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    n = len(next(iter(arrays.values())))
+    row = sum(4 * int(np.prod(x.shape[1:])) for x in arrays.values())
+    budget = DUMP_BUDGET // world
+    idx = None
+    if n * row > budget:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=max(1, budget // (row + 8)), replace=False))
+        np.save(d / f"{pre}sample_index.npy", idx.astype(np.float64))
+    for k, x in arrays.items():
+        np.save(d / f"{pre}{k}.npy", np.asarray(x if idx is None else x[idx], dtype=np.float32))
 
 
 FETCH_SIZE_FACTOR = 2.0   # gfx950: FETCH_SIZE tallies a 128-byte request at 64 bytes (MI355X_MICROARCH.md, HBM).  The guide calibrated that on wide coalesced streams and asks for a
@@ -562,6 +595,8 @@ def multi_ctx_main(a):
         step()
     elapsed = time.perf_counter() - t0                       # the host-pointer call returns when its results are in the caller's array
     assert np.array_equal(ok, synth.expected_ok(total)), "verify results differ from the expected corruption pattern"
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"ok": ok})
     value = total * a.steps / elapsed
     line = {"metric": f"PLUME verifies/sec (secp256k1 V{ver}) at batch=2^{a.log2_batch}" + (" per GPU" if a.scaling == "weak" else " total") + ", host-pointer calls (PCIe-inclusive)",
             "value": round(value, 1), "unit": "verifies/s", "n_gpus": g, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * elapsed / a.steps, 3), "higher_is_better": True,
@@ -685,9 +720,17 @@ def main():
                     clk_acc.append(g)
     fence()
     elapsed_rank = time.perf_counter() - t0
+    if a.dump_outputs and a.steps > 0:
+        last = (a.steps - 1) % F                                 # the lane of the last timed step (the serial pass below writes into lane 0's arrays again)
+        if sign:
+            arrs = {k: outs[last][k].cpu().numpy() for k in ("pk", "nullifier", "c", "s", "r_point", "hashed_to_curve_r")}
+            arrs["status"] = statuses[last].cpu().numpy()
+        else:
+            arrs = {"ok": oks[last].cpu().numpy()}
+        dump_outputs(a.dump_outputs, arrs, rank, world)
     stage_div = a.steps
     in_flight_info = None
-    if F > 1:
+    if F > 1 and a.full:
         # what the kernels of the timed region's LAST call took (its predecessor's multi-scalar kernel ran beside its first stages; its own multi-scalar kernel finishes with the
         # machine nearly to itself -- calls in the middle of the stream are stretched more, up to +0.4 ms on that kernel by tests with two contexts)
         infl = {name: ms for name, ms in eng.last_stage_times()}        # the lane of the last call
@@ -712,12 +755,13 @@ def main():
                           "serial": {"steps": S, "ms_per_step": round(serial_s * 1e3, 3), ("signs_per_s" if sign else "verifies_per_s"): round(n / serial_s, 1),
                                      "note": "the same calls one after the other on one stream, after the timed region: stage_ms and roofline.kernel_ms are this pass's"}}
     if sign:
-        # the timed passes' outputs: equal to the setup pass's (host-pointer entry point) and, on a sample, to the CPU oracle's
+        # the timed passes' outputs: equal to the setup pass's (host-pointer entry point) and, on a sample, to the CPU oracle's (--full; a plain run checks the status bytes)
         for oo, st_ in zip(outs, statuses):
-            for k in ("pk", "nullifier", "c", "s", "r_point", "hashed_to_curve_r"):
-                assert np.array_equal(oo[k].cpu().numpy(), signed[k]), f"sign outputs differ between passes: {k}"
+            if a.full:
+                for k in ("pk", "nullifier", "c", "s", "r_point", "hashed_to_curve_r"):
+                    assert np.array_equal(oo[k].cpu().numpy(), signed[k]), f"sign outputs differ between passes: {k}"
             assert not bool(st_.any())
-        if rank == 0:
+        if rank == 0 and a.full:
             from tests import _oracle_c as OC
             m = 256
             want = OC.sign_batch(ver, b["msgs"], b["off"][: m + 1], b["sk"][:m], b["r"][:m], nthreads=8)
@@ -730,7 +774,7 @@ def main():
     per_rank = [elapsed_rank]
     # this rank's record: which device, which slice of the batch, and whether its verdicts were the corruption pattern (asserted above: a rank that got here passed)
     rank_rec = {"rank": rank, "local_rank": local_rank, "device": local_dev, "slice": [start, stop], "items_per_step": n, "elapsed_s": round(elapsed_rank, 6),
-                ("outputs_match_setup_pass" if sign else "verdicts_match_pattern"): True}
+                ("outputs_match_setup_pass" if sign else "verdicts_match_pattern"): True if (a.full or not sign) else None}
     ranks = [rank_rec]
     if use_dist:
         gathered = [torch.zeros(1, dtype=torch.float64, device=tdev) for _ in range(world)]
@@ -756,8 +800,8 @@ def main():
                                    + ("" if sign else "1/16 corrupted, ") + "inputs resident in HBM; Fp arithmetic on 9x29-bit limbs through chains of v_mad_u64_u32 (32x32+64)",
                        "form": "one process per GPU (torch.distributed ranks), device-resident entry point plume_" + op + "_batch_device; " +
                                (f"{F} batches in flight per GPU (plume_set_in_flight): step i goes to lane i mod {F} of the context on stream i mod {F}, each call's launch order strictly serial (sub_batches = 1); "
-                                f"GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')} so that the streams sit on different hardware queues; "
-                                "stage_ms and roofline from a serial pass after the timed region (in_flight.serial)" if F > 1 else
+                                f"GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')} so that the streams sit on different hardware queues; " +
+                                ("stage_ms and roofline from a serial pass after the timed region (in_flight.serial)" if a.full else "no serial pass (bench.py --full adds it)") if F > 1 else
                                 "one call after the other on torch's current stream, launch order strictly serial (sub_batches = 1)") + f"; library {eng.version()}",
                        "items_per_gpu": n, "global_items_per_step": total, "parallelism": f"shard x{world}, no collective on the data path",
                        "version": ver, "items_per_step_total": total,
@@ -770,11 +814,12 @@ def main():
         }
         # the serial rate next to the headline: `value` is the timed region ({F} batches in flight); stage_ms / roofline.kernel_ms are one call after the other
         ser = in_flight_info["serial"] if in_flight_info else None
-        line["value_serial"] = round(total / n * ser["signs_per_s" if sign else "verifies_per_s"], 1) if ser else line["value"]
-        line["ms_per_step_serial"] = ser["ms_per_step"] if ser else line["ms_per_step"]
+        if ser or F == 1:                                   # (a plain run with batches in flight has no serial pass)
+            line["value_serial"] = round(total / n * ser["signs_per_s" if sign else "verifies_per_s"], 1) if ser else line["value"]
+            line["ms_per_step_serial"] = ser["ms_per_step"] if ser else line["ms_per_step"]
         if in_flight_info:
             line["in_flight"] = in_flight_info
-        if stages:
+        if stages and a.full:
             # the kernel the roofline is about is known beforehand: the multi-scalar kernel (k_verify_msm[_s]; the signer: k_sign_hmul), 75-78 % of a step at every batch size.
             # (Round 5: picking the LONGEST stage instead dropped `roofline` from a 2^16 line once, when a hiccup in front of the first kernel made that stage read longer.)
             want = "sign_hmul" if sign else "verify_msm"
@@ -895,7 +940,7 @@ def main():
                                          "achieved_whole_path": round(whole, 1), "frac_whole_path": round(whole / mad_rate, 4),
                                          "msm_kernel_ms": msm_ms,
                                          "accounting": f"{FPMUL_SIGN_PER_ITEM if sign else FPMUL_PER_ITEM[ver]} Fp-mult/{op} x 72 MACs (SURVEY.md §8d, frozen in BASELINE.md §4)"}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(ver, sign)
             except Exception as e:
@@ -925,7 +970,7 @@ def main():
                 print(out, flush=True)
                 os._exit(0)
         threading.Thread(target=_watchdog, daemon=True).start()
-        if world == 1 and not a.no_extras and a.scaling == "weak" and a.log2_batch == 20 and not sign:
+        if a.full and world == 1 and not a.no_extras and a.scaling == "weak" and a.log2_batch == 20 and not sign:
             try:
                 line["other_workloads"] = extras(eng, dev, n, b, signed if ver == 1 else None)
             except Exception as e:

@@ -5,6 +5,7 @@
 # Counters go in their own passes, each with --kernel-trace only (never with sys/hip/hsa traces).  The profiled runs take --no-probe: the issue-rate probe kernels
 # (k_microbench) would otherwise be half of the trace.
 R=${1:-r06}
+export PLUME_BENCH_FULL=1      # every bench.py run below is a complete one (= bench.py --full): serial pass, roofline views, CPU baseline, secondary workloads
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 python3 -c "import zk_nullifier_sig_amd as p; print(p.Engine(0).version())" > gpurun_out/build_$R.txt 2>/dev/null

@@ -403,13 +403,13 @@ def test_sec1_der_scalar_marshalling(eng, kats):
 
 # ------------------------------------------------------------------------------- bench.py contract
 def test_bench_line_contract_on_a_small_preset():
-    """python bench.py --config 2 (2^16 V1 verify): one JSON line with the contract's keys, the binding roof in `roofline`, the HBM view beside it,
+    """python bench.py --full --config 2 (2^16 V1 verify): one JSON line with the contract's keys, the binding roof in `roofline`, the HBM view beside it,
     per-rank values; and the strong-scaling split of config 4's kind (V2) at a size that keeps the test short"""
     import subprocess
     import sys
     root = Path(__file__).resolve().parent.parent
     for extra, ver in ((["--config", "2"], 1), (["--scaling", "strong", "--log2-batch", "17", "--version", "2"], 2)):
-        r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=600)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1500:], r.stderr[-1500:])
         d = json.loads(lines[0])

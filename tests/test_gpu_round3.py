@@ -286,7 +286,7 @@ def test_worker_threads_numa_binding_is_reported_and_harmless(eng):
 
 
 def test_bench_multi_ctx_form_and_config3():
-    """bench.py --multi-ctx (one process, plume_init_multi, host-pointer calls from page-locked arrays) and --config 3 (the sign workload) produce contract lines"""
+    """bench.py --multi-ctx (one process, plume_init_multi, host-pointer calls from page-locked arrays) and --full --config 3 (the sign workload, with its roofline) produce contract lines"""
     import json
     import subprocess
     import sys
@@ -297,7 +297,7 @@ def test_bench_multi_ctx_form_and_config3():
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1500:], r.stderr[-3000:])
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and "plume_init_multi" in d["config"]["form"] and d["e2e_multi_ctx"]["items_per_s"] == d["value"] and d["value"] > 1e6
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--config", "3", "--log2-batch", "16", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--config", "3", "--log2-batch", "16", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1500:], r.stderr[-3000:])
     d = json.loads(lines[0])
