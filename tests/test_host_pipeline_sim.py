@@ -78,10 +78,13 @@ def test_host_side_under_asan_ubsan_on_eight_devices(builds):
     with ThreadPoolExecutor(4) as ex:
         res = list(ex.map(lambda j: (j, _run(exe, j[0], j[1], j[2])), jobs))
     _all_ok(res)
-    # the pipeline's own timeline (PLUME_HOST_TRACE=1: six timing events per piece, read after the call) through the same runs
-    r = _run(exe, "verify", None, 4, {"PLUME_HOST_TRACE": "1"})
-    _all_ok([("host trace", r)])
-    assert "plume_host_trace:" in r.stderr and "piece  1 lane" in r.stderr
+    # the pipeline's own timeline (PLUME_HOST_TRACE=1: six timing events per piece, read after the call) through the same runs.  Both groups run calls
+    # on pageable arrays (one lane) and on page-locked ones (two lanes): a page-lock check that misses or misjudges an array fails here
+    for group in ("verify", "sign"):
+        r = _run(exe, group, None, 4, {"PLUME_HOST_TRACE": "1"})
+        _all_ok([(f"host trace, {group}", r)])
+        assert "plume_host_trace:" in r.stderr and "piece  1 lane" in r.stderr, group
+        assert ", one lane" in r.stderr and ", two lanes" in r.stderr, group
     # a machine with another GPU, a machine with none: refused by name, no context
     _all_ok([("gfx942", _run(exe, "noarch", None, 1, {"PLUME_MOCK_ARCH": "gfx942"})), ("no device", _run(exe, "noarch", None, 1, {"PLUME_MOCK_DEVICES": "0"}))])
 

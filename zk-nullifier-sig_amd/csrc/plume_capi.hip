@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <iterator>
 #include <map>
 #include <mutex>
 #include <cerrno>
@@ -883,15 +884,39 @@ static int args_ok(int version, size_t n, const void* msgs, const void* off) {
     if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
     return 0;
 }
+// One argument check per operation, shared by its host-pointer and device-resident forms.  verify_non_zk passes its digest_private as c.
+static int verify_args_ok(int version, int mode, size_t n, const void* msgs, const void* off, const void* pk, const void* nul, const void* c, const void* s, const void* rpt,
+                          const void* hr, const void* ok) {
+    if (int rc = args_ok(version, n, msgs, off)) return rc;
+    if (n && (!pk || !nul || !c || !s || !ok || (mode == PLUME_MODE_NON_ZK && (!rpt || !hr)))) return fail(PLUME_ERR_ARG, "null array");
+    if (n && version == 1 && (!rpt || !hr)) return fail(PLUME_ERR_ARG, "V1 needs r_point and hashed_to_curve_r");
+    return 0;
+}
+static int sign_args_ok(int version, size_t n, const void* msgs, const void* off, const void* sk, const void* r, const void* nul, const void* c, const void* s, const void* rpt,
+                        const void* hr, const void* status) {
+    if (int rc = args_ok(version, n, msgs, off)) return rc;
+    if (n && (!sk || !r || !nul || !c || !s || !rpt || !hr || !status)) return fail(PLUME_ERR_ARG, "null array");
+    return 0;
+}
+static int h2c_args_ok(size_t n, const void* msgs, const void* off, const void* h_out) {
+    if (int rc = args_ok(1, n, msgs, off)) return rc;
+    if (n && !h_out) return fail(PLUME_ERR_ARG, "null array");
+    return 0;
+}
+// hints_call: the hints form, whose one output is required (the intermediates form may ask for any of its four)
+static int h2c_inter_args_ok(size_t n, const void* msgs, const void* off, int registers, bool hints_call, const void* hints) {
+    if (hints_call && n && !hints) return fail(PLUME_ERR_ARG, "null array");
+    if (int rc = args_ok(1, n, msgs, off)) return rc;
+    if (registers != 0 && registers != 1) return fail(PLUME_ERR_ARG, "registers must be 0 or 1");
+    return 0;
+}
 
 extern "C" int plume_verify_batch_device(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes,
                                          const uint8_t* pk, const uint8_t* nullifier, const uint8_t* c, const uint8_t* s, const uint8_t* r_point,
                                          const uint8_t* hashed_to_curve_r, uint8_t* ok, void* stream) {
     Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
     if (int rc = bind(ctx)) return rc;
-    if (int rc = args_ok(version, n, msgs, msg_off)) return rc;
-    if (n && (!pk || !nullifier || !c || !s || !ok)) return fail(PLUME_ERR_ARG, "null array");
-    if (n && version == 1 && (!r_point || !hashed_to_curve_r)) return fail(PLUME_ERR_ARG, "V1 needs r_point and hashed_to_curve_r");
+    if (int rc = verify_args_ok(version, PLUME_MODE_VERIFY, n, msgs, msg_off, pk, nullifier, c, s, r_point, hashed_to_curve_r, ok)) return rc;
     return verify_device(ctx, version, PLUME_MODE_VERIFY, n, msgs, msg_off, msgs_bytes, pk, nullifier, c, s, version == 1 ? r_point : nullptr,
                          version == 1 ? hashed_to_curve_r : nullptr, ok, st_);
 }
@@ -902,8 +927,7 @@ extern "C" int plume_verify_non_zk_batch_device(plume_ctx* ctx, int version, siz
                                                 const uint8_t* hashed_to_curve_r, const uint8_t* digest_private, uint8_t* ok, void* stream) {
     Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
     if (int rc = bind(ctx)) return rc;
-    if (int rc = args_ok(version, n, msgs, msg_off)) return rc;
-    if (n && (!pk || !nullifier || !s || !r_point || !hashed_to_curve_r || !digest_private || !ok)) return fail(PLUME_ERR_ARG, "null array");
+    if (int rc = verify_args_ok(version, PLUME_MODE_NON_ZK, n, msgs, msg_off, pk, nullifier, digest_private, s, r_point, hashed_to_curve_r, ok)) return rc;
     return verify_device(ctx, version, PLUME_MODE_NON_ZK, n, msgs, msg_off, msgs_bytes, pk, nullifier, digest_private, s, r_point, hashed_to_curve_r, ok,
                          st_);
 }
@@ -937,9 +961,7 @@ extern "C" int plume_verify_batch_sec1_device(plume_ctx* ctx, int version, size_
                                               const uint8_t* hashed_to_curve_r33, uint8_t* ok, void* stream) {
     Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
     if (int rc = bind(ctx)) return rc;
-    if (int rc = args_ok(version, n, msgs, msg_off)) return rc;
-    if (n && (!pk33 || !nullifier33 || !c || !s || !ok)) return fail(PLUME_ERR_ARG, "null array");
-    if (n && version == 1 && (!r_point33 || !hashed_to_curve_r33)) return fail(PLUME_ERR_ARG, "V1 needs r_point and hashed_to_curve_r");
+    if (int rc = verify_args_ok(version, PLUME_MODE_VERIFY, n, msgs, msg_off, pk33, nullifier33, c, s, r_point33, hashed_to_curve_r33, ok)) return rc;
     return verify_sec1_device(ctx, version, n, msgs, msg_off, msgs_bytes, pk33, nullifier33, c, s, r_point33, hashed_to_curve_r33, ok, st_);
 }
 
@@ -948,8 +970,7 @@ extern "C" int plume_sign_batch_device(plume_ctx* ctx, int version, size_t n, co
                                        uint8_t* hashed_to_curve_r, uint8_t* status, void* stream) {
     Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
     if (int rc = bind(ctx)) return rc;
-    if (int rc = args_ok(version, n, msgs, msg_off)) return rc;
-    if (n && (!sk || !r || !nullifier || !c || !s || !r_point || !hashed_to_curve_r || !status)) return fail(PLUME_ERR_ARG, "null array");
+    if (int rc = sign_args_ok(version, n, msgs, msg_off, sk, r, nullifier, c, s, r_point, hashed_to_curve_r, status)) return rc;
     return sign_device(ctx, version, n, msgs, msg_off, msgs_bytes, sk, r, pk_in, pk, nullifier, c, s, r_point, hashed_to_curve_r, status, nullptr,
                        st_);
 }
@@ -959,17 +980,13 @@ extern "C" int plume_sign_batch_sec1_device(plume_ctx* ctx, int version, size_t 
                                             uint8_t* hashed_to_curve_r33, uint8_t* status, void* stream) {
     Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
     if (int rc = bind(ctx)) return rc;
-    if (int rc = args_ok(version, n, msgs, msg_off)) return rc;
-    if (n && (!sk || !r || !nullifier33 || !c || !s || !r_point33 || !hashed_to_curve_r33 || !status)) return fail(PLUME_ERR_ARG, "null array");
+    if (int rc = sign_args_ok(version, n, msgs, msg_off, sk, r, nullifier33, c, s, r_point33, hashed_to_curve_r33, status)) return rc;
     return sign_device(ctx, version, n, msgs, msg_off, msgs_bytes, sk, r, pk_in, pk33, nullifier33, c, s, r_point33, hashed_to_curve_r33, status, nullptr,
                        st_, true);
 }
 
-// unrouted bodies: the host-pointer paths call these on the context itself (host calls never go to a lane: host_pipeline), the extern "C" wrappers route first
+// unchecked bodies: the host-pointer paths call these on the context itself (host calls never go to a lane: host_pipeline), the extern "C" wrappers check first
 static int h2c_only_device(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, const uint8_t* pk, uint8_t* h_out, hipStream_t st) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = args_ok(1, n, msgs, msg_off)) return rc;
-    if (n && !h_out) return fail(PLUME_ERR_ARG, "null array");
     if (n == 0) return 0;
     H2cArgs a; a.n = (uint32_t)n; a.msgs = msgs; a.msg_off = msg_off; a.msgs_bytes = msgs_bytes; a.pk = pk; a.h_out = h_out;
     ctx->timer.begin(st);
@@ -980,15 +997,14 @@ static int h2c_only_device(plume_ctx* ctx, size_t n, const uint8_t* msgs, const 
 extern "C" int plume_hash_to_curve_batch_device(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, const uint8_t* pk,
                                                 uint8_t* h_out, void* stream) {
     Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = h2c_args_ok(n, msgs, msg_off, h_out)) return rc;
     return h2c_only_device(ctx, n, msgs, msg_off, msgs_bytes, pk, h_out, st_);
 }
 
 // ------------------------------------------------------------------------------ circuit witness hints
 static int h2c_inter_device(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, const uint8_t* pk, int registers, uint8_t* u,
                             uint8_t* mapped, uint8_t* q, uint8_t* h, uint8_t* hints, void* stream) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = args_ok(1, n, msgs, msg_off)) return rc;
-    if (registers != 0 && registers != 1) return fail(PLUME_ERR_ARG, "registers must be 0 or 1");
     if (n == 0) return 0;
     H2cInterArgs a;
     a.n = (uint32_t)n; a.msgs = msgs; a.msg_off = msg_off; a.msgs_bytes = msgs_bytes; a.pk = pk; a.registers = registers; a.u = u; a.mapped = mapped; a.q = q; a.h = h; a.hints = hints;
@@ -1000,12 +1016,15 @@ static int h2c_inter_device(plume_ctx* ctx, size_t n, const uint8_t* msgs, const
 }
 extern "C" int plume_h2c_intermediates_batch_device(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, const uint8_t* pk,
                                                     int registers, uint8_t* u, uint8_t* mapped, uint8_t* q, uint8_t* h, void* stream) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = h2c_inter_args_ok(n, msgs, msg_off, registers, false, nullptr)) return rc;
     return h2c_inter_device(ctx, n, msgs, msg_off, msgs_bytes, pk, registers, u, mapped, q, h, nullptr, stream);
 }
 // the square-root hints of the two maps (UNPINNED definitions, include/plume_hip.h): n x 192 bytes
 extern "C" int plume_h2c_hints_batch_device(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, const uint8_t* pk, int registers,
                                             uint8_t* hints, void* stream) {
-    if (n && !hints) return fail(PLUME_ERR_ARG, "null array");
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = h2c_inter_args_ok(n, msgs, msg_off, registers, true, hints)) return rc;
     return h2c_inter_device(ctx, n, msgs, msg_off, msgs_bytes, pk, registers, nullptr, nullptr, nullptr, nullptr, hints, stream);
 }
 static int der_device(plume_ctx* ctx, size_t n, const uint8_t* scalars, uint8_t* der109, uint8_t* status, hipStream_t st) {
@@ -1377,114 +1396,129 @@ static int host_pipeline(plume_ctx* ctx, size_t n, bool out_heavy, Up up, Run ru
     return rc;
 }
 
-// one single-device context, items [0, n) of the arrays given (a shard of a multi-device call passes offset pointers; msg_off keeps the
-// caller's absolute offsets into the same msgs buffer)
-static int verify_host(plume_ctx* ctx, int version, int mode, bool sec1, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, const uint8_t* nullifier,
-                       const uint8_t* c, const uint8_t* s, const uint8_t* r_point, const uint8_t* hashed_to_curve_r, uint8_t* ok) {
-    HIPCHK(hipSetDevice(ctx->device));
-    const bool pts = version == 1 || mode == PLUME_MODE_NON_ZK;
-    const size_t P = sec1 ? 33 : 64;
-    ScopedPins pins;
-    if (n) {
-        pins.add(ctx, msgs + msg_off[0], (size_t)(msg_off[n] - msg_off[0]));
-        pins.add(ctx, pk, P * n); pins.add(ctx, nullifier, P * n); pins.add(ctx, c, 32 * n); pins.add(ctx, s, 32 * n);
-        if (pts) { pins.add(ctx, r_point, P * n); pins.add(ctx, hashed_to_curve_r, P * n); }
+// One host-pointer call, stated once: the caller's arrays in the order of HostSlot::in[k] / out[k].  Registration, the page-lock check for two lanes, the copies and
+// the shard offsets are all read off this table, so they cannot disagree (round 4's page-lock check listed its arrays by hand and missed some: ADVICE r4).
+struct HostArray {
+    const void* p = nullptr;   // the caller's array; null: not given
+    size_t stride = 0;         // bytes per item; 0 = unused entry
+    bool secret = false;       // an input whose staged copy is wiped once the kernels have read it
+};
+struct HostCall {
+    const uint8_t* msgs;
+    const uint64_t* msg_off;
+    HostArray in[6], out[7];
+    bool out_heavy = false, may_use_two_lanes = false;
+    // items [lo, ...) of the same call: msg_off keeps the caller's absolute offsets into the same msgs buffer
+    HostCall shard(size_t lo) const {
+        HostCall c = *this;
+        c.msg_off += lo;
+        for (HostArray& a : c.in) if (a.p) a.p = (const uint8_t*)a.p + a.stride * lo;
+        for (HostArray& a : c.out) if (a.p) a.p = (const uint8_t*)a.p + a.stride * lo;
+        return c;
     }
+};
+
+// one single-device context, items [0, n > 0) of the call.  run(slot, cnt, lane) enqueues the kernels of one piece and picks which of the slot's buffers they get;
+// every output buffer is allocated, given or not.
+template <class Run>
+static int host_call(plume_ctx* ctx, size_t n, const HostCall& call, Run run) {
+    HIPCHK(hipSetDevice(ctx->device));
+    const uint8_t* m0 = call.msgs + call.msg_off[0];
+    const size_t mbytes = (size_t)(call.msg_off[n] - call.msg_off[0]);
+    // one-byte-per-item outputs (verdicts, statuses, hash_ok) are not registered: registering them costs more than copying them
+    ScopedPins pins;
+    pins.add(ctx, m0, mbytes);
+    for (const HostArray& a : call.in) if (a.stride > 1) pins.add(ctx, a.p, a.stride * n);
+    for (const HostArray& a : call.out) if (a.stride > 1) pins.add(ctx, a.p, a.stride * n);
     // two lanes only when EVERY array of the call is page-locked: one pageable array is enough to send its copies through blit kernels, which queue behind the saturating
-    // kernels of two lanes and make the call slower than one lane would be (round 4 looked at pk and nullifier only)
-    bool all_locked = n > 0;
-    for (const void* a : {(const void*)pk, (const void*)nullifier, (const void*)c, (const void*)s, (const void*)ok, pts ? (const void*)r_point : (const void*)pk,
-                          pts ? (const void*)hashed_to_curve_r : (const void*)pk, (n && msg_off[n] > msg_off[0]) ? (const void*)(msgs + msg_off[0]) : (const void*)pk})
-        all_locked = all_locked && is_page_locked(a);
+    // kernels of two lanes and make the call slower than one lane would be
+    bool two_lanes = call.may_use_two_lanes;
+    for (const HostArray& a : call.in) two_lanes = two_lanes && (!a.p || is_page_locked(a.p));
+    for (const HostArray& a : call.out) two_lanes = two_lanes && (!a.p || is_page_locked(a.p));
+    two_lanes = two_lanes && (mbytes == 0 || is_page_locked(m0));
     return host_pipeline(
-        ctx, n, false,
+        ctx, n, call.out_heavy,
         [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
-            if (int rc = stage_msgs(ctx, sl, msgs, msg_off, i0, cnt)) return rc;
-            if (int rc = h2d(ctx, sl.in[0], pk + P * i0, P * cnt)) return rc;
-            if (int rc = h2d(ctx, sl.in[1], nullifier + P * i0, P * cnt)) return rc;
-            if (int rc = h2d(ctx, sl.in[2], c + 32 * i0, 32 * cnt)) return rc;
-            if (int rc = h2d(ctx, sl.in[3], s + 32 * i0, 32 * cnt)) return rc;
-            if (pts) {
-                if (int rc = h2d(ctx, sl.in[4], r_point + P * i0, P * cnt)) return rc;
-                if (int rc = h2d(ctx, sl.in[5], hashed_to_curve_r + P * i0, P * cnt)) return rc;
+            if (int rc = stage_msgs(ctx, sl, call.msgs, call.msg_off, i0, cnt)) return rc;
+            for (size_t k = 0; k < std::size(call.in); k++) {
+                const HostArray& a = call.in[k];
+                if (a.p) { if (int rc = h2d(ctx, sl.in[k], (const uint8_t*)a.p + a.stride * i0, a.stride * cnt)) return rc; }
             }
-            return sl.out[0].ensure(cnt);
+            for (size_t k = 0; k < std::size(call.out); k++) if (sl.out[k].ensure(call.out[k].stride * cnt)) return PLUME_ERR_HIP;
+            return 0;
         },
         [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-            const uint8_t *rp = pts ? sl.in[4].as<uint8_t>() : nullptr, *hp = pts ? sl.in[5].as<uint8_t>() : nullptr;
-            if (sec1)
-                return verify_sec1_device(on, version, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
-                                          sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(), rp, hp, sl.out[0].as<uint8_t>(), on->stream);
-            return verify_device(on, version, mode, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
-                                 sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(), rp, hp, sl.out[0].as<uint8_t>(), on->stream);
+            if (int rc = run(sl, cnt, on)) return rc;
+            // wipe the staged secrets before the slot is reused or freed
+            for (size_t k = 0; k < std::size(call.in); k++) if (call.in[k].secret) HIPCHK(hipMemsetAsync(sl.in[k].p, 0, call.in[k].stride * cnt, on->stream));
+            return 0;
         },
-        [&](HostSlot& sl, size_t i0, size_t cnt) -> int { return d2h(ctx, ok + i0, sl.out[0], cnt); }, all_locked);
+        [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
+            for (size_t k = 0; k < std::size(call.out); k++) {
+                const HostArray& a = call.out[k];
+                if (a.p) { if (int rc = d2h(ctx, (uint8_t*)a.p + a.stride * i0, sl.out[k], a.stride * cnt)) return rc; }
+            }
+            return 0;
+        },
+        two_lanes);
 }
 
-static int verify_host_any(plume_ctx* ctx, int version, int mode, bool sec1, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, const uint8_t* nullifier,
-                           const uint8_t* c, const uint8_t* s, const uint8_t* r_point, const uint8_t* hashed_to_curve_r, uint8_t* ok) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = args_ok(version, n, msgs, msg_off)) return rc;
-    if (n && (!pk || !nullifier || !c || !s || !ok)) return fail(PLUME_ERR_ARG, "null array");
-    const bool pts = version == 1 || mode == PLUME_MODE_NON_ZK;
-    if (n && pts && (!r_point || !hashed_to_curve_r)) return fail(PLUME_ERR_ARG, "r_point and hashed_to_curve_r are required");
+// a context of either kind, arguments already checked: a multi-device context runs every shard's items on that shard
+template <class Run>
+static int host_call_any(plume_ctx* ctx, size_t n, const HostCall& call, Run run) {
     if (n == 0) return 0;
+    if (ctx->shards.empty()) return host_call(ctx, n, call, run);
+    return for_shards(ctx, n, [&](plume_ctx* sh, size_t lo, size_t hi) -> int { return host_call(sh, hi - lo, call.shard(lo), run); });
+}
+
+// verify, verify_sec1 (33-byte points) and verify_non_zk (c = digest_private)
+static int verify_host(plume_ctx* ctx, int version, int mode, bool sec1, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, const uint8_t* nullifier,
+                       const uint8_t* c, const uint8_t* s, const uint8_t* r_point, const uint8_t* hashed_to_curve_r, uint8_t* ok) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = verify_args_ok(version, mode, n, msgs, msg_off, pk, nullifier, c, s, r_point, hashed_to_curve_r, ok)) return rc;
+    const bool pts = version == 1 || mode == PLUME_MODE_NON_ZK;       // V2 verify takes no R, Hr
     const size_t P = sec1 ? 33 : 64;
-    if (ctx->shards.empty()) return verify_host(ctx, version, mode, sec1, n, msgs, msg_off, pk, nullifier, c, s, pts ? r_point : nullptr, pts ? hashed_to_curve_r : nullptr, ok);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
-        return verify_host(sh, version, mode, sec1, hi - lo, msgs, msg_off + lo, pk + P * lo, nullifier + P * lo, c + 32 * lo, s + 32 * lo, pts ? r_point + P * lo : nullptr,
-                           pts ? hashed_to_curve_r + P * lo : nullptr, ok + lo);
+    const HostCall call{msgs, msg_off, {{pk, P}, {nullifier, P}, {c, 32}, {s, 32}, {pts ? r_point : nullptr, P}, {pts ? hashed_to_curve_r : nullptr, P}}, {{ok, 1}}, false, true};
+    return host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        const uint8_t *rp = pts ? sl.in[4].as<uint8_t>() : nullptr, *hp = pts ? sl.in[5].as<uint8_t>() : nullptr;
+        if (sec1)
+            return verify_sec1_device(on, version, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
+                                      sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(), rp, hp, sl.out[0].as<uint8_t>(), on->stream);
+        return verify_device(on, version, mode, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
+                             sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(), rp, hp, sl.out[0].as<uint8_t>(), on->stream);
     });
 }
 
 extern "C" int plume_verify_batch(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk,
                                   const uint8_t* nullifier, const uint8_t* c, const uint8_t* s, const uint8_t* r_point, const uint8_t* hashed_to_curve_r,
                                   uint8_t* ok) {
-    return verify_host_any(ctx, version, PLUME_MODE_VERIFY, false, n, msgs, msg_off, pk, nullifier, c, s, r_point, hashed_to_curve_r, ok);
+    return verify_host(ctx, version, PLUME_MODE_VERIFY, false, n, msgs, msg_off, pk, nullifier, c, s, r_point, hashed_to_curve_r, ok);
 }
 extern "C" int plume_verify_batch_sec1(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk33,
                                        const uint8_t* nullifier33, const uint8_t* c, const uint8_t* s, const uint8_t* r_point33,
                                        const uint8_t* hashed_to_curve_r33, uint8_t* ok) {
-    return verify_host_any(ctx, version, PLUME_MODE_VERIFY, true, n, msgs, msg_off, pk33, nullifier33, c, s, r_point33, hashed_to_curve_r33, ok);
+    return verify_host(ctx, version, PLUME_MODE_VERIFY, true, n, msgs, msg_off, pk33, nullifier33, c, s, r_point33, hashed_to_curve_r33, ok);
 }
 extern "C" int plume_verify_non_zk_batch(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk,
                                          const uint8_t* nullifier, const uint8_t* s, const uint8_t* r_point, const uint8_t* hashed_to_curve_r,
                                          const uint8_t* digest_private, uint8_t* ok) {
-    return verify_host_any(ctx, version, PLUME_MODE_NON_ZK, false, n, msgs, msg_off, pk, nullifier, digest_private, s, r_point, hashed_to_curve_r, ok);
+    return verify_host(ctx, version, PLUME_MODE_NON_ZK, false, n, msgs, msg_off, pk, nullifier, digest_private, s, r_point, hashed_to_curve_r, ok);
 }
 
 // aggregate check over host arrays: the pieces of the batch run through the same three-stream pipeline; every piece adds its sum to the running
 // record kept in HBM (coefficients are indexed by the item's position in the WHOLE batch, so the record does not depend on how the batch was cut)
-static int aggregate_host(plume_ctx* ctx, int version, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, const uint8_t* nullifier,
-                          const uint8_t* c, const uint8_t* s, const uint8_t* r_point, const uint8_t* hashed_to_curve_r, const uint8_t* seed, uint64_t index_base,
-                          uint8_t* hash_ok, uint8_t* record) {
+static int aggregate_host(plume_ctx* ctx, int version, int mode, size_t n, const HostCall& call, const uint8_t* seed, uint64_t index_base, uint8_t* record) {
     HIPCHK(hipSetDevice(ctx->device));
     if (ctx->agg_record.ensure(PLUME_AGG_RESULT_BYTES)) return PLUME_ERR_HIP;
     uint8_t* rec = ctx->agg_record.as<uint8_t>();
-    ScopedPins pins;
-    pins.add(ctx, msgs + msg_off[0], (size_t)(msg_off[n] - msg_off[0]));
-    pins.add(ctx, pk, 64 * n); pins.add(ctx, nullifier, 64 * n); pins.add(ctx, c, 32 * n); pins.add(ctx, s, 32 * n); pins.add(ctx, r_point, 64 * n); pins.add(ctx, hashed_to_curve_r, 64 * n);
     size_t done = 0;
-    int rc = host_pipeline(
-        ctx, n, false,
-        [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
-            if (int r = stage_msgs(ctx, sl, msgs, msg_off, i0, cnt)) return r;
-            if (int r = h2d(ctx, sl.in[0], pk + 64 * i0, 64 * cnt)) return r;
-            if (int r = h2d(ctx, sl.in[1], nullifier + 64 * i0, 64 * cnt)) return r;
-            if (int r = h2d(ctx, sl.in[2], c + 32 * i0, 32 * cnt)) return r;
-            if (int r = h2d(ctx, sl.in[3], s + 32 * i0, 32 * cnt)) return r;
-            if (int r = h2d(ctx, sl.in[4], r_point + 64 * i0, 64 * cnt)) return r;
-            if (int r = h2d(ctx, sl.in[5], hashed_to_curve_r + 64 * i0, 64 * cnt)) return r;
-            return sl.out[0].ensure(cnt);
-        },
-        [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-            const int r = aggregate_device(ctx, version, mode, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
-                                           sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(), sl.in[4].as<uint8_t>(), sl.in[5].as<uint8_t>(), seed, index_base + done, sl.out[0].as<uint8_t>(),
-                                           done ? rec : nullptr, rec, ctx->stream);
-            done += cnt;
-            return r;
-        },
-        [&](HostSlot& sl, size_t i0, size_t cnt) -> int { return hash_ok ? d2h(ctx, hash_ok + i0, sl.out[0], cnt) : 0; });
+    int rc = host_call(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx*) -> int {
+        const int r = aggregate_device(ctx, version, mode, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
+                                       sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(), sl.in[4].as<uint8_t>(), sl.in[5].as<uint8_t>(), seed, index_base + done, sl.out[0].as<uint8_t>(),
+                                       done ? rec : nullptr, rec, ctx->stream);
+        done += cnt;
+        return r;
+    });
     if (rc) return rc;
     HIPCHK(hipMemcpy(record, rec, PLUME_AGG_RESULT_BYTES, hipMemcpyDeviceToHost));
     return 0;
@@ -1500,16 +1534,16 @@ extern "C" int plume_aggregate_check(plume_ctx* ctx, int version, int mode, size
     uint8_t drawn[32];
     seed = agg_seed(seed, drawn);                                   // one seed for all pieces and shards of the call
     if (!seed) return fail(PLUME_ERR_HIP, "getrandom failed: no seed for the aggregate check's coefficients");
-    if (ctx->shards.empty()) return aggregate_host(ctx, version, mode, n, msgs, msg_off, pk, nullifier, c, s, r_point, hashed_to_curve_r, seed, 0, hash_ok, result);
+    const HostCall call{msgs, msg_off, {{pk, 64}, {nullifier, 64}, {c, 32}, {s, 32}, {r_point, 64}, {hashed_to_curve_r, 64}}, {{hash_ok, 1}}};
+    if (ctx->shards.empty()) return aggregate_host(ctx, version, mode, n, call, seed, 0, result);
     const size_t g = ctx->shards.size();
     std::vector<uint8_t> records(PLUME_AGG_RESULT_BYTES * g, 0);       // an empty shard leaves zeros: the identity, no bad item
     uint8_t* recs = records.data();
     plume_ctx* const* shards = ctx->shards.data();
-    int rc = for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
+    int rc = for_shards(ctx, n, [&](plume_ctx* sh, size_t lo, size_t hi) -> int {
         size_t d = 0;
         while (shards[d] != sh) d++;
-        return aggregate_host(sh, version, mode, hi - lo, msgs, msg_off + lo, pk + 64 * lo, nullifier + 64 * lo, c + 32 * lo, s + 32 * lo, r_point + 64 * lo,
-                              hashed_to_curve_r + 64 * lo, seed, (uint64_t)lo, hash_ok ? hash_ok + lo : nullptr, recs + PLUME_AGG_RESULT_BYTES * d);
+        return aggregate_host(sh, version, mode, hi - lo, call.shard(lo), seed, (uint64_t)lo, recs + PLUME_AGG_RESULT_BYTES * d);
     });
     if (rc) return rc;
     // the shards' records are added up on the first shard's GPU
@@ -1524,144 +1558,59 @@ extern "C" int plume_aggregate_check(plume_ctx* ctx, int version, int mode, size
     return 0;
 }
 
+// sign and sign_sec1 (P = 33: SEC1 output points)
 static int sign_host(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* sk, const uint8_t* r,
                      const uint8_t* pk_in, uint8_t* pk, uint8_t* nullifier, uint8_t* c, uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r,
                      uint8_t* status, const size_t P /* bytes per output point record: 64, or 33 for SEC1 */) {
-    HIPCHK(hipSetDevice(ctx->device));
-    ScopedPins pins;
-    if (n) {
-        pins.add(ctx, msgs + msg_off[0], (size_t)(msg_off[n] - msg_off[0]));
-        pins.add(ctx, sk, 32 * n); pins.add(ctx, r, 32 * n); pins.add(ctx, pk_in, 64 * n);
-        pins.add(ctx, pk, P * n); pins.add(ctx, nullifier, P * n); pins.add(ctx, c, 32 * n); pins.add(ctx, s, 32 * n); pins.add(ctx, r_point, P * n); pins.add(ctx, hashed_to_curve_r, P * n);
-    }
-    // two lanes (round 5) under the same condition as the verifier: every array of the call page-locked
-    bool sign_two_lanes = n > 0 && ctx->host_sign_lanes > 1;
-    for (const void* a : {(const void*)sk, (const void*)r, (const void*)nullifier, (const void*)c, (const void*)s, (const void*)r_point, (const void*)hashed_to_curve_r, (const void*)status,
-                          pk ? (const void*)pk : (const void*)sk, pk_in ? (const void*)pk_in : (const void*)sk, (n && msg_off[n] > msg_off[0]) ? (const void*)(msgs + msg_off[0]) : (const void*)sk})
-        sign_two_lanes = sign_two_lanes && is_page_locked(a);
-    return host_pipeline(
-        ctx, n, true,
-        [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
-            if (int rc = stage_msgs(ctx, sl, msgs, msg_off, i0, cnt)) return rc;
-            if (int rc = h2d(ctx, sl.in[0], sk + 32 * i0, 32 * cnt)) return rc;
-            if (int rc = h2d(ctx, sl.in[1], r + 32 * i0, 32 * cnt)) return rc;
-            if (pk_in) { if (int rc = h2d(ctx, sl.in[2], pk_in + 64 * i0, 64 * cnt)) return rc; }
-            return sl.out[0].ensure(P * cnt) || sl.out[1].ensure(P * cnt) || sl.out[2].ensure(32 * cnt) || sl.out[3].ensure(32 * cnt) || sl.out[4].ensure(P * cnt) ||
-                           sl.out[5].ensure(P * cnt) || sl.out[6].ensure(cnt)
-                       ? PLUME_ERR_HIP
-                       : 0;
-        },
-        [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-            if (int rc = sign_device(on, version, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
-                                     pk_in ? sl.in[2].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(),
-                                     sl.out[3].as<uint8_t>(), sl.out[4].as<uint8_t>(), sl.out[5].as<uint8_t>(), sl.out[6].as<uint8_t>(), nullptr, on->stream, P == 33))
-                return rc;
-            // wipe the staged secrets before the slot is reused or freed
-            HIPCHK(hipMemsetAsync(sl.in[0].p, 0, 32 * cnt, on->stream));
-            HIPCHK(hipMemsetAsync(sl.in[1].p, 0, 32 * cnt, on->stream));
-            return 0;
-        },
-        [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
-            if (pk) { if (int rc = d2h(ctx, pk + P * i0, sl.out[0], P * cnt)) return rc; }
-            if (int rc = d2h(ctx, nullifier + P * i0, sl.out[1], P * cnt)) return rc;
-            if (int rc = d2h(ctx, c + 32 * i0, sl.out[2], 32 * cnt)) return rc;
-            if (int rc = d2h(ctx, s + 32 * i0, sl.out[3], 32 * cnt)) return rc;
-            if (int rc = d2h(ctx, r_point + P * i0, sl.out[4], P * cnt)) return rc;
-            if (int rc = d2h(ctx, hashed_to_curve_r + P * i0, sl.out[5], P * cnt)) return rc;
-            return d2h(ctx, status + i0, sl.out[6], cnt);
-        }, sign_two_lanes);
-}
-static int sign_host_any(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* sk, const uint8_t* r,
-                         const uint8_t* pk_in, uint8_t* pk, uint8_t* nullifier, uint8_t* c, uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r,
-                         uint8_t* status, const size_t P) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = args_ok(version, n, msgs, msg_off)) return rc;
-    if (n && (!sk || !r || !nullifier || !c || !s || !r_point || !hashed_to_curve_r || !status)) return fail(PLUME_ERR_ARG, "null array");
-    if (n == 0) return 0;
-    if (ctx->shards.empty()) return sign_host(ctx, version, n, msgs, msg_off, sk, r, pk_in, pk, nullifier, c, s, r_point, hashed_to_curve_r, status, P);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
-        return sign_host(sh, version, hi - lo, msgs, msg_off + lo, sk + 32 * lo, r + 32 * lo, pk_in ? pk_in + 64 * lo : nullptr, pk ? pk + P * lo : nullptr, nullifier + P * lo,
-                         c + 32 * lo, s + 32 * lo, r_point + P * lo, hashed_to_curve_r + P * lo, status + lo, P);
+    if (int rc = sign_args_ok(version, n, msgs, msg_off, sk, r, nullifier, c, s, r_point, hashed_to_curve_r, status)) return rc;
+    // two lanes (round 5) under the same condition as the verifier (host_call)
+    const HostCall call{msgs, msg_off, {{sk, 32, true}, {r, 32, true}, {pk_in, 64}}, {{pk, P}, {nullifier, P}, {c, 32}, {s, 32}, {r_point, P}, {hashed_to_curve_r, P}, {status, 1}},
+                        true, ctx->host_sign_lanes > 1};
+    return host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return sign_device(on, version, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
+                           pk_in ? sl.in[2].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(),
+                           sl.out[3].as<uint8_t>(), sl.out[4].as<uint8_t>(), sl.out[5].as<uint8_t>(), sl.out[6].as<uint8_t>(), nullptr, on->stream, P == 33);
     });
 }
 
 extern "C" int plume_sign_batch(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* sk, const uint8_t* r,
                                 const uint8_t* pk_in, uint8_t* pk, uint8_t* nullifier, uint8_t* c, uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r,
                                 uint8_t* status) {
-    return sign_host_any(ctx, version, n, msgs, msg_off, sk, r, pk_in, pk, nullifier, c, s, r_point, hashed_to_curve_r, status, 64);
+    return sign_host(ctx, version, n, msgs, msg_off, sk, r, pk_in, pk, nullifier, c, s, r_point, hashed_to_curve_r, status, 64);
 }
 extern "C" int plume_sign_batch_sec1(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* sk, const uint8_t* r,
                                      const uint8_t* pk_in, uint8_t* pk33, uint8_t* nullifier33, uint8_t* c, uint8_t* s, uint8_t* r_point33,
                                      uint8_t* hashed_to_curve_r33, uint8_t* status) {
-    return sign_host_any(ctx, version, n, msgs, msg_off, sk, r, pk_in, pk33, nullifier33, c, s, r_point33, hashed_to_curve_r33, status, 33);
+    return sign_host(ctx, version, n, msgs, msg_off, sk, r, pk_in, pk33, nullifier33, c, s, r_point33, hashed_to_curve_r33, status, 33);
 }
 
-static int h2c_host(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, uint8_t* h_out) {
-    HIPCHK(hipSetDevice(ctx->device));
-    return host_pipeline(
-        ctx, n, false,
-        [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
-            if (int rc = stage_msgs(ctx, sl, msgs, msg_off, i0, cnt)) return rc;
-            if (pk) { if (int rc = h2d(ctx, sl.in[0], pk + 64 * i0, 64 * cnt)) return rc; }
-            return sl.out[0].ensure(64 * cnt);
-        },
-        [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-            return h2c_only_device(ctx, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], pk ? sl.in[0].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(), ctx->stream);
-        },
-        [&](HostSlot& sl, size_t i0, size_t cnt) -> int { return d2h(ctx, h_out + 64 * i0, sl.out[0], 64 * cnt); });
-}
 extern "C" int plume_hash_to_curve_batch(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, uint8_t* h_out) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = args_ok(1, n, msgs, msg_off)) return rc;
-    if (n && !h_out) return fail(PLUME_ERR_ARG, "null array");
-    if (n == 0) return 0;
-    if (ctx->shards.empty()) return h2c_host(ctx, n, msgs, msg_off, pk, h_out);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int { return h2c_host(sh, hi - lo, msgs, msg_off + lo, pk ? pk + 64 * lo : nullptr, h_out + 64 * lo); });
+    if (int rc = h2c_args_ok(n, msgs, msg_off, h_out)) return rc;
+    const HostCall call{msgs, msg_off, {{pk, 64}}, {{h_out, 64}}};
+    return host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return h2c_only_device(on, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], pk ? sl.in[0].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(), on->stream);
+    });
 }
 
-static int h2c_inter_host(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, int registers, uint8_t* u, uint8_t* mapped, uint8_t* q,
-                          uint8_t* h, uint8_t* hints) {
-    HIPCHK(hipSetDevice(ctx->device));
-    return host_pipeline(
-        ctx, n, true,
-        [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
-            if (int rc = stage_msgs(ctx, sl, msgs, msg_off, i0, cnt)) return rc;
-            if (pk) { if (int rc = h2d(ctx, sl.in[0], pk + 64 * i0, 64 * cnt)) return rc; }
-            return sl.out[0].ensure(64 * cnt) || sl.out[1].ensure(128 * cnt) || sl.out[2].ensure(128 * cnt) || sl.out[3].ensure(64 * cnt) || sl.out[4].ensure(192 * cnt) ? PLUME_ERR_HIP : 0;
-        },
-        [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-            return h2c_inter_device(ctx, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], pk ? sl.in[0].as<uint8_t>() : nullptr, registers,
-                                    u ? sl.out[0].as<uint8_t>() : nullptr, mapped ? sl.out[1].as<uint8_t>() : nullptr, q ? sl.out[2].as<uint8_t>() : nullptr,
-                                    h ? sl.out[3].as<uint8_t>() : nullptr, hints ? sl.out[4].as<uint8_t>() : nullptr, ctx->stream);
-        },
-        [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
-            if (u) { if (int rc = d2h(ctx, u + 64 * i0, sl.out[0], 64 * cnt)) return rc; }
-            if (mapped) { if (int rc = d2h(ctx, mapped + 128 * i0, sl.out[1], 128 * cnt)) return rc; }
-            if (q) { if (int rc = d2h(ctx, q + 128 * i0, sl.out[2], 128 * cnt)) return rc; }
-            if (h) { if (int rc = d2h(ctx, h + 64 * i0, sl.out[3], 64 * cnt)) return rc; }
-            if (hints) { if (int rc = d2h(ctx, hints + 192 * i0, sl.out[4], 192 * cnt)) return rc; }
-            return 0;
-        });
-}
-static int h2c_inter_any(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, int registers, uint8_t* u, uint8_t* mapped, uint8_t* q, uint8_t* h,
-                         uint8_t* hints) {
+static int h2c_inter_host(plume_ctx* ctx, bool hints_call, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, int registers, uint8_t* u,
+                          uint8_t* mapped, uint8_t* q, uint8_t* h, uint8_t* hints) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = args_ok(1, n, msgs, msg_off)) return rc;
-    if (registers != 0 && registers != 1) return fail(PLUME_ERR_ARG, "registers must be 0 or 1");
-    if (n == 0) return 0;
-    if (ctx->shards.empty()) return h2c_inter_host(ctx, n, msgs, msg_off, pk, registers, u, mapped, q, h, hints);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
-        return h2c_inter_host(sh, hi - lo, msgs, msg_off + lo, pk ? pk + 64 * lo : nullptr, registers, u ? u + 64 * lo : nullptr, mapped ? mapped + 128 * lo : nullptr,
-                              q ? q + 128 * lo : nullptr, h ? h + 64 * lo : nullptr, hints ? hints + 192 * lo : nullptr);
+    if (int rc = h2c_inter_args_ok(n, msgs, msg_off, registers, hints_call, hints)) return rc;
+    const HostCall call{msgs, msg_off, {{pk, 64}}, {{u, 64}, {mapped, 128}, {q, 128}, {h, 64}, {hints, 192}}, true};
+    return host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return h2c_inter_device(on, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], pk ? sl.in[0].as<uint8_t>() : nullptr, registers,
+                                u ? sl.out[0].as<uint8_t>() : nullptr, mapped ? sl.out[1].as<uint8_t>() : nullptr, q ? sl.out[2].as<uint8_t>() : nullptr,
+                                h ? sl.out[3].as<uint8_t>() : nullptr, hints ? sl.out[4].as<uint8_t>() : nullptr, on->stream);
     });
 }
 extern "C" int plume_h2c_intermediates_batch(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, int registers, uint8_t* u,
                                              uint8_t* mapped, uint8_t* q, uint8_t* h) {
-    return h2c_inter_any(ctx, n, msgs, msg_off, pk, registers, u, mapped, q, h, nullptr);
+    return h2c_inter_host(ctx, false, n, msgs, msg_off, pk, registers, u, mapped, q, h, nullptr);
 }
 extern "C" int plume_h2c_hints_batch(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, int registers, uint8_t* hints) {
-    if (n && !hints) return fail(PLUME_ERR_ARG, "null array");
-    return h2c_inter_any(ctx, n, msgs, msg_off, pk, registers, nullptr, nullptr, nullptr, nullptr, hints);
+    return h2c_inter_host(ctx, true, n, msgs, msg_off, pk, registers, nullptr, nullptr, nullptr, nullptr, hints);
 }
 static int der_host(plume_ctx* ctx, size_t n, const uint8_t* scalars, uint8_t* der109, uint8_t* status) {
     HIPCHK(hipSetDevice(ctx->device));
