@@ -92,6 +92,17 @@ extern "C" {
     fn plume_shard_numa_node(ctx: *const plume_ctx, shard: c_int) -> c_int;
     fn plume_aggregate_check(ctx: *mut plume_ctx, version: c_int, mode: c_int, n: usize, msgs: *const u8, msg_off: *const u64, pk: *const u8, nullifier: *const u8, c: *const u8,
                              s: *const u8, r_point: *const u8, hashed_to_curve_r: *const u8, seed: *const u8, hash_ok: *mut u8, result: *mut u8) -> c_int;
+    fn plume_nullset_create(ctx: *mut plume_ctx, reserve_items: usize, set: *mut *mut c_void) -> c_int;
+    fn plume_nullset_destroy(set: *mut c_void);
+    fn plume_nullset_reserve(set: *mut c_void, items: usize) -> c_int;
+    fn plume_nullset_clear(set: *mut c_void) -> c_int;
+    fn plume_nullset_size(set: *mut c_void, size: *mut u64, capacity: *mut u64) -> c_int;
+    fn plume_nullset_insert(set: *mut c_void, n: usize, nullifier: *const u8, live: *const u8, ids: *const u64, fresh: *mut u8, n_fresh: *mut u64) -> c_int;
+    fn plume_nullset_contains(set: *mut c_void, n: usize, nullifier: *const u8, found: *mut u8) -> c_int;
+    fn plume_nullset_export(set: *mut c_void, cap: usize, records: *mut u8, count: *mut u64) -> c_int;
+    fn plume_nullset_insert_device(set: *mut c_void, n: usize, nullifier: *const u8, live: *const u8, ids: *const u64, fresh: *mut u8, n_fresh: *mut u64,
+                                   stream: *mut c_void) -> c_int;
+    fn plume_nullset_contains_device(set: *mut c_void, n: usize, nullifier: *const u8, found: *mut u8, stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -311,6 +322,72 @@ impl HipEngine {
     /// upload / compute / download pipeline overlaps fully.  Pair with `unpin`.
     pub fn pin(buf: &mut [u8]) -> Result<(), HipError> { if unsafe { plume_host_register(buf.as_mut_ptr() as *mut c_void, buf.len()) } == 0 { Ok(()) } else { Err(last_error()) } }
     pub fn unpin(buf: &mut [u8]) -> Result<(), HipError> { if unsafe { plume_host_unregister(buf.as_mut_ptr() as *mut c_void) } == 0 { Ok(()) } else { Err(last_error()) } }
+}
+
+// ------------------------------------------------------------------------------------------------ persistent nullifier set
+/// A GPU-resident set of nullifiers that persists across batches (`plume_nullset_*`): `insert` tells which signatures carry a nullifier for the first
+/// time EVER, across every earlier insert into the set — the check an application makes before it accepts a verified signature.  Lives on the engine's
+/// (first) GPU and may outlive the engine.  One caller thread at a time.
+pub struct NullifierSet(*mut c_void);
+unsafe impl Send for NullifierSet {}
+impl Drop for NullifierSet { fn drop(&mut self) { unsafe { plume_nullset_destroy(self.0) } } }
+
+impl NullifierSet {
+    /// An empty set with room for `reserve` records before its first growth.
+    pub fn new(engine: &HipEngine, reserve: usize) -> Result<Self, HipError> {
+        let mut h: *mut c_void = std::ptr::null_mut();
+        if unsafe { plume_nullset_create(engine.0, reserve, &mut h) } == 0 { Ok(NullifierSet(h)) } else { Err(last_error()) }
+    }
+    /// `fresh[i]`: `live[i]` (None = all), the nullifier was not in the set, and no earlier live item of this call carries it.  Returns the flags and their count;
+    /// every live nullifier is in the set afterwards.
+    pub fn insert(&self, nullifiers: &[AffinePoint], live: Option<&[bool]>) -> Result<(Vec<bool>, u64), HipError> {
+        let n = nullifiers.len();
+        if let Some(l) = live { assert_eq!(l.len(), n, "one live flag per nullifier"); }
+        let mut nul = vec![0u8; 64 * n];
+        for (i, p) in nullifiers.iter().enumerate() { put_point(&mut nul[64 * i..], p); }
+        let lv: Vec<u8> = live.map_or(Vec::new(), |l| l.iter().map(|b| *b as u8).collect());
+        let mut fresh = vec![0u8; n];
+        let mut cnt: u64 = 0;
+        let rc = unsafe { plume_nullset_insert(self.0, n, nul.as_ptr(), if live.is_some() { lv.as_ptr() } else { std::ptr::null() }, std::ptr::null(), fresh.as_mut_ptr(), &mut cnt) };
+        if rc == 0 { Ok((fresh.into_iter().map(|f| f != 0).collect(), cnt)) } else { Err(last_error()) }
+    }
+    /// Membership, read-only.
+    pub fn contains(&self, nullifiers: &[AffinePoint]) -> Result<Vec<bool>, HipError> {
+        let n = nullifiers.len();
+        let mut nul = vec![0u8; 64 * n];
+        for (i, p) in nullifiers.iter().enumerate() { put_point(&mut nul[64 * i..], p); }
+        let mut found = vec![0u8; n];
+        if unsafe { plume_nullset_contains(self.0, n, nul.as_ptr(), found.as_mut_ptr()) } == 0 { Ok(found.into_iter().map(|f| f != 0).collect()) } else { Err(last_error()) }
+    }
+    /// Number of nullifiers in the set.
+    pub fn len(&self) -> Result<u64, HipError> {
+        let (mut size, mut cap) = (0u64, 0u64);
+        if unsafe { plume_nullset_size(self.0, &mut size, &mut cap) } == 0 { Ok(size) } else { Err(last_error()) }
+    }
+    pub fn reserve(&self, items: usize) -> Result<(), HipError> { if unsafe { plume_nullset_reserve(self.0, items) } == 0 { Ok(()) } else { Err(last_error()) } }
+    pub fn clear(&self) -> Result<(), HipError> { if unsafe { plume_nullset_clear(self.0) } == 0 { Ok(()) } else { Err(last_error()) } }
+    /// Every nullifier of the set, in no particular order.
+    pub fn export(&self) -> Result<Vec<AffinePoint>, HipError> {
+        let mut cnt: u64 = 0;
+        if unsafe { plume_nullset_export(self.0, 0, std::ptr::null_mut(), &mut cnt) } != 0 { return Err(last_error()); }
+        let mut rec = vec![0u8; 64 * cnt as usize];
+        if cnt > 0 && unsafe { plume_nullset_export(self.0, cnt as usize, rec.as_mut_ptr(), &mut cnt) } != 0 { return Err(last_error()); }
+        Ok(rec.chunks(64).take(cnt as usize).map(get_point).collect())
+    }
+    /// Device form: every pointer on the set's GPU, enqueued on `stream` (null = the set's own); `n_fresh` may be null.  Does not synchronise.
+    ///
+    /// # Safety
+    /// The pointers must be valid device allocations of the sizes `plume_hip.h` states, alive until the work has run.
+    pub unsafe fn insert_device(&self, n: usize, nullifier: *const u8, live: *const u8, ids: *const u64, fresh: *mut u8, n_fresh: *mut u64, stream: *mut c_void) -> Result<(), HipError> {
+        if plume_nullset_insert_device(self.0, n, nullifier, live, ids, fresh, n_fresh, stream) == 0 { Ok(()) } else { Err(last_error()) }
+    }
+    /// Device form of `contains`.
+    ///
+    /// # Safety
+    /// As for `insert_device`.
+    pub unsafe fn contains_device(&self, n: usize, nullifier: *const u8, found: *mut u8, stream: *mut c_void) -> Result<(), HipError> {
+        if plume_nullset_contains_device(self.0, n, nullifier, found, stream) == 0 { Ok(()) } else { Err(last_error()) }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ the reference's single-item surface

@@ -13,7 +13,7 @@
 //   namespace plume_arkworks     rust-arkworks/src/lib.rs:60-291, rust-arkworks/src/tests.rs:28-78,119-124
 //       Affine, Fr, PlumeVersion, PlumeSignaturePublic / PlumeSignaturePrivate (zeroized on drop), sec1_affine, hash_to_curve, sign_with_r, sign,
 //       keygen, verify_non_zk
-//   namespace plume_hip          Engine (RAII over plume_ctx, one or several GPUs), Error
+//   namespace plume_hip          Engine (RAII over plume_ctx, one or several GPUs), Error, NullifierSet (the persistent nullifier set: insert / contains / export_all)
 //
 // Error behaviour:  the signer's `expect(..)` panics (randomizedsigner.rs:61,91,95) -> plume_rustcrypto::Panic;  `signature::Error`
 // (randomizedsigner.rs:59) -> plume_rustcrypto::SignatureError;  `HashToCurveError` (rust-arkworks/src/lib.rs:99-101) ->
@@ -493,6 +493,59 @@ inline CircuitH2cInputs circuit_h2c_inputs(const Bytes& m, const AffinePoint& pk
 }
 
 }  // namespace plume_rustcrypto
+
+namespace plume_hip {
+
+// A persistent nullifier set (plume_hip.h, plume_nullset_*): GPU-resident, it remembers every nullifier inserted into it across calls, so that an application
+// accepts ONE signature per nullifier over a stream of batches.  Lives on the engine's (first) GPU; may outlive the engine.  One host thread at a time.
+class NullifierSet {
+  public:
+    explicit NullifierSet(Engine& eng, size_t reserve = 0) { check(plume_nullset_create(eng.ctx(), reserve, &set_), "plume_nullset_create"); }
+    ~NullifierSet() { plume_nullset_destroy(set_); }
+    NullifierSet(const NullifierSet&) = delete;
+    NullifierSet& operator=(const NullifierSet&) = delete;
+    NullifierSet(NullifierSet&& o) noexcept : set_(o.set_) { o.set_ = nullptr; }
+    void* handle() const { return set_; }
+    // fresh[i]: live[i] (empty = all), the nullifier was not in the set, and no earlier live item of this call has it; every live nullifier is in the set afterwards
+    std::vector<bool> insert(const std::vector<plume_rustcrypto::AffinePoint>& nullifiers, const std::vector<bool>& live = {}, uint64_t* n_fresh = nullptr) {
+        const size_t n = nullifiers.size();
+        if (!live.empty() && live.size() != n) throw std::invalid_argument("live must be empty or hold one flag per nullifier");
+        Bytes nul = pack(nullifiers), lv(live.begin(), live.end()), fresh(n);
+        uint64_t cnt = 0;
+        check(plume_nullset_insert(set_, n, nul.data(), live.empty() ? nullptr : lv.data(), nullptr, fresh.data(), &cnt), "plume_nullset_insert");
+        if (n_fresh) *n_fresh = cnt;
+        return std::vector<bool>(fresh.begin(), fresh.end());
+    }
+    std::vector<bool> contains(const std::vector<plume_rustcrypto::AffinePoint>& nullifiers) const {
+        Bytes nul = pack(nullifiers), found(nullifiers.size());
+        check(plume_nullset_contains(set_, nullifiers.size(), nul.data(), found.data()), "plume_nullset_contains");
+        return std::vector<bool>(found.begin(), found.end());
+    }
+    uint64_t size() const { uint64_t s = 0, c = 0; check(plume_nullset_size(set_, &s, &c), "plume_nullset_size"); return s; }
+    uint64_t capacity() const { uint64_t s = 0, c = 0; check(plume_nullset_size(set_, &s, &c), "plume_nullset_size"); return c; }
+    void reserve(size_t items) { check(plume_nullset_reserve(set_, items), "plume_nullset_reserve"); }
+    void clear() { check(plume_nullset_clear(set_), "plume_nullset_clear"); }
+    // every nullifier of the set, in no particular order
+    std::vector<plume_rustcrypto::AffinePoint> export_all() const {
+        uint64_t cnt = 0;
+        check(plume_nullset_export(set_, 0, nullptr, &cnt), "plume_nullset_export");
+        Bytes rec(64 * cnt);
+        if (cnt) check(plume_nullset_export(set_, cnt, rec.data(), &cnt), "plume_nullset_export");
+        std::vector<plume_rustcrypto::AffinePoint> out(cnt);
+        for (uint64_t i = 0; i < cnt; i++) out[i] = plume_rustcrypto::AffinePoint::from_bytes64(&rec[64 * i]);
+        return out;
+    }
+
+  private:
+    static Bytes pack(const std::vector<plume_rustcrypto::AffinePoint>& pts) {
+        Bytes b(64 * pts.size());
+        for (size_t i = 0; i < pts.size(); i++) std::memcpy(&b[64 * i], pts[i].xy.data(), 64);
+        return b;
+    }
+    void* set_ = nullptr;
+};
+
+}  // namespace plume_hip
 
 // ================================================================================================ plume_arkworks shape
 namespace plume_arkworks {

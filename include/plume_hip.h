@@ -71,7 +71,7 @@ int plume_shard_numa_node(const plume_ctx* ctx, int shard);
 void plume_destroy(plume_ctx* ctx);
 /* Last error text of this thread (valid until the next failing call on the thread). */
 const char* plume_last_error(void);
-/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
+/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.7: the persistent nullifier set (plume_nullset_*); 0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
  * the signer defaults to uniform level 1; the generator tables are built by the first call that needs them; stream = NULL means the stream of the context the caller
  * holds; plume_destroy waits for the context's own work only (its last call on any stream and its private streams), not for the whole device. */
 const char* plume_version(void);
@@ -380,6 +380,38 @@ int plume_aggregate_check_device(plume_ctx* ctx, int version, int mode, size_t n
                                  const uint8_t* pk, const uint8_t* nullifier, const uint8_t* c, const uint8_t* s,
                                  const uint8_t* r_point, const uint8_t* hashed_to_curve_r,
                                  const uint8_t seed[32], uint64_t index_base, uint8_t* hash_ok, uint8_t* result, void* stream);
+
+/* ---- persistent nullifier set: reject repeats across batches  (library 0.7) ----------------------------------
+ * A consumer that verifies a STREAM of batches (a vote tally, a claim relayer, a rate limiter) must reject a nullifier it accepted any number of
+ * batches ago.  A set S is a GPU-resident table of distinct 64-byte records that persists across calls (csrc/plume_nullset.h); records are opaque
+ * and compared byte for byte, exactly as plume_nullifier_first_occurrence compares them (the all-zero identity is an ordinary record).
+ *   insert   : fresh[i] = 1 iff live[i] (live NULL = all items), nullifier[i] was not in S before the call, and no live item j of the call with the
+ *              same record has ids[j] < ids[i] (ids NULL = the position in the call; ids are distinct).  Afterwards S holds every live record;
+ *              n_fresh (optional) = the number of 1s = the growth of |S|.  Equivalently: first-occurrence marking over every live item of every
+ *              earlier insert into this set followed by this call's items, restricted to this call.  Independent of lane order, hash key and table size.
+ *   contains : found[i] = 1 iff nullifier[i] is in S (read-only).
+ *   size     : |S| and the table's capacity in slots (synchronises).   reserve: room for `items` records without growing.   clear: S = {}.
+ *   export   : every record, in no particular order.  records NULL or cap < size: *count = size and nothing is written (PLUME_ERR_ARG when records
+ *              is not NULL); otherwise the records and *count = size.  Export, then insert into another set, is the way to move or save a set.
+ * Limits: n <= 2^30 per call; |S| <= 2^31; the table is at most half full and grows by itself to the next power of two >= 2 (|S| + n).  A request above
+ * the limits returns PLUME_ERR_ARG before anything is allocated; a growth or allocation that fails returns PLUME_ERR_HIP and leaves the set unchanged and usable.
+ * The set lives on the context's device (the first shard's for a plume_init_multi context) with a stream, buffers and "last operation" event of its own:
+ * it never touches the context's workspace and may outlive the context.  The handle is used by one host thread at a time.
+ * Device forms: every data pointer is a DEVICE pointer on the set's device, n_fresh (optional) is a device pointer to one uint64_t; the work is enqueued
+ * on `stream` (NULL = the set's own stream), after the set's previous operation whatever stream that ran on; nothing synchronises, except when the host's
+ * upper bound on |S| says the call might cross half the capacity -- the exact size is read then, and a growth synchronises once before it frees the old table.
+ * Host forms synchronise before they return. */
+int plume_nullset_create(plume_ctx* ctx, size_t reserve_items, void** set);
+void plume_nullset_destroy(void* set);
+int plume_nullset_reserve(void* set, size_t items);
+int plume_nullset_clear(void* set);
+int plume_nullset_size(void* set, uint64_t* size, uint64_t* capacity);
+int plume_nullset_insert(void* set, size_t n, const uint8_t* nullifier, const uint8_t* live, const uint64_t* ids, uint8_t* fresh, uint64_t* n_fresh);
+int plume_nullset_contains(void* set, size_t n, const uint8_t* nullifier, uint8_t* found);
+int plume_nullset_export(void* set, size_t cap, uint8_t* records, uint64_t* count);
+int plume_nullset_insert_device(void* set, size_t n, const uint8_t* nullifier, const uint8_t* live, const uint64_t* ids, uint8_t* fresh, uint64_t* n_fresh,
+                                void* stream);
+int plume_nullset_contains_device(void* set, size_t n, const uint8_t* nullifier, uint8_t* found, void* stream);
 
 /* ---- measurement hooks (bench.py) -------------------------------------------------------------------------
  * Per-stage device time of the most recent *_device call on this context, measured with HIP events recorded on

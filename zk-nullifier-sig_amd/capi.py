@@ -118,11 +118,19 @@ def _load():
     lib.plume_registers_from_be_device.argtypes = [vp, sz, vp, vp, vp]
     lib.plume_aggregate_check.argtypes = [vp, i, i, sz] + [vp] * 11
     lib.plume_aggregate_check_device.argtypes = [vp, i, i, sz, vp, vp, sz] + [vp] * 7 + [C.c_uint64, vp, vp, vp]
+    # the persistent nullifier set (library 0.7; an older build selected through PLUME_HIP_LIB lacks it: NullifierSet raises PlumeHipError then)
+    for name, args, res in (("plume_nullset_create", [vp, sz, C.POINTER(C.c_void_p)], i), ("plume_nullset_destroy", [vp], None), ("plume_nullset_reserve", [vp, sz], i),
+                            ("plume_nullset_clear", [vp], i), ("plume_nullset_size", [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], i),
+                            ("plume_nullset_insert", [vp, sz, vp, vp, vp, vp, C.POINTER(C.c_uint64)], i), ("plume_nullset_contains", [vp, sz, vp, vp], i),
+                            ("plume_nullset_export", [vp, sz, vp, C.POINTER(C.c_uint64)], i), ("plume_nullset_insert_device", [vp, sz, vp, vp, vp, vp, vp, vp], i),
+                            ("plume_nullset_contains_device", [vp, sz, vp, vp, vp], i)):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes, fn.restype = args, res
     _lib = lib
-    ver = tuple(int(x) for x in lib.plume_version().decode().split()[1].split(".")[:2])
-    if ver < (0, 6) and not os.environ.get("PLUME_HIP_LIB"):
+    if _version(lib) < (0, 7) and not os.environ.get("PLUME_HIP_LIB"):
         _lib = None
-        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.6 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.7 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
     return lib
 
 
@@ -133,7 +141,9 @@ def exported_symbols():
             "plume_registers_from_be", "plume_registers_from_be_device", "plume_scalars_to_sec1_der_batch", "plume_scalars_to_sec1_der_batch_device", "plume_sec1_der_to_scalars", "plume_sec1_der_to_scalars_checked",
             "plume_init", "plume_destroy", "plume_last_error", "plume_version", "plume_set_chunk", "plume_set_host_piece", "plume_verify_batch", "plume_verify_batch_sec1", "plume_verify_batch_sec1_device", "plume_sign_batch", "plume_sign_batch_sec1", "plume_sign_batch_sec1_device",
             "plume_hash_to_curve_batch", "plume_nullifier_first_occurrence", "plume_nullifier_first_occurrence_device", "plume_verify_batch_device", "plume_sign_batch_device", "plume_hash_to_curve_batch_device",
-            "plume_last_stage_times", "plume_microbench", "plume_microbench_last_ticks"]
+            "plume_last_stage_times", "plume_microbench", "plume_microbench_last_ticks",
+            "plume_nullset_create", "plume_nullset_destroy", "plume_nullset_reserve", "plume_nullset_clear", "plume_nullset_size", "plume_nullset_insert", "plume_nullset_contains",
+            "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device"]
 
 
 def pack_messages(msgs):
@@ -554,6 +564,12 @@ class Engine:
         self._chk(self._lib.plume_nullifier_first_occurrence_device(self._ctx, int(n), d(nullifier), d(live), d(ids), d(first), d(n_unique), C.c_void_p(st)),
                   "plume_nullifier_first_occurrence_device")
 
+    # ------------------------------------------------------------------ persistent nullifier set
+    def nullifier_set(self, reserve=0):
+        """a GPU-resident set of 64-byte nullifiers that persists across calls (include/plume_hip.h, plume_nullset_*), on this context's device
+        (the first one of a multi-device engine); see NullifierSet"""
+        return NullifierSet(self, reserve)
+
     # ------------------------------------------------------------------ measurement
     def set_stage_timing(self, on):
         """per-stage timing events inside the device pipelines (plume_set_stage_timing): OFF by default since library 0.5 -- an event between two kernels costs ~6 us of idle
@@ -589,6 +605,118 @@ class Engine:
         ms = C.c_float()
         t = self._lib.plume_microbench_last_ticks(C.byref(ms))
         return float(t), float(ms.value)
+
+
+def _version(lib):
+    return tuple(int(x) for x in lib.plume_version().decode().split()[1].split(".")[:2])
+
+
+class NullifierSet:
+    """A set S of distinct 64-byte records on the GPU that persists across calls: the step after `verify` for a consumer of a stream of batches,
+    which must accept ONE signature per nullifier, ever.  insert(nullifier, live, ids) -> (fresh, n_fresh): fresh[i] = 1 iff the item is live, its
+    record was not in S before the call and no live item of the call with the same record has a smaller id (default: position); S then holds every
+    live record.  contains / export / clear / reserve / len; the *_device forms take torch tensors on the set's device and do not synchronise
+    (the set orders its operations itself, whatever streams they are issued on).  One host thread at a time.  May outlive its Engine."""
+
+    def __init__(self, engine, reserve=0):
+        lib = engine._lib
+        if getattr(lib, "plume_nullset_create", None) is None or _version(lib) < (0, 7):
+            raise PlumeHipError(f"{lib.plume_version().decode()} has no persistent nullifier set: it needs plume_hip >= 0.7 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        self._lib = lib
+        self.device_id = engine.device_id
+        self._h = C.c_void_p()
+        rc = lib.plume_nullset_create(engine._ctx, int(reserve), C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            raise PlumeHipError(f"plume_nullset_create failed ({rc}): {lib.plume_last_error().decode()}")
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise PlumeHipError(f"{what} failed ({rc}): {self._lib.plume_last_error().decode()}")
+
+    def _handle(self):
+        if not self._h:
+            raise PlumeHipError("the nullifier set is closed")
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.plume_nullset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _size(self):
+        size, cap = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._lib.plume_nullset_size(self._handle(), C.byref(size), C.byref(cap)), "plume_nullset_size")
+        return int(size.value), int(cap.value)
+
+    def __len__(self):
+        return self._size()[0]
+
+    @property
+    def capacity(self):
+        """slots of the table (a power of two, at least twice the size)"""
+        return self._size()[1]
+
+    def reserve(self, items):
+        self._chk(self._lib.plume_nullset_reserve(self._handle(), int(items)), "plume_nullset_reserve")
+
+    def clear(self):
+        self._chk(self._lib.plume_nullset_clear(self._handle()), "plume_nullset_clear")
+
+    def insert(self, nullifier, live=None, ids=None):
+        """numpy in / out: (fresh uint8[n], number of fresh items)"""
+        nullifier = np.ascontiguousarray(nullifier, dtype=np.uint8).reshape(-1, 64)
+        n = len(nullifier)
+        live = None if live is None else np.ascontiguousarray(live, dtype=np.uint8).reshape(n)
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint64).reshape(n)
+        fresh = np.zeros(n, dtype=np.uint8)
+        cnt = C.c_uint64(0)
+        self._chk(self._lib.plume_nullset_insert(self._handle(), n, _ptr(nullifier), _ptr(live), _ptr(ids), _ptr(fresh), C.byref(cnt)), "plume_nullset_insert")
+        return fresh, int(cnt.value)
+
+    def contains(self, nullifier):
+        """numpy in / out: found uint8[n]"""
+        nullifier = np.ascontiguousarray(nullifier, dtype=np.uint8).reshape(-1, 64)
+        found = np.zeros(len(nullifier), dtype=np.uint8)
+        self._chk(self._lib.plume_nullset_contains(self._handle(), len(nullifier), _ptr(nullifier), _ptr(found)), "plume_nullset_contains")
+        return found
+
+    def export(self):
+        """every record, uint8[len, 64], in no particular order"""
+        cnt = C.c_uint64(0)
+        self._chk(self._lib.plume_nullset_export(self._handle(), 0, None, C.byref(cnt)), "plume_nullset_export")
+        out = np.zeros((int(cnt.value), 64), dtype=np.uint8)
+        if len(out):
+            self._chk(self._lib.plume_nullset_export(self._handle(), len(out), _ptr(out), C.byref(cnt)), "plume_nullset_export")
+        return out[:int(cnt.value)]
+
+    def _stream(self, stream):
+        import torch
+        return (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+
+    def insert_device(self, n, nullifier, live, ids, fresh, n_fresh=None, stream=None):
+        """tensors on the set's device (nullifier n x 64 uint8, live / fresh uint8[n] or None, ids int64/uint64[n] or None, n_fresh one 64-bit word or None);
+        enqueued on `stream` (torch.cuda.Stream or None = the current stream); does not synchronise.  torch's default stream has the handle 0, which the library
+        reads as "the set's own stream": to chain an insert behind other work (a verify_batch_device), issue both on one non-default torch stream"""
+        d = Engine._dp
+        self._chk(self._lib.plume_nullset_insert_device(self._handle(), int(n), d(nullifier), d(live), d(ids), d(fresh), d(n_fresh), C.c_void_p(self._stream(stream))),
+                  "plume_nullset_insert_device")
+
+    def contains_device(self, n, nullifier, found, stream=None):
+        d = Engine._dp
+        self._chk(self._lib.plume_nullset_contains_device(self._handle(), int(n), d(nullifier), d(found), C.c_void_p(self._stream(stream))), "plume_nullset_contains_device")
 
 
 _default = None

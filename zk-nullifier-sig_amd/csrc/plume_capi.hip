@@ -24,6 +24,7 @@
 
 #include "../../include/plume_hip.h"
 #include "plume_agg_launch.h"
+#include "plume_capi_internal.h"
 #include "plume_host_logic.h"
 #include "plume_launch.h"
 
@@ -274,7 +275,7 @@ extern "C" const char* plume_last_error(void) { return g_err.c_str(); }
 #ifndef PLUME_BUILD_ID
 #define PLUME_BUILD_ID "unknown"
 #endif
-extern "C" const char* plume_version(void) { return "plume_hip 0.6 gfx950 build=" PLUME_BUILD_ID; }
+extern "C" const char* plume_version(void) { return "plume_hip 0.7 gfx950 build=" PLUME_BUILD_ID; }
 
 static void destroy_single(plume_ctx* ctx) {
     for (plume_ctx* l : ctx->lanes) destroy_single(l);
@@ -1156,6 +1157,14 @@ static bool os_random(void* out, size_t len) {
     }
     return true;
 }
+// services for the library's other translation units (plume_capi_internal.h)
+int plume::capi_fail(int code, const char* msg) { return fail(code, msg); }
+int plume::capi_ctx_device(const plume_ctx* ctx, int* device) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    *device = ctx->shards.empty() ? ctx->device : ctx->shards[0]->device;
+    return 0;
+}
+bool plume::capi_os_random(void* out, size_t len) { return os_random(out, len); }
 static const uint8_t* agg_seed(const uint8_t* seed, uint8_t drawn[32]) {      // nullptr: the OS generator failed
     if (seed) return seed;
     return os_random(drawn, 32) ? drawn : nullptr;
