@@ -103,6 +103,10 @@ extern "C" {
     fn plume_nullset_insert_device(set: *mut c_void, n: usize, nullifier: *const u8, live: *const u8, ids: *const u64, fresh: *mut u8, n_fresh: *mut u64,
                                    stream: *mut c_void) -> c_int;
     fn plume_nullset_contains_device(set: *mut c_void, n: usize, nullifier: *const u8, found: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_sign_batch_rfc6979(ctx: *mut plume_ctx, version: c_int, n: usize, msgs: *const u8, msg_off: *const u64, sk: *const u8, aux: *const u8, pk_in: *const u8,
+        pk: *mut u8, nullifier: *mut u8, c: *mut u8, s: *mut u8, r_point: *mut u8, hashed_to_curve_r: *mut u8, status: *mut u8) -> c_int;
+    fn plume_sign_batch_rfc6979_device(ctx: *mut plume_ctx, version: c_int, n: usize, msgs: *const u8, msg_off: *const u64, msgs_bytes: usize, sk: *const u8, aux: *const u8,
+        pk_in: *const u8, pk: *mut u8, nullifier: *mut u8, c: *mut u8, s: *mut u8, r_point: *mut u8, hashed_to_curve_r: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -234,19 +238,30 @@ impl HipEngine {
         sk.iter_mut().for_each(|b| *b = 0);   // the reference zeroizes its secrets (SecretKey: ZeroizeOnDrop); so does the library on the device
         r.iter_mut().for_each(|b| *b = 0);
         if rc != 0 { return Err(last_error()); }
-        Ok((0..n).map(|i| {
-            let st = status[i];
-            let nullifier = get_point(&nul[64 * i..]);
-            if st & PLUME_STATUS_BAD_SCALAR != 0 { return Err(SignError::BadScalar); }
-            if st & PLUME_STATUS_IDENTITY != 0 && nullifier == AffinePoint::IDENTITY { return Err(SignError::HashedToIdentity); }     // :61
-            if st & PLUME_STATUS_C_NOT_CANONICAL != 0 { return Err(SignError::ChallengeNotCanonical); }                           // :91
-            if st & PLUME_STATUS_IDENTITY != 0 { return Err(SignError::ZeroResponse); }                                             // :95
-            Ok(PlumeSignature {
-                message: msgs[i].to_vec(), pk: get_point(&pk[64 * i..]), nullifier,
-                c: get_scalar(&c[32 * i..]).ok_or(SignError::ChallengeNotCanonical)?, s: get_scalar(&s[32 * i..]).ok_or(SignError::ZeroResponse)?,
-                v1specific: if v1 { Some(PlumeSignatureV1Fields { r_point: get_point(&rp[64 * i..]), hashed_to_curve_r: get_point(&hr[64 * i..]) }) } else { None },
-            })
-        }).collect())
+        Ok(signatures(msgs, v1, &pk, &nul, &c, &s, &rp, &hr, &status))
+    }
+
+    /// Same with each nonce derived on the GPU by RFC 6979 from (key, variant, message), hedged with `aux[i]` when given (`plume_sign_batch_rfc6979`):
+    /// no nonce exists in host memory, and the same inputs give the same signatures.
+    pub fn sign_batch_deterministic(&self, keys: &[SecretKey], msgs: &[&[u8]], v1: bool, aux: Option<&[[u8; 32]]>)
+        -> Result<Vec<Result<PlumeSignature, SignError>>, HipError> {
+        let n = keys.len();
+        assert!(msgs.len() == n && aux.map_or(true, |a| a.len() == n));
+        let (mut buf, mut off) = (Vec::new(), vec![0u64]);
+        for m in msgs { buf.extend_from_slice(m); off.push(buf.len() as u64); }
+        buf.push(0);
+        let (mut sk, mut ax) = (vec![0u8; 32 * n], vec![0u8; if aux.is_some() { 32 * n } else { 0 }]);
+        for i in 0..n { sk[32 * i..32 * i + 32].copy_from_slice(&keys[i].to_bytes()); }
+        if let Some(a) = aux { for i in 0..n { ax[32 * i..32 * i + 32].copy_from_slice(&a[i]); } }
+        let (mut pk, mut nul, mut rp, mut hr) = (vec![0u8; 64 * n], vec![0u8; 64 * n], vec![0u8; 64 * n], vec![0u8; 64 * n]);
+        let (mut c, mut s, mut status) = (vec![0u8; 32 * n], vec![0u8; 32 * n], vec![0u8; n]);
+        let rc = unsafe { plume_sign_batch_rfc6979(self.0, if v1 { 1 } else { 2 }, n, buf.as_ptr(), off.as_ptr(), sk.as_ptr(), if aux.is_some() { ax.as_ptr() } else { std::ptr::null() },
+                                                   std::ptr::null(), pk.as_mut_ptr(), nul.as_mut_ptr(), c.as_mut_ptr(), s.as_mut_ptr(), rp.as_mut_ptr(), hr.as_mut_ptr(),
+                                                   status.as_mut_ptr()) };
+        sk.iter_mut().for_each(|b| *b = 0);
+        ax.iter_mut().for_each(|b| *b = 0);
+        if rc != 0 { return Err(last_error()); }
+        Ok(signatures(msgs, v1, &pk, &nul, &c, &s, &rp, &hr, &status))
     }
 
     /// `SecretKey::from(scalar).to_sec1_der()` for a batch — the encoding the wasm wrapper uses for `s` and `digest_private`
@@ -325,6 +340,23 @@ impl HipEngine {
 }
 
 // ------------------------------------------------------------------------------------------------ persistent nullifier set
+/// The signatures of one sign call's outputs; an item on which the reference would panic comes back as `Err(SignError)`.
+fn signatures(msgs: &[&[u8]], v1: bool, pk: &[u8], nul: &[u8], c: &[u8], s: &[u8], rp: &[u8], hr: &[u8], status: &[u8]) -> Vec<Result<PlumeSignature, SignError>> {
+    (0..msgs.len()).map(|i| {
+        let st = status[i];
+        let nullifier = get_point(&nul[64 * i..]);
+        if st & PLUME_STATUS_BAD_SCALAR != 0 { return Err(SignError::BadScalar); }
+        if st & PLUME_STATUS_IDENTITY != 0 && nullifier == AffinePoint::IDENTITY { return Err(SignError::HashedToIdentity); }     // :61
+        if st & PLUME_STATUS_C_NOT_CANONICAL != 0 { return Err(SignError::ChallengeNotCanonical); }                           // :91
+        if st & PLUME_STATUS_IDENTITY != 0 { return Err(SignError::ZeroResponse); }                                             // :95
+        Ok(PlumeSignature {
+            message: msgs[i].to_vec(), pk: get_point(&pk[64 * i..]), nullifier,
+            c: get_scalar(&c[32 * i..]).ok_or(SignError::ChallengeNotCanonical)?, s: get_scalar(&s[32 * i..]).ok_or(SignError::ZeroResponse)?,
+            v1specific: if v1 { Some(PlumeSignatureV1Fields { r_point: get_point(&rp[64 * i..]), hashed_to_curve_r: get_point(&hr[64 * i..]) }) } else { None },
+        })
+    }).collect()
+}
+
 /// A GPU-resident set of nullifiers that persists across batches (`plume_nullset_*`): `insert` tells which signatures carry a nullifier for the first
 /// time EVER, across every earlier insert into the set — the check an application makes before it accepts a verified signature.  Lives on the engine's
 /// (first) GPU and may outlive the engine.  One caller thread at a time.
@@ -421,6 +453,18 @@ impl<'signing> PlumeSigner<'signing> {
     }
     pub fn sign_with_rng(&self, engine: &HipEngine, rng: &mut impl CryptoRngCore, msg: &[u8]) -> PlumeSignature {
         self.try_sign_with_rng(engine, rng, msg).expect("libplume_hip call failed")
+    }
+    /// The nonce derived on the GPU by RFC 6979 from (secret key, variant, message), hedged with `aux` when given (`plume_sign_batch_rfc6979`); no RNG.
+    pub fn sign_deterministic(&self, engine: &HipEngine, msg: &[u8], aux: Option<&[u8; 32]>) -> Result<PlumeSignature, HipError> {
+        let a = aux.map(|a| [*a]);
+        let mut out = engine.sign_batch_deterministic(std::slice::from_ref(self.secret_key), &[msg], self.v1, a.as_ref().map(|a| &a[..]))?;
+        match out.remove(0) {
+            Ok(sig) => Ok(sig),
+            Err(SignError::HashedToIdentity) => panic!("something is drammatically wrong if the input hashed to the identity"),
+            Err(SignError::ChallengeNotCanonical) => panic!("it should be impossible to get the hash equal to zero"),
+            Err(SignError::ZeroResponse) => panic!("something is terribly wrong if the nonce is equal to negated product of the secret and the hash"),
+            Err(SignError::BadScalar) => unreachable!("SecretKey is in [1, n-1] by construction; a derived nonce outside it has probability below 2^-2000"),
+        }
     }
 }
 

@@ -309,6 +309,8 @@ class PlumeSigner {
     PlumeSignature try_sign_with_rng(Rng& rng, const Bytes& msg, Engine& eng = Engine::shared()) const;
     template <class Rng>
     PlumeSignature sign_with_rng(Rng& rng, const Bytes& msg, Engine& eng = Engine::shared()) const { return try_sign_with_rng(rng, msg, eng); }
+    // the nonce derived on the GPU by RFC 6979 from (secret key, variant, message), hedged with aux when given (plume_hip.h, plume_sign_batch_rfc6979)
+    PlumeSignature sign_deterministic(const Bytes& msg, const std::optional<Bytes32>& aux = std::nullopt, Engine& eng = Engine::shared()) const;
 
   private:
     const SecretKey& secret_key_;
@@ -322,6 +324,27 @@ inline void raise_for_status(uint8_t st, const AffinePoint& nullifier) {
     if (st & PLUME_STATUS_IDENTITY) throw Panic("something is terribly wrong if the nonce is equal to negated product of the secret and the hash");
 }
 
+// the signatures of one sign call's outputs; throws Panic at the first item the reference's signer would panic on
+inline std::vector<PlumeSignature> detail_signatures(const std::vector<Bytes>& msgs, bool v1, const Bytes& pk, const Bytes& nul, const Bytes& c, const Bytes& s, const Bytes& rp,
+                                                     const Bytes& hr, const Bytes& st) {
+    const size_t n = msgs.size();
+    std::vector<PlumeSignature> out;
+    out.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+        const AffinePoint nl = AffinePoint::from_bytes64(&nul[64 * i]);
+        raise_for_status(st[i], nl);
+        Bytes32 cb, sb;
+        std::memcpy(cb.data(), &c[32 * i], 32);
+        std::memcpy(sb.data(), &s[32 * i], 32);
+        auto cs = NonZeroScalar::from_repr(cb), ss = NonZeroScalar::from_repr(sb);
+        if (!cs) throw Panic("it should be impossible to get the hash equal to zero");
+        if (!ss) throw Panic("something is terribly wrong if the nonce is equal to negated product of the secret and the hash");
+        PlumeSignature g{msgs[i], AffinePoint::from_bytes64(&pk[64 * i]), nl, *cs, *ss, std::nullopt};
+        if (v1) g.v1specific = PlumeSignatureV1Fields{AffinePoint::from_bytes64(&rp[64 * i]), AffinePoint::from_bytes64(&hr[64 * i])};
+        out.push_back(std::move(g));
+    }
+    return out;
+}
 // batch twin of the signer with the nonces supplied (the RNG stays on the host): one signature per (key, message, nonce).  Throws Panic at the first
 // item the reference's signer would panic on.
 inline std::vector<PlumeSignature> sign_batch_with_nonces(const std::vector<SecretKey>& keys, const std::vector<Bytes>& msgs, bool v1, const std::vector<SecretKey>& nonces,
@@ -341,21 +364,31 @@ inline std::vector<PlumeSignature> sign_batch_with_nonces(const std::vector<Secr
     { volatile uint8_t* w = sk.data(); for (size_t i = 0; i < sk.size(); i++) w[i] = 0; }
     { volatile uint8_t* w = r.data(); for (size_t i = 0; i < r.size(); i++) w[i] = 0; }
     plume_hip::check(rc, "plume_sign_batch");
-    out.reserve(n);
+    return detail_signatures(msgs, v1, pk, nul, c, s, rp, hr, st);
+}
+// ... and with each nonce derived on the GPU by RFC 6979 (plume_hip.h, plume_sign_batch_rfc6979): no nonce exists in host memory.  aux: empty, or one 32-byte
+// hedging input per signature (RFC 6979 section 3.6).
+inline std::vector<PlumeSignature> sign_batch_deterministic(const std::vector<SecretKey>& keys, const std::vector<Bytes>& msgs, bool v1, const std::vector<Bytes32>& aux = {},
+                                                            Engine& eng = Engine::shared()) {
+    const size_t n = keys.size();
+    if (msgs.size() != n || (!aux.empty() && aux.size() != n)) throw std::invalid_argument("keys, msgs and aux (when given) must have one entry per signature");
+    plume_hip::PackedMessages m;
+    Bytes sk(32 * n), ax(32 * aux.size()), pk(64 * n), nul(64 * n), c(32 * n), s(32 * n), rp(64 * n), hr(64 * n), st(n);
     for (size_t i = 0; i < n; i++) {
-        const AffinePoint nl = AffinePoint::from_bytes64(&nul[64 * i]);
-        raise_for_status(st[i], nl);
-        Bytes32 cb, sb;
-        std::memcpy(cb.data(), &c[32 * i], 32);
-        std::memcpy(sb.data(), &s[32 * i], 32);
-        auto cs = NonZeroScalar::from_repr(cb), ss = NonZeroScalar::from_repr(sb);
-        if (!cs) throw Panic("it should be impossible to get the hash equal to zero");
-        if (!ss) throw Panic("something is terribly wrong if the nonce is equal to negated product of the secret and the hash");
-        PlumeSignature g{msgs[i], AffinePoint::from_bytes64(&pk[64 * i]), nl, *cs, *ss, std::nullopt};
-        if (v1) g.v1specific = PlumeSignatureV1Fields{AffinePoint::from_bytes64(&rp[64 * i]), AffinePoint::from_bytes64(&hr[64 * i])};
-        out.push_back(std::move(g));
+        m.push(msgs[i].data(), msgs[i].size());
+        std::memcpy(&sk[32 * i], keys[i].to_bytes().data(), 32);
+        if (!aux.empty()) std::memcpy(&ax[32 * i], aux[i].data(), 32);
     }
-    return out;
+    if (n == 0) return {};
+    const int rc = plume_sign_batch_rfc6979(eng.ctx(), v1 ? 1 : 2, n, m.data(), m.off.data(), sk.data(), aux.empty() ? nullptr : ax.data(), nullptr, pk.data(), nul.data(),
+                                            c.data(), s.data(), rp.data(), hr.data(), st.data());
+    { volatile uint8_t* w = sk.data(); for (size_t i = 0; i < sk.size(); i++) w[i] = 0; }
+    { volatile uint8_t* w = ax.data(); for (size_t i = 0; i < ax.size(); i++) w[i] = 0; }
+    plume_hip::check(rc, "plume_sign_batch_rfc6979");
+    return detail_signatures(msgs, v1, pk, nul, c, s, rp, hr, st);
+}
+inline PlumeSignature PlumeSigner::sign_deterministic(const Bytes& msg, const std::optional<Bytes32>& aux, Engine& eng) const {
+    return std::move(sign_batch_deterministic({secret_key_}, {msg}, v1, aux ? std::vector<Bytes32>{*aux} : std::vector<Bytes32>{}, eng)[0]);
 }
 // ... and with the nonces drawn as the reference draws them: SecretKey::random(rng) per signature, in order (randomizedsigner.rs:49)
 template <class Rng>

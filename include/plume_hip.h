@@ -71,7 +71,7 @@ int plume_shard_numa_node(const plume_ctx* ctx, int shard);
 void plume_destroy(plume_ctx* ctx);
 /* Last error text of this thread (valid until the next failing call on the thread). */
 const char* plume_last_error(void);
-/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.7: the persistent nullifier set (plume_nullset_*); 0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
+/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.8: derived signing nonces (plume_sign_batch_rfc6979*); 0.7: the persistent nullifier set (plume_nullset_*); 0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
  * the signer defaults to uniform level 1; the generator tables are built by the first call that needs them; stream = NULL means the stream of the context the caller
  * holds; plume_destroy waits for the context's own work only (its last call on any stream and its private streams), not for the whole device. */
 const char* plume_version(void);
@@ -380,6 +380,32 @@ int plume_aggregate_check_device(plume_ctx* ctx, int version, int mode, size_t n
                                  const uint8_t* pk, const uint8_t* nullifier, const uint8_t* c, const uint8_t* s,
                                  const uint8_t* r_point, const uint8_t* hashed_to_curve_r,
                                  const uint8_t seed[32], uint64_t index_base, uint8_t* hash_ok, uint8_t* result, void* stream);
+
+/* ---- derived signing nonces: RFC 6979, optionally hedged  (library 0.8) ------------------------------------
+ * plume_sign_batch with r computed on the GPU instead of supplied: PLUME's s = r + sk*c leaks sk when r repeats under two different c, or is biased.  For item i,
+ * with version in {1, 2} and mode = 0 when pk_in is NULL, 1 otherwise:
+ *     h1  = SHA-256( "PLUME-RFC6979" (13 ASCII bytes) || u8 version || u8 mode || pk_in[i] (64 B, mode 1 only) || msg_i )
+ *     x   = sk[i], the 32 bytes as given
+ *     r_i = RFC 6979 section 3.2 steps a-h with HMAC-SHA-256, q = n (the secp256k1 group order), qlen = hlen = 256, bits2octets(h1) = int2octets(int(h1) mod n);
+ *           aux != NULL: k' = aux[i] (32 B) is appended after bits2octets(h1) in steps d and f (section 3.6, "hedged" signing); nothing is appended otherwise.
+ * Every output (pk, nullifier, c, s, r_point, hashed_to_curve_r, status) is then byte-identical to plume_sign_batch given r[i] = r_i, at every
+ * plume_set_sign_uniform level.  Version, mode and pk_in are in h1 because everything that feeds c feeds r: the same (sk, msg) signed as V1 and V2, or under two
+ * supplied pk_in, gets two nonces.  Identical inputs give identical signatures.
+ * Step h's retry (a candidate outside [1, n-1], probability ~2^-128) runs at most 16 candidates per item; an item that exhausts them (probability below 2^-2000)
+ * gets r_i = 0 and so PLUME_STATUS_BAD_SCALAR.  sk outside [1, n-1], pk_in off the curve and rejected message offsets behave as in plume_sign_batch*; a rejected
+ * offset hashes the empty message and msgs is not read for it.
+ * The nonce exists only in the context's device workspace between the kernels that use it -- never in host memory -- and is wiped on the call's stream after the
+ * last of them.  There is no API that returns it.  Argument checks, error codes, routing, sharding over plume_init_multi and threading are those of
+ * plume_sign_batch / plume_sign_batch_device; aux may be NULL where those require r.  The host form stages aux like sk and wipes the staged copies. */
+int plume_sign_batch_rfc6979(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off,
+                             const uint8_t* sk, const uint8_t* aux, const uint8_t* pk_in,
+                             uint8_t* pk, uint8_t* nullifier, uint8_t* c, uint8_t* s,
+                             uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* status);
+int plume_sign_batch_rfc6979_device(plume_ctx* ctx, int version, size_t n,
+                                    const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes,
+                                    const uint8_t* sk, const uint8_t* aux, const uint8_t* pk_in,
+                                    uint8_t* pk, uint8_t* nullifier, uint8_t* c, uint8_t* s,
+                                    uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* status, void* stream);
 
 /* ---- persistent nullifier set: reject repeats across batches  (library 0.7) ----------------------------------
  * A consumer that verifies a STREAM of batches (a vote tally, a claim relayer, a rate limiter) must reject a nullifier it accepted any number of

@@ -127,10 +127,15 @@ def _load():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, res
+    # derived signing nonces (library 0.8; Engine.sign_batch_rfc6979* raise PlumeHipError on an older build)
+    for name, args in (("plume_sign_batch_rfc6979", [vp, i, sz] + [vp] * 12), ("plume_sign_batch_rfc6979_device", [vp, i, sz, vp, vp, sz] + [vp] * 11)):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
     _lib = lib
-    if _version(lib) < (0, 7) and not os.environ.get("PLUME_HIP_LIB"):
+    if _version(lib) < (0, 8) and not os.environ.get("PLUME_HIP_LIB"):
         _lib = None
-        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.7 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.8 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
     return lib
 
 
@@ -143,7 +148,7 @@ def exported_symbols():
             "plume_hash_to_curve_batch", "plume_nullifier_first_occurrence", "plume_nullifier_first_occurrence_device", "plume_verify_batch_device", "plume_sign_batch_device", "plume_hash_to_curve_batch_device",
             "plume_last_stage_times", "plume_microbench", "plume_microbench_last_ticks",
             "plume_nullset_create", "plume_nullset_destroy", "plume_nullset_reserve", "plume_nullset_clear", "plume_nullset_size", "plume_nullset_insert", "plume_nullset_contains",
-            "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device"]
+            "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device", "plume_sign_batch_rfc6979", "plume_sign_batch_rfc6979_device"]
 
 
 def pack_messages(msgs):
@@ -433,6 +438,30 @@ class Engine:
         o["status"] = status
         return o
 
+    def _derived(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None or _version(self._lib) < (0, 8):
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no derived-nonce signer: {name} needs plume_hip >= 0.8 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    def sign_batch_rfc6979(self, version, msgs, msg_off, sk, aux=None, pk_in=None, out=None):
+        """sign_batch with each nonce derived on the GPU by RFC 6979 (include/plume_hip.h, plume_sign_batch_rfc6979): h1 = SHA-256("PLUME-RFC6979" || version || mode ||
+        pk_in || msg), x = sk; aux (n x 32 bytes, optional) is the hedging input of RFC 6979 section 3.6.  The nonces never reach host memory.  Same outputs as sign_batch."""
+        fn = self._derived("plume_sign_batch_rfc6979")
+        n = len(msg_off) - 1
+        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
+        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        sk = _np(sk, 32, n, "sk")
+        aux = None if aux is None else _np(aux, 32, n, "aux")
+        pk_in = None if pk_in is None else _np(pk_in, 64, n, "pk_in")
+        o = out if out is not None else {k: np.zeros((n, w), dtype=np.uint8) for k, w in
+                                         [("pk", 64), ("nullifier", 64), ("c", 32), ("s", 32), ("r_point", 64), ("hashed_to_curve_r", 64)]}
+        status = o["status"] if out is not None else np.zeros(n, dtype=np.uint8)
+        self._chk(fn(self._ctx, int(version), n, _ptr(msgs), _ptr(msg_off), _ptr(sk), _ptr(aux), _ptr(pk_in), _ptr(o["pk"]), _ptr(o["nullifier"]), _ptr(o["c"]), _ptr(o["s"]),
+                     _ptr(o["r_point"]), _ptr(o["hashed_to_curve_r"]), _ptr(status)), "plume_sign_batch_rfc6979")
+        o["status"] = status
+        return o
+
     def sign_batch_sec1(self, version, msgs, msg_off, sk, r, pk_in=None):
         """sign_batch with pk, nullifier, r_point, hashed_to_curve_r as 33-byte SEC1-compressed records"""
         n = len(msg_off) - 1
@@ -555,6 +584,15 @@ class Engine:
         self._chk(self._lib.plume_sign_batch_device(self._ctx, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(sk), d(r), d(pk_in), d(pk),
                                                     d(nullifier), d(c), d(s), d(r_point), d(hashed_to_curve_r), d(status), C.c_void_p(st)),
                   "plume_sign_batch_device")
+
+    def sign_batch_rfc6979_device(self, version, n, msgs, msg_off, msgs_bytes, sk, aux, pk_in, pk, nullifier, c, s, r_point, hashed_to_curve_r, status, stream=None):
+        """the device form of sign_batch_rfc6979 on torch tensors (aux, pk_in: None or tensors); enqueues on `stream` (None = current stream); does not synchronise"""
+        import torch
+        fn = self._derived("plume_sign_batch_rfc6979_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(sk), d(aux), d(pk_in), d(pk), d(nullifier), d(c), d(s), d(r_point),
+                     d(hashed_to_curve_r), d(status), C.c_void_p(st)), "plume_sign_batch_rfc6979_device")
 
     def nullifier_first_occurrence_device(self, n, nullifier, live, ids, first, n_unique=None, stream=None):
         """tensors on cuda:<device_id> (nullifier n x 64 uint8, live / first uint8[n] or None, ids int64/uint64[n] or None, n_unique one 64-bit word or None)"""

@@ -27,6 +27,7 @@
 #include "plume_capi_internal.h"
 #include "plume_host_logic.h"
 #include "plume_launch.h"
+#include "plume_nonce.h"
 
 using namespace plume;
 
@@ -170,6 +171,7 @@ struct plume_ctx {
     size_t in_flight_min = 0;                                      // verify / sign calls of fewer items are not dealt out to the lanes (env PLUME_IN_FLIGHT_MIN; 0, the default: every call is)
     plume_ctx* lane_last = nullptr;                               // the lane the last device-resident call went to (plume_last_stage_times, plume_last_redo_tasks)
     DevBuf bases, jobflags, itemflags, tab, tabscr, res, resinf, res2, res2inf, pkaff, sink, redo, digs, eq1fall, eq1k, clk;
+    DevBuf nonce;                                                  // the derived-nonce signer: r of the call in flight, 32 B / item, wiped on the call's stream after sign_final
     int eq1_short = 1;                                             // verify calls that give R: equation 1 in its short form (plume_eis.h).  0 = long form always (A/B), 2 = test: every item takes the fallback
     size_t eq1_short_min = (size_t)1 << 16;                        // ... for calls of at least this many items.  Round 6 sweep on one box, interleaved (profiles/r06_eq1_threshold.txt), now that the
                                                                    // scalar stage -- half-GCD included -- of calls up to 2^16 runs in role B of the two-role ingest kernel: 2^16 items 1.385 -> 1.343 ms
@@ -275,7 +277,7 @@ extern "C" const char* plume_last_error(void) { return g_err.c_str(); }
 #ifndef PLUME_BUILD_ID
 #define PLUME_BUILD_ID "unknown"
 #endif
-extern "C" const char* plume_version(void) { return "plume_hip 0.7 gfx950 build=" PLUME_BUILD_ID; }
+extern "C" const char* plume_version(void) { return "plume_hip 0.8 gfx950 build=" PLUME_BUILD_ID; }
 
 static void destroy_single(plume_ctx* ctx) {
     for (plume_ctx* l : ctx->lanes) destroy_single(l);
@@ -288,7 +290,7 @@ static void destroy_single(plume_ctx* ctx) {
     if (ctx->ws_used && ctx->ws_free) (void)hipEventSynchronize(ctx->ws_free);
     for (hipStream_t q : {ctx->stream, ctx->up, ctx->down, ctx->side, ctx->pre}) if (q) (void)hipStreamSynchronize(q);
     for (DevBuf* b : {&ctx->bases, &ctx->jobflags, &ctx->itemflags, &ctx->tab, &ctx->tabscr, &ctx->res, &ctx->resinf, &ctx->res2, &ctx->res2inf, &ctx->pkaff,
-                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
+                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
         b->release();
     for (DevBuf& b : ctx->agg) b.release();
     if (ctx->fixed) {
@@ -824,7 +826,8 @@ static int verify_device(plume_ctx* ctx, int version, int mode, size_t n, const 
 
 static int sign_device(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, const uint8_t* sk, const uint8_t* r,
                        const uint8_t* pk_in, uint8_t* pk, uint8_t* nul, uint8_t* c, uint8_t* s, uint8_t* rpt, uint8_t* hr, uint8_t* status, uint8_t* h_out,
-                       hipStream_t st, bool out33 = false) {
+                       hipStream_t st, bool out33 = false, const uint8_t* aux = nullptr, SignNonceLaunch nonce_fn = nullptr) {
+    // nonce_fn (the derived-nonce signer, plume_nonce_capi.hip): r is not given; the hook writes it into ctx->nonce in front of each sub-batch's first stage
     if (n == 0) return 0;
     if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
     if (int rc = need_sign_tables(ctx)) return rc;
@@ -838,7 +841,8 @@ static int sign_device(plume_ctx* ctx, int version, size_t n, const uint8_t* msg
     for (size_t k = 0; k < nsub; k++) scr_bytes = std::max(scr_bytes, table_stage_scratch(ctx, SK * (cut[k + 1] - cut[k]), 0));
     if (ctx->bases.ensure((size_t)PLUME_BASE_WORDS * 4 * SK * n) || ctx->jobflags.ensure(SK * n) || ctx->itemflags.ensure(n) || ctx->tab.ensure((size_t)PLUME_TAB_WORDS * 4 * SK * n) ||
         ctx->tabscr.ensure(scr_bytes) ||
-        ctx->res.ensure((size_t)PLUME_JAC_WORDS * 4 * 2 * n) || ctx->resinf.ensure(2 * n) || ctx->res2.ensure((size_t)PLUME_JAC_WORDS * 4 * 2 * n) || ctx->res2inf.ensure(2 * n) || ctx->pkaff.ensure((size_t)2 * PLUME_FE_WORDS * 4 * n))
+        ctx->res.ensure((size_t)PLUME_JAC_WORDS * 4 * 2 * n) || ctx->resinf.ensure(2 * n) || ctx->res2.ensure((size_t)PLUME_JAC_WORDS * 4 * 2 * n) || ctx->res2inf.ensure(2 * n) || ctx->pkaff.ensure((size_t)2 * PLUME_FE_WORDS * 4 * n) ||
+        (nonce_fn && ctx->nonce.ensure(32 * n)))
         return PLUME_ERR_HIP;
     if (overlapped) { if (int rc = pre_events(ctx, nsub)) return rc; if (int rc = pre_stream(ctx)) return rc; }
     StageTimer& t = ctx->timer;
@@ -852,13 +856,20 @@ static int sign_device(plume_ctx* ctx, int version, size_t n, const uint8_t* msg
     for (size_t k = 0; k < nsub; k++) {
         const size_t lo = cut[k], cnt = cut[k + 1] - cut[k];
         SignArgs a;
-        a.version = version; a.n = (uint32_t)cnt; a.msgs = msgs; a.msg_off = msg_off + lo; a.msgs_bytes = msgs_bytes; a.sk = sk + 32 * lo; a.r = r + 32 * lo; a.pk_in = pk_in ? pk_in + 64 * lo : nullptr;
+        a.version = version; a.n = (uint32_t)cnt; a.msgs = msgs; a.msg_off = msg_off + lo; a.msgs_bytes = msgs_bytes; a.sk = sk + 32 * lo; a.pk_in = pk_in ? pk_in + 64 * lo : nullptr;
+        a.r = nonce_fn ? ctx->nonce.as<uint8_t>() + 32 * lo : r + 32 * lo;
         a.pk = pk ? pk + P * lo : nullptr; a.nul = nul + P * lo; a.c = c + 32 * lo; a.s = s + 32 * lo; a.rpt = rpt + P * lo; a.hr = hr + P * lo; a.status = status + lo;
         a.h_out = h_out ? h_out + 64 * lo : nullptr; a.out33 = out33 ? 1 : 0;
         a.gres = ctx->res.as<uint32_t>() + (size_t)PLUME_JAC_WORDS * 2 * lo; a.gresinf = ctx->resinf.as<uint8_t>() + 2 * lo; a.bases = ctx->bases.as<uint32_t>() + (size_t)PLUME_BASE_WORDS * SK * lo;
         a.jobflags = ctx->jobflags.as<uint8_t>() + SK * lo; a.itemflags = ctx->itemflags.as<uint8_t>() + lo; a.pkaff = ctx->pkaff.as<uint32_t>() + (size_t)2 * PLUME_FE_WORDS * lo;
         a.tab = ctx->tab.as<uint32_t>() + (size_t)PLUME_TAB_WORDS * SK * lo; a.hres = ctx->res2.as<uint32_t>() + (size_t)PLUME_JAC_WORDS * 2 * lo; a.hresinf = ctx->res2inf.as<uint8_t>() + 2 * lo;
         a.gcomb = ctx->fixed->gcomb.as<uint32_t>(); a.gscan = ctx->fixed->gscan.as<uint32_t>(); a.uniform = ctx->sign_uniform;
+        if (nonce_fn) {
+            NonceArgs na;
+            na.version = version; na.n = (uint32_t)cnt; na.msgs = msgs; na.msg_off = a.msg_off; na.msgs_bytes = msgs_bytes; na.sk = a.sk; na.aux = aux ? aux + 32 * lo : nullptr;
+            na.pk_in = a.pk_in; na.r = ctx->nonce.as<uint8_t>() + 32 * lo;
+            nonce_fn(na, pre); if (!overlapped) t.stage("sign_nonce", st);
+        }
         launch_sign_gmul(a, pre); if (!overlapped) t.stage("sign_gmul", st);
         launch_normalize(a.gres, a.gresinf, 2 * cnt, pre); if (!overlapped) t.stage("to_affine_g", st);
         launch_sign_h2c(a, pre); if (!overlapped) t.stage("sign_h2c", st);
@@ -875,6 +886,7 @@ static int sign_device(plume_ctx* ctx, int version, size_t n, const uint8_t* msg
     if (overlapped) t.stage("sign_overlapped", st);
     // the reference zeroizes secrets: wipe the device-side images derived from sk / r
     HIPCHK(hipMemsetAsync(ctx->res.p, 0, (size_t)PLUME_JAC_WORDS * 4 * 2 * n, st));
+    if (nonce_fn) HIPCHK(hipMemsetAsync(ctx->nonce.p, 0, 32 * n, st));      // ... and the derived nonces themselves, which never leave the device
     HIPCHK(hipGetLastError());
     return hold.release();
 }
@@ -893,10 +905,11 @@ static int verify_args_ok(int version, int mode, size_t n, const void* msgs, con
     if (n && version == 1 && (!rpt || !hr)) return fail(PLUME_ERR_ARG, "V1 needs r_point and hashed_to_curve_r");
     return 0;
 }
+// derived: the derived-nonce signer, whose r (there: aux) may be NULL
 static int sign_args_ok(int version, size_t n, const void* msgs, const void* off, const void* sk, const void* r, const void* nul, const void* c, const void* s, const void* rpt,
-                        const void* hr, const void* status) {
+                        const void* hr, const void* status, bool derived = false) {
     if (int rc = args_ok(version, n, msgs, off)) return rc;
-    if (n && (!sk || !r || !nul || !c || !s || !rpt || !hr || !status)) return fail(PLUME_ERR_ARG, "null array");
+    if (n && (!sk || (!r && !derived) || !nul || !c || !s || !rpt || !hr || !status)) return fail(PLUME_ERR_ARG, "null array");
     return 0;
 }
 static int h2c_args_ok(size_t n, const void* msgs, const void* off, const void* h_out) {
@@ -1445,7 +1458,7 @@ static int host_call(plume_ctx* ctx, size_t n, const HostCall& call, Run run) {
     for (const HostArray& a : call.in) two_lanes = two_lanes && (!a.p || is_page_locked(a.p));
     for (const HostArray& a : call.out) two_lanes = two_lanes && (!a.p || is_page_locked(a.p));
     two_lanes = two_lanes && (mbytes == 0 || is_page_locked(m0));
-    return host_pipeline(
+    const int rc = host_pipeline(
         ctx, n, call.out_heavy,
         [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
             if (int rc = stage_msgs(ctx, sl, call.msgs, call.msg_off, i0, cnt)) return rc;
@@ -1459,7 +1472,7 @@ static int host_call(plume_ctx* ctx, size_t n, const HostCall& call, Run run) {
         [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
             if (int rc = run(sl, cnt, on)) return rc;
             // wipe the staged secrets before the slot is reused or freed
-            for (size_t k = 0; k < std::size(call.in); k++) if (call.in[k].secret) HIPCHK(hipMemsetAsync(sl.in[k].p, 0, call.in[k].stride * cnt, on->stream));
+            for (size_t k = 0; k < std::size(call.in); k++) if (call.in[k].secret && call.in[k].p) HIPCHK(hipMemsetAsync(sl.in[k].p, 0, call.in[k].stride * cnt, on->stream));
             return 0;
         },
         [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
@@ -1470,6 +1483,13 @@ static int host_call(plume_ctx* ctx, size_t n, const HostCall& call, Run run) {
             return 0;
         },
         two_lanes);
+    // a call that failed part-way (an allocation, a copy) may have staged secrets that no kernel read and so no wipe followed: wipe every slot's copies now
+    if (rc) {
+        for (HostSlot& sl : ctx->slot)
+            for (size_t k = 0; k < std::size(call.in); k++) if (call.in[k].secret && sl.in[k].p) (void)hipMemsetAsync(sl.in[k].p, 0, sl.in[k].cap, ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    return rc;
 }
 
 // a context of either kind, arguments already checked: a multi-device context runs every shard's items on that shard
@@ -1568,18 +1588,21 @@ extern "C" int plume_aggregate_check(plume_ctx* ctx, int version, int mode, size
 }
 
 // sign and sign_sec1 (P = 33: SEC1 output points)
+// nonce_fn: the derived-nonce signer -- r is not given and `r` carries its hedging input aux (or NULL), staged and wiped like sk
 static int sign_host(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* sk, const uint8_t* r,
                      const uint8_t* pk_in, uint8_t* pk, uint8_t* nullifier, uint8_t* c, uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r,
-                     uint8_t* status, const size_t P /* bytes per output point record: 64, or 33 for SEC1 */) {
+                     uint8_t* status, const size_t P /* bytes per output point record: 64, or 33 for SEC1 */, SignNonceLaunch nonce_fn = nullptr) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = sign_args_ok(version, n, msgs, msg_off, sk, r, nullifier, c, s, r_point, hashed_to_curve_r, status)) return rc;
+    if (int rc = sign_args_ok(version, n, msgs, msg_off, sk, r, nullifier, c, s, r_point, hashed_to_curve_r, status, nonce_fn != nullptr)) return rc;
     // two lanes (round 5) under the same condition as the verifier (host_call)
     const HostCall call{msgs, msg_off, {{sk, 32, true}, {r, 32, true}, {pk_in, 64}}, {{pk, P}, {nullifier, P}, {c, 32}, {s, 32}, {r_point, P}, {hashed_to_curve_r, P}, {status, 1}},
                         true, ctx->host_sign_lanes > 1};
     return host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return sign_device(on, version, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
+        const uint8_t* r1 = r ? sl.in[1].as<uint8_t>() : nullptr;
+        return sign_device(on, version, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), nonce_fn ? nullptr : r1,
                            pk_in ? sl.in[2].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(),
-                           sl.out[3].as<uint8_t>(), sl.out[4].as<uint8_t>(), sl.out[5].as<uint8_t>(), sl.out[6].as<uint8_t>(), nullptr, on->stream, P == 33);
+                           sl.out[3].as<uint8_t>(), sl.out[4].as<uint8_t>(), sl.out[5].as<uint8_t>(), sl.out[6].as<uint8_t>(), nullptr, on->stream, P == 33,
+                           nonce_fn ? r1 : nullptr, nonce_fn);
     });
 }
 
@@ -1592,6 +1615,20 @@ extern "C" int plume_sign_batch_sec1(plume_ctx* ctx, int version, size_t n, cons
                                      const uint8_t* pk_in, uint8_t* pk33, uint8_t* nullifier33, uint8_t* c, uint8_t* s, uint8_t* r_point33,
                                      uint8_t* hashed_to_curve_r33, uint8_t* status) {
     return sign_host(ctx, version, n, msgs, msg_off, sk, r, pk_in, pk33, nullifier33, c, s, r_point33, hashed_to_curve_r33, status, 33);
+}
+// the derived-nonce signer (plume_capi_internal.h): the ABI and the launcher live in plume_nonce_capi.hip
+int plume::capi_sign_derived(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* sk, const uint8_t* aux, const uint8_t* pk_in,
+                             uint8_t* pk, uint8_t* nullifier, uint8_t* c, uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* status, SignNonceLaunch nonce_fn) {
+    return sign_host(ctx, version, n, msgs, msg_off, sk, aux, pk_in, pk, nullifier, c, s, r_point, hashed_to_curve_r, status, 64, nonce_fn);
+}
+int plume::capi_sign_derived_device(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, const uint8_t* sk,
+                                    const uint8_t* aux, const uint8_t* pk_in, uint8_t* pk, uint8_t* nullifier, uint8_t* c, uint8_t* s, uint8_t* r_point,
+                                    uint8_t* hashed_to_curve_r, uint8_t* status, void* stream, SignNonceLaunch nonce_fn) {
+    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = sign_args_ok(version, n, msgs, msg_off, sk, aux, nullifier, c, s, r_point, hashed_to_curve_r, status, true)) return rc;
+    return sign_device(ctx, version, n, msgs, msg_off, msgs_bytes, sk, nullptr, pk_in, pk, nullifier, c, s, r_point, hashed_to_curve_r, status, nullptr, st_, false, aux,
+                       nonce_fn);
 }
 
 extern "C" int plume_hash_to_curve_batch(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, uint8_t* h_out) {

@@ -1,6 +1,8 @@
-// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
+// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
 
 struct plume_ctx;
 
@@ -12,5 +14,18 @@ __attribute__((visibility("hidden"))) int capi_fail(int code, const char* msg);
 __attribute__((visibility("hidden"))) int capi_ctx_device(const plume_ctx* ctx, int* device);
 // len bytes of the OS generator (getrandom); false if it failed
 __attribute__((visibility("hidden"))) bool capi_os_random(void* out, size_t len);
+
+// The derived-nonce signer (plume_sign_batch_rfc6979*): the sign pipeline with r computed on the device.  The launcher of the nonce kernel comes in as a hook, so
+// that plume_capi.hip never names it; it is called once per sub-batch, on the stream of the stages in front of the multiplications by G, and writes the
+// workspace buffer that SignArgs::r then points at.  Arguments, routing, sharding and error codes are those of plume_sign_batch / plume_sign_batch_device.
+struct NonceArgs;
+typedef void (*SignNonceLaunch)(const NonceArgs& a, hipStream_t st);
+__attribute__((visibility("hidden"))) int capi_sign_derived(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* sk,
+                                                            const uint8_t* aux, const uint8_t* pk_in, uint8_t* pk, uint8_t* nullifier, uint8_t* c, uint8_t* s,
+                                                            uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* status, SignNonceLaunch nonce_fn);
+__attribute__((visibility("hidden"))) int capi_sign_derived_device(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes,
+                                                                   const uint8_t* sk, const uint8_t* aux, const uint8_t* pk_in, uint8_t* pk, uint8_t* nullifier, uint8_t* c,
+                                                                   uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* status, void* stream,
+                                                                   SignNonceLaunch nonce_fn);
 
 }  // namespace plume

@@ -157,6 +157,9 @@ class PlumeSigner:  # rust-k256/src/randomizedsigner.rs:25-41
         msgs, off = pack_messages([bytes(msg)])
         a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
         o = eng.sign_batch(1 if self.v1 else 2, msgs, off, a(self.secret_key.to_bytes()), a(r.to_bytes()))
+        return self._signature(o, msg)
+
+    def _signature(self, o, msg: bytes) -> PlumeSignature:
         st = int(o["status"][0])
         if st & 4 and AffinePoint.from_bytes64(o["nullifier"][0]).is_identity:
             raise PlumePanic("something is drammatically wrong if the input hashed to the identity")               # :61
@@ -172,6 +175,17 @@ class PlumeSigner:  # rust-k256/src/randomizedsigner.rs:25-41
 
     def sign_with_rng(self, rng, msg: bytes) -> PlumeSignature:
         return self.try_sign_with_rng(rng, msg)
+
+    def sign_deterministic(self, msg: bytes, aux: Optional[bytes] = None) -> PlumeSignature:
+        """sign with the nonce derived on the GPU by RFC 6979 from (secret key, version, message), hedged with the 32 bytes of aux when given
+        (include/plume_hip.h, plume_sign_batch_rfc6979).  The same inputs give the same signature; no RNG is needed."""
+        eng = self._engine or default_engine()
+        if aux is not None and len(bytes(aux)) != 32:
+            raise ValueError("aux must be 32 bytes")
+        msgs, off = pack_messages([bytes(msg)])
+        a = lambda b: np.frombuffer(bytes(b), dtype=np.uint8)  # noqa: E731
+        o = eng.sign_batch_rfc6979(1 if self.v1 else 2, msgs, off, a(self.secret_key.to_bytes()), None if aux is None else a(aux))
+        return self._signature(o, msg)
 
 
 # ------------------------------------------------------------------------------------------- plume_arkworks shape
