@@ -45,6 +45,9 @@ pub enum SignError {
     ZeroResponse,
     /// a scalar outside [1, n-1] reached the library (cannot happen through `SecretKey` / `NonZeroScalar`)
     BadScalar,
+    /// the signer's self-check (`Engine::set_sign_selfcheck(1)`) withheld the item: the signer called it good but its records do not verify.  Not one of the
+    /// reference's panics: the reference releases such a signature
+    SelfCheckFailed,
 }
 
 #[derive(Debug)]
@@ -53,6 +56,13 @@ impl std::fmt::Display for HipError {
     fn fmt(&self, f: &mut std::fmt::Formatter<'_>) -> std::fmt::Result { write!(f, "plume_hip: {}", self.0) }
 }
 impl std::error::Error for HipError {}
+impl HipError {
+    /// What `PlumeSigner::try_sign_with_rng` / `sign_deterministic` return when the signer's self-check (`HipEngine::set_sign_selfcheck(1)`) withheld the signature:
+    /// not a failed library call and not one of the reference's panics -- the signature was computed, did not verify and was not released.
+    pub const SELF_CHECK_FAILED: &'static str = "the signature does not verify and was withheld by the signer's self-check";
+    pub fn self_check_failed() -> Self { HipError(Self::SELF_CHECK_FAILED.to_string()) }
+    pub fn is_self_check_failed(&self) -> bool { self.0 == Self::SELF_CHECK_FAILED }
+}
 
 // ------------------------------------------------------------------------------------------------------ FFI (include/plume_hip.h)
 #[repr(C)]
@@ -61,6 +71,7 @@ pub struct plume_ctx { _private: [u8; 0] }
 pub const PLUME_STATUS_C_NOT_CANONICAL: u8 = 1;
 pub const PLUME_STATUS_BAD_SCALAR: u8 = 2;
 pub const PLUME_STATUS_IDENTITY: u8 = 4;
+pub const PLUME_STATUS_SELFCHECK_FAILED: u8 = 8;
 
 #[link(name = "plume_hip")]
 extern "C" {
@@ -84,6 +95,8 @@ extern "C" {
     fn plume_set_in_flight(ctx: *mut plume_ctx, batches: c_int) -> c_int;
     fn plume_set_sign_uniform(ctx: *mut plume_ctx, level: c_int) -> c_int;
     fn plume_get_sign_uniform(ctx: *const plume_ctx) -> c_int;
+    fn plume_set_sign_selfcheck(ctx: *mut plume_ctx, mode: c_int) -> c_int;
+    fn plume_get_sign_selfcheck(ctx: *const plume_ctx) -> c_int;
     fn plume_set_host_lanes(ctx: *mut plume_ctx, lanes: c_int) -> c_int;
     fn plume_set_stage_timing(ctx: *mut plume_ctx, on: c_int) -> c_int;
     fn plume_set_eq1_short(ctx: *mut plume_ctx, mode: c_int) -> c_int;
@@ -320,6 +333,11 @@ impl HipEngine {
     pub fn eq1_short(&self) -> Result<(i32, usize), HipError> { let mut m: usize = 0; let r = unsafe { plume_get_eq1_short(self.0, &mut m) }; if r >= 0 { Ok((r as i32, m)) } else { Err(last_error()) } }
     /// Measurement hook (`plume_last_msm_kernel`): the multi-scalar kernel the last verify call on this context launched.
     pub fn last_msm_kernel(&self) -> Option<String> { let p = unsafe { plume_last_msm_kernel(self.0) }; if p.is_null() { None } else { Some(unsafe { std::ffi::CStr::from_ptr(p) }.to_string_lossy().into_owned()) } }
+    /// The signer's self-check (`plume_set_sign_selfcheck`): mode 1 = every sign call verifies its own records on the GPU before anything reaches the caller's arrays;
+    /// an item that does not verify comes back as `Err(SignError::SelfCheckFailed)`.  0 (the default) = off.
+    pub fn set_sign_selfcheck(&self, mode: i32) -> Result<(), HipError> { if unsafe { plume_set_sign_selfcheck(self.0, mode as c_int) } == 0 { Ok(()) } else { Err(last_error()) } }
+    /// The mode this context signs with (`plume_get_sign_selfcheck`).
+    pub fn sign_selfcheck(&self) -> Result<i32, HipError> { let m = unsafe { plume_get_sign_selfcheck(self.0) }; if m >= 0 { Ok(m as i32) } else { Err(last_error()) } }
     /// The level this context signs at (`plume_get_sign_uniform`).
     pub fn sign_uniform(&self) -> Result<i32, HipError> { let l = unsafe { plume_get_sign_uniform(self.0) }; if l >= 0 { Ok(l as i32) } else { Err(last_error()) } }
     /// per-stage timing events inside the device pipelines: off by default (library 0.5); turn on before a call whose `last_stage_times` are wanted
@@ -345,6 +363,7 @@ fn signatures(msgs: &[&[u8]], v1: bool, pk: &[u8], nul: &[u8], c: &[u8], s: &[u8
     (0..msgs.len()).map(|i| {
         let st = status[i];
         let nullifier = get_point(&nul[64 * i..]);
+        if st & PLUME_STATUS_SELFCHECK_FAILED != 0 { return Err(SignError::SelfCheckFailed); }
         if st & PLUME_STATUS_BAD_SCALAR != 0 { return Err(SignError::BadScalar); }
         if st & PLUME_STATUS_IDENTITY != 0 && nullifier == AffinePoint::IDENTITY { return Err(SignError::HashedToIdentity); }     // :61
         if st & PLUME_STATUS_C_NOT_CANONICAL != 0 { return Err(SignError::ChallengeNotCanonical); }                           // :91
@@ -440,7 +459,8 @@ pub struct PlumeSigner<'signing> {
 impl<'signing> PlumeSigner<'signing> {
     pub fn new(secret_key: &'signing SecretKey, v1: bool) -> Self { PlumeSigner { secret_key, v1 } }
     /// `RandomizedSigner::try_sign_with_rng` (randomizedsigner.rs:43-112).  `Err` only where the reference returns `signature::Error` (h2c failure,
-    /// unreachable with this DST); the reference's `expect`s panic here too, with its messages.
+    /// unreachable with this DST), where the library call fails, or where the signer's self-check withheld the signature (`HipError::is_self_check_failed`);
+    /// the reference's `expect`s panic here too, with its messages.
     pub fn try_sign_with_rng(&self, engine: &HipEngine, rng: &mut impl CryptoRngCore, msg: &[u8]) -> Result<PlumeSignature, HipError> {
         let mut out = engine.sign_batch(std::slice::from_ref(self.secret_key), &[msg], self.v1, rng)?;
         match out.remove(0) {
@@ -449,6 +469,7 @@ impl<'signing> PlumeSigner<'signing> {
             Err(SignError::ChallengeNotCanonical) => panic!("it should be impossible to get the hash equal to zero"),
             Err(SignError::ZeroResponse) => panic!("something is terribly wrong if the nonce is equal to negated product of the secret and the hash"),
             Err(SignError::BadScalar) => unreachable!("SecretKey is in [1, n-1] by construction"),
+            Err(SignError::SelfCheckFailed) => Err(HipError::self_check_failed()),
         }
     }
     pub fn sign_with_rng(&self, engine: &HipEngine, rng: &mut impl CryptoRngCore, msg: &[u8]) -> PlumeSignature {
@@ -464,6 +485,7 @@ impl<'signing> PlumeSigner<'signing> {
             Err(SignError::ChallengeNotCanonical) => panic!("it should be impossible to get the hash equal to zero"),
             Err(SignError::ZeroResponse) => panic!("something is terribly wrong if the nonce is equal to negated product of the secret and the hash"),
             Err(SignError::BadScalar) => unreachable!("SecretKey is in [1, n-1] by construction; a derived nonce outside it has probability below 2^-2000"),
+            Err(SignError::SelfCheckFailed) => Err(HipError::self_check_failed()),
         }
     }
 }

@@ -46,6 +46,9 @@ struct Error : std::runtime_error {
     int code;
     Error(int c, const std::string& what) : std::runtime_error(what), code(c) {}
 };
+// the signer's self-check (Engine::set_sign_selfcheck(1)) withheld a signature: the signer called it good (status 0) but its records do not verify -- a pk that is not
+// sk G handed to sign_with_r, or a computation gone wrong.  Its own class: the reference has no such error, it releases the signature.
+struct SelfCheckError : std::runtime_error { using std::runtime_error::runtime_error; };
 inline void check(int rc, const char* call) {
     if (rc != PLUME_OK) throw Error(rc, std::string(call) + ": " + plume_last_error());
 }
@@ -66,6 +69,10 @@ class Engine {
     // them, 2 = and no table address derived from one -- the property k256's constant-time multiplication has (rust-k256/src/randomizedsigner.rs:51-70 multiplies by secrets).
     void set_sign_uniform(int level) { check(plume_set_sign_uniform(ctx_, level), "plume_set_sign_uniform"); }
     int sign_uniform() const { const int l = plume_get_sign_uniform(ctx_); check(l < 0 ? l : 0, "plume_get_sign_uniform"); return l; }   // 1 by default (library 0.4)
+    // The signer's self-check (plume_hip.h, plume_set_sign_selfcheck): 1 = every sign call verifies its own records on the GPU before anything reaches the caller's arrays;
+    // a signature that does not verify is withheld and the façades throw SelfCheckError.  0 (the default) = off.
+    void set_sign_selfcheck(int mode) { check(plume_set_sign_selfcheck(ctx_, mode), "plume_set_sign_selfcheck"); }
+    int sign_selfcheck() const { const int m = plume_get_sign_selfcheck(ctx_); check(m < 0 ? m : 0, "plume_get_sign_selfcheck"); return m; }
     void set_stage_timing(bool on) { check(plume_set_stage_timing(ctx_, on ? 1 : 0), "plume_set_stage_timing"); }   // off by default (library 0.5): needed before last_stage_times
     void set_host_lanes(int lanes) { check(plume_set_host_lanes(ctx_, lanes), "plume_set_host_lanes"); }
     void set_eq1_short(int mode) { check(plume_set_eq1_short(ctx_, mode), "plume_set_eq1_short"); }   // the verifier's first equation where R is given (plume_hip.h): 1 short for large calls (default), 3 short always, 0 long, 2 test
@@ -318,6 +325,7 @@ class PlumeSigner {
 
 // status byte of the signer -> the reference's panics, in the order the reference would hit them (randomizedsigner.rs:61,91,95)
 inline void raise_for_status(uint8_t st, const AffinePoint& nullifier) {
+    if (st & PLUME_STATUS_SELFCHECK_FAILED) throw plume_hip::SelfCheckError("the signature does not verify and was withheld (plume_set_sign_selfcheck)");
     if (st & PLUME_STATUS_BAD_SCALAR) throw Panic("secret key or nonce outside [1, n-1] (no SecretKey / NonZeroScalar holds it)");
     if ((st & PLUME_STATUS_IDENTITY) && nullifier.is_identity()) throw Panic("something is drammatically wrong if the input hashed to the identity");
     if (st & PLUME_STATUS_C_NOT_CANONICAL) throw Panic("it should be impossible to get the hash equal to zero");
@@ -682,6 +690,7 @@ inline std::vector<Signature> sign_with_r_batch(const std::vector<std::pair<Publ
     plume_hip::check(rc, "plume_sign_batch");
     out.reserve(n);
     for (size_t i = 0; i < n; i++) {
+        if (st[i] & PLUME_STATUS_SELFCHECK_FAILED) throw plume_hip::SelfCheckError("the signature does not verify under the supplied pk and was withheld (plume_set_sign_selfcheck)");
         // Fr holds zero, so a zero sk / r is a value here; the engine's k256-shaped status bits are not errors of this API, except an off-curve pk
         if ((st[i] & PLUME_STATUS_BAD_SCALAR) && !keypairs[i].second.is_zero() && !r_scalars[i].is_zero()) throw HashToCurveError("`pk` is not a point of the curve");
         out.emplace_back(PlumeSignaturePublic{messages[i], Fr::from_be_bytes_mod_order(&s[32 * i], 32), Affine::from_bytes64(&nul[64 * i]), version},

@@ -44,11 +44,15 @@ typedef struct plume_ctx plume_ctx;
 #define PLUME_STATUS_BAD_SCALAR 2      /* sk or r outside [1, n-1] (NonZeroScalar / SecretKey invariant), a supplied pk not on the curve, or \
                                           (device-resident calls) message offsets that decrease or reach past msgs_bytes */
 #define PLUME_STATUS_IDENTITY 4        /* H == identity (randomizedsigner.rs:61) or s == 0 (randomizedsigner.rs:95) */
+#define PLUME_STATUS_SELFCHECK_FAILED 8 /* plume_set_sign_selfcheck(ctx, 1) only: the signer called the item good (no other bit) but its records do not verify; \
+                                           every output record of the item is all zero */
 
 /* Create a context bound to HIP device `device_id` (>= 0): streams, events and a small scratch area; about 1.5 ms.  The generator's fixed tables are built by the first call
  * that needs them, ONCE per device and process -- (1..2^23)*G for the verifier's 24-bit windows (1 GiB, first verify / verify_non_zk call) and the signer's doubling-free
  * comb, 15 windows of 2^17 rows (252 MiB, first sign / SEC1-DER export / aggregate check) -- about 18 ms for both, synchronously inside that call.  They are read-only and
- * shared by every context of the process on that device; the last context to go frees them.  A verify-only process never holds the comb, a sign-only one never the 1 GiB table.
+ * shared by every context of the process on that device; the last context to go frees them.  A verify-only process never holds the comb, a sign-only one never the 1 GiB table
+ * -- unless it signs with the self-check on (plume_set_sign_selfcheck): the check is a verify_non_zk call, so such a signer holds the 1 GiB window table as well (equation 2
+ * and the fallback of equation 1's short form walk it), next to the comb (level 0 / 1, and the check's short first equation for calls of at least 2^16 items) or the scanned table (level 2).
  * plume_destroy (and plume_set_in_flight when it takes lanes away) waits for the context's OWN work before it releases anything -- the last device-resident call it was
  * given, on whatever stream (every such call leaves an event behind its last kernel and waits for its predecessor's), and its private streams -- and does not call
  * hipDeviceSynchronize.  It then frees its workspace with hipFree, which the HIP runtime may itself implement with a device-wide wait: a caller that must not stall
@@ -71,7 +75,7 @@ int plume_shard_numa_node(const plume_ctx* ctx, int shard);
 void plume_destroy(plume_ctx* ctx);
 /* Last error text of this thread (valid until the next failing call on the thread). */
 const char* plume_last_error(void);
-/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.8: derived signing nonces (plume_sign_batch_rfc6979*); 0.7: the persistent nullifier set (plume_nullset_*); 0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
+/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.9: the signer's self-check (plume_set_sign_selfcheck, PLUME_STATUS_SELFCHECK_FAILED); 0.8: derived signing nonces (plume_sign_batch_rfc6979*); 0.7: the persistent nullifier set (plume_nullset_*); 0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
  * the signer defaults to uniform level 1; the generator tables are built by the first call that needs them; stream = NULL means the stream of the context the caller
  * holds; plume_destroy waits for the context's own work only (its last call on any stream and its private streams), not for the whole device. */
 const char* plume_version(void);
@@ -116,6 +120,25 @@ int plume_set_in_flight(plume_ctx* ctx, int batches);
 int plume_set_sign_uniform(plume_ctx* ctx, int level);
 /* the level this context signs at (0, 1, 2), or a negative error code */
 int plume_get_sign_uniform(const plume_ctx* ctx);
+/* The signer's self-check (library 0.9), off by default: a deterministic signer that computes one signature wrongly and releases it leaks sk (s = r + sk c: the same
+ * derived r under two challenges gives sk = (s - s') / (c - c')), and a pk_in that is on the curve but is not sk G yields status 0 and records no verifier accepts.
+ * mode 0 = off: every byte, status, stage and table of the signer is what it was before 0.9.  mode 1 = check every item; any other mode is PLUME_ERR_ARG.
+ * Env PLUME_SIGN_SELFCHECK=<mode> sets the default of new contexts.  Like plume_set_sign_uniform the setting reaches in-flight lanes, the host pipeline's lanes and the
+ * shards of a plume_init_multi context, and it applies to EVERY sign entry point: plume_sign_batch, _sec1, _rfc6979 and their _device forms.  With mode 1, for item i:
+ *   - the signer's own status is non-zero: the item is released exactly as mode 0 writes it, same bytes, same status;
+ *   - otherwise pk (derived or pk_in), nullifier, c, s, r_point, hashed_to_curve_r are checked with msg_i as verify_non_zk(version, ..., digest_private = c) -- H
+ *     recomputed from (msg, pk), the challenge re-hashed, both group equations; that covers all six outputs for V1 and V2 and, for a status-0 item, is true exactly when
+ *     PlumeSignature::verify is.  Verdict 1: the records are released byte-identical to mode 0, status 0.  Any other verdict: EVERY output record of the item is all
+ *     zero (64-, 33- and 32-byte forms alike) and status[i] = PLUME_STATUS_SELFCHECK_FAILED.
+ * Nothing unchecked reaches caller memory: the sign kernels write context-owned staging (always 64-byte records; the _sec1 signers compress after the gate), the check
+ * reads the staging, and one kernel (k_sign_release) writes the caller's arrays -- device-resident arrays on the caller's stream as well as the host pipeline's slots.
+ * The staging is wiped on the call's stream behind the release.  The device-resident forms gain no host synchronisation.  The check runs the verifier's own stages on
+ * the workspace the sign call holds and obeys the short-form / pair / split rules of a plume_verify_non_zk_batch_device call of that size; its cost is that call's
+ * (plus 0.8 GB of copies per 2^20 items), its workspace the verifier's (3.9 KB per item in flight) plus 322 B of staging per item, its tables: plume_init.
+ * plume_last_stage_times after such a call lists the sign stages, then the check's stages, then "sign_release"; plume_last_msm_kernel / plume_last_redo_tasks report the check's verify.
+ * The check detects a wrong RESULT.  It says nothing about power or EM side channels, and a fault that hits signer and check alike (a wrong msg buffer) is out of its reach. */
+int plume_set_sign_selfcheck(plume_ctx* ctx, int mode);
+int plume_get_sign_selfcheck(const plume_ctx* ctx);
 /* The verifier's first equation, R' = s G - c pk compared with the given r_point (rust-k256/src/lib.rs:101,115-121), for calls that GIVE r_point as a 64-byte record (V1
  * verify, verify_non_zk).  It is an identity check, so it may be multiplied by any tau != 0: with (tau, upsilon) from a half-GCD of c in the Eisenstein integers
  * (tau c = upsilon mod n through lambda; all four coefficients of about 64 bits -- csrc/plume_eis.h) the GPU checks  k G - upsilon pk - (tau - 1) R == R,  k = tau s mod n:
@@ -140,6 +163,7 @@ int plume_get_eq1_short(const plume_ctx* ctx, size_t* min_items);
  *                            addition (default 16384; 0: never): on a machine a small call leaves empty, the kernel's time is one chain's latency
  *   PLUME_JOBS_PER_LANE      jobs per lane of the table passes (default: 3..6 by batch size)
  *   PLUME_SIGN_UNIFORM       default level of plume_set_sign_uniform (0, 1, 2; default 1)
+ *   PLUME_SIGN_SELFCHECK     default mode of plume_set_sign_selfcheck (0, 1; default 0)
  *   PLUME_EQ1_SHORT, PLUME_EQ1_SHORT_MIN   plume_set_eq1_short's mode and the smallest call that takes the short form (default 1, 65536)
  *   PLUME_NO_AFFINITY        multi-device contexts: leave the shard threads' CPU affinity alone */
 /* Host-pointer calls only: a call is cut into pieces; piece k+1 uploads while piece k computes and piece k-1 downloads (an upload, a download and the compute streams,
@@ -452,10 +476,10 @@ int plume_set_stage_timing(plume_ctx* ctx, int on);
 /* Measurement / test hook: the number of multi-scalar tasks (two per item) of the last verify call on this context whose unchecked addition chain met p == +-q and that
  * the second, dense launch redid with checked additions (k_verify_msm_redo).  Honest batches: 0.  Crafted items (pk = +-k G for small k with s = +-c, ...) file one or two
  * tasks each: that is all they cost -- their wavefront neighbours no longer wait for them.  Counts the last device-resident call (for a host-pointer call: its last piece;
- * for a multi-device context: the first shard).  Synchronises with the device. */
+ * for a multi-device context: the first shard).  A sign call with the self-check on (plume_set_sign_selfcheck) counts as a verify call here: its check's.  Synchronises with the device. */
 int plume_last_redo_tasks(plume_ctx* ctx, uint64_t* count);
 /* Measurement hook: the multi-scalar kernel the last verify call served by this context launched -- "k_verify_msm" (both equations in the long form), "k_verify_msm_s"
- * (equation 1 in the short form) or "k_verify_msm_pair" (half chains: small calls); NULL before the first verify.  Reports the same call as plume_last_stage_times.  A static string. */
+ * (equation 1 in the short form) or "k_verify_msm_pair" (half chains: small calls); NULL before the first verify.  Reports the same call as plume_last_stage_times; after a sign call with the self-check on, the kernel of its check.  A static string. */
 const char* plume_last_msm_kernel(const plume_ctx* ctx);
 /* Measurement hook: the shader clock (GHz) the multi-scalar kernel of the last verify call on this context ran at, sampled INSIDE that kernel -- one workgroup in 32 adds the
  * shader-clock cycles and the constant-rate wall-clock ticks it lived for to two counters.  kernel time x this clock = the kernel's duration in cycles, a figure that does not

@@ -132,10 +132,15 @@ def _load():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
+    # the signer's self-check (library 0.9; Engine.set_sign_selfcheck raises PlumeHipError on an older build selected through PLUME_HIP_LIB)
+    for name, args in (("plume_set_sign_selfcheck", [vp, i]), ("plume_get_sign_selfcheck", [vp])):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
     _lib = lib
-    if _version(lib) < (0, 8) and not os.environ.get("PLUME_HIP_LIB"):
+    if _version(lib) < (0, 9) and not os.environ.get("PLUME_HIP_LIB"):
         _lib = None
-        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.8 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.9 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
     return lib
 
 
@@ -148,7 +153,8 @@ def exported_symbols():
             "plume_hash_to_curve_batch", "plume_nullifier_first_occurrence", "plume_nullifier_first_occurrence_device", "plume_verify_batch_device", "plume_sign_batch_device", "plume_hash_to_curve_batch_device",
             "plume_last_stage_times", "plume_microbench", "plume_microbench_last_ticks",
             "plume_nullset_create", "plume_nullset_destroy", "plume_nullset_reserve", "plume_nullset_clear", "plume_nullset_size", "plume_nullset_insert", "plume_nullset_contains",
-            "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device", "plume_sign_batch_rfc6979", "plume_sign_batch_rfc6979_device"]
+            "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device", "plume_sign_batch_rfc6979", "plume_sign_batch_rfc6979_device",
+            "plume_set_sign_selfcheck", "plume_get_sign_selfcheck"]
 
 
 def pack_messages(msgs):
@@ -308,6 +314,24 @@ class Engine:
         rc = self._lib.plume_get_sign_uniform(self._ctx)
         if rc < 0:
             self._chk(rc, "plume_get_sign_uniform")
+        return rc
+
+    def _selfcheck_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None or _version(self._lib) < (0, 9):
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no signer self-check: {name} needs plume_hip >= 0.9 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    def set_sign_selfcheck(self, mode):
+        """the signer's self-check (plume_set_sign_selfcheck): 1 (or True) = every sign call verifies its own records on the GPU (verify_non_zk) before anything reaches
+        the caller's arrays; an item that does not verify comes out all zero with status STATUS_SELFCHECK_FAILED (8).  0 (the default) = off"""
+        self._chk(self._selfcheck_fn("plume_set_sign_selfcheck")(self._ctx, int(mode)), "plume_set_sign_selfcheck")
+
+    def sign_selfcheck(self):
+        """the mode this context signs with (plume_get_sign_selfcheck): 0 by default"""
+        rc = self._selfcheck_fn("plume_get_sign_selfcheck")(self._ctx)
+        if rc < 0:
+            self._chk(rc, "plume_get_sign_selfcheck")
         return rc
 
     def set_eq1_short(self, mode):

@@ -19,6 +19,7 @@
 #include <string>
 #include <thread>
 #include <algorithm>
+#include <atomic>
 #include <memory>
 #include <vector>
 
@@ -28,6 +29,7 @@
 #include "plume_host_logic.h"
 #include "plume_launch.h"
 #include "plume_nonce.h"
+#include "plume_selfcheck.h"
 
 using namespace plume;
 
@@ -171,6 +173,8 @@ struct plume_ctx {
     size_t in_flight_min = 0;                                      // verify / sign calls of fewer items are not dealt out to the lanes (env PLUME_IN_FLIGHT_MIN; 0, the default: every call is)
     plume_ctx* lane_last = nullptr;                               // the lane the last device-resident call went to (plume_last_stage_times, plume_last_redo_tasks)
     DevBuf bases, jobflags, itemflags, tab, tabscr, res, resinf, res2, res2inf, pkaff, sink, redo, digs, eq1fall, eq1k, clk;
+    int sign_selfcheck = 0;                                        // plume_set_sign_selfcheck: 1 = every sign call stages its outputs here, verifies them and releases what verifies (sign_device)
+    DevBuf scstage;                                                // ... the staging: six records in the 64-byte form, the signer's status and the check's verdict, 322 B / item; wiped after the release
     DevBuf nonce;                                                  // the derived-nonce signer: r of the call in flight, 32 B / item, wiped on the call's stream after sign_final
     int eq1_short = 1;                                             // verify calls that give R: equation 1 in its short form (plume_eis.h).  0 = long form always (A/B), 2 = test: every item takes the fallback
     size_t eq1_short_min = (size_t)1 << 16;                        // ... for calls of at least this many items.  Round 6 sweep on one box, interleaved (profiles/r06_eq1_threshold.txt), now that the
@@ -188,7 +192,7 @@ struct plume_ctx {
 // Every per-context tunable a derived context (an in-flight lane, the host pipeline's second lane, a shard) has to share with the context it serves: ONE place, so that a new
 // knob cannot reach some derived contexts and miss others (round 4's host lane did not inherit sign_uniform: VERDICT r4).
 static void inherit_tunables(plume_ctx* to, const plume_ctx* from) {
-    to->chunk = from->chunk; to->sub_batches = from->sub_batches; to->overlap_min = from->overlap_min; to->sign_uniform = from->sign_uniform;
+    to->chunk = from->chunk; to->sub_batches = from->sub_batches; to->overlap_min = from->overlap_min; to->sign_uniform = from->sign_uniform; to->sign_selfcheck = from->sign_selfcheck;
     to->ingest_split_max = from->ingest_split_max; to->split_scalars = from->split_scalars; to->msm_pair_max = from->msm_pair_max;
     to->jobs_per_lane = from->jobs_per_lane; to->jobs_per_lane_forced = from->jobs_per_lane_forced;
     to->host_piece = from->host_piece; to->host_first_piece = from->host_first_piece; to->host_tail_piece = from->host_tail_piece; to->host_register_min = from->host_register_min;
@@ -277,7 +281,7 @@ extern "C" const char* plume_last_error(void) { return g_err.c_str(); }
 #ifndef PLUME_BUILD_ID
 #define PLUME_BUILD_ID "unknown"
 #endif
-extern "C" const char* plume_version(void) { return "plume_hip 0.8 gfx950 build=" PLUME_BUILD_ID; }
+extern "C" const char* plume_version(void) { return "plume_hip 0.9 gfx950 build=" PLUME_BUILD_ID; }
 
 static void destroy_single(plume_ctx* ctx) {
     for (plume_ctx* l : ctx->lanes) destroy_single(l);
@@ -290,7 +294,7 @@ static void destroy_single(plume_ctx* ctx) {
     if (ctx->ws_used && ctx->ws_free) (void)hipEventSynchronize(ctx->ws_free);
     for (hipStream_t q : {ctx->stream, ctx->up, ctx->down, ctx->side, ctx->pre}) if (q) (void)hipStreamSynchronize(q);
     for (DevBuf* b : {&ctx->bases, &ctx->jobflags, &ctx->itemflags, &ctx->tab, &ctx->tabscr, &ctx->res, &ctx->resinf, &ctx->res2, &ctx->res2inf, &ctx->pkaff,
-                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
+                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->scstage, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
         b->release();
     for (DevBuf& b : ctx->agg) b.release();
     if (ctx->fixed) {
@@ -332,6 +336,7 @@ static int init_single(plume_ctx* ctx) {
     if (const char* e = std::getenv("PLUME_SPLIT_SCALARS")) ctx->split_scalars = std::atoi(e) != 0;   // A/B knob
     if (const char* e = std::getenv("PLUME_INGEST_SPLIT_MAX")) { long v = std::atol(e); if (v >= 0) ctx->ingest_split_max = (size_t)v; }   // tuning knob (0: never)
     if (const char* e = std::getenv("PLUME_SIGN_UNIFORM")) ctx->sign_uniform = std::min(2, std::max(0, std::atoi(e)));   // default of new contexts (plume_set_sign_uniform); 0 opts out of the uniform schedule
+    if (const char* e = std::getenv("PLUME_SIGN_SELFCHECK")) { int v = std::atoi(e); if (v == 0 || v == 1) ctx->sign_selfcheck = v; }   // default of new contexts (plume_set_sign_selfcheck)
     if (const char* e = std::getenv("PLUME_EQ1_SHORT")) { int v = std::atoi(e); if (v >= 0 && v <= 3) ctx->eq1_short = v; }   // A/B and test knob (plume_eis.h)
     if (const char* e = std::getenv("PLUME_EQ1_SHORT_MIN")) { long v = std::atol(e); if (v >= 0) ctx->eq1_short_min = (size_t)v; }   // tuning knob
     if (const char* e = std::getenv("PLUME_IN_FLIGHT_MIN")) { long v = std::atol(e); if (v >= 0) ctx->in_flight_min = (size_t)v; }   // tuning knob (plume_set_in_flight)
@@ -622,6 +627,22 @@ extern "C" int plume_set_eq1_short(plume_ctx* ctx, int mode) {
     propagate_tunables(ctx);
     return 0;
 }
+// The signer's self-check (include/plume_hip.h, plume_set_sign_selfcheck; the gate itself: sign_device).  The release kernel's launcher is a hook that
+// plume_selfcheck_capi.hip files here, so that this file links without it (tests/hostsim).
+static std::atomic<SignReleaseLaunch> g_sign_release{nullptr};          // written once, when the library is loaded; read by sign_device on any thread
+int plume::capi_sign_release_hook(SignReleaseLaunch release_fn) { g_sign_release.store(release_fn); return 0; }
+int plume::capi_set_sign_selfcheck(plume_ctx* ctx, int mode, SignReleaseLaunch release_fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "plume_set_sign_selfcheck: null context");
+    if (mode != 0 && mode != 1) return fail(PLUME_ERR_ARG, "plume_set_sign_selfcheck: the mode is 0 or 1");
+    if (release_fn && !g_sign_release.load()) g_sign_release.store(release_fn);   // (filed already by the static registration of plume_selfcheck_capi.hip)
+    ctx->sign_selfcheck = mode;
+    propagate_tunables(ctx);
+    return 0;
+}
+extern "C" int plume_get_sign_selfcheck(const plume_ctx* ctx) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "plume_get_sign_selfcheck: null context");
+    return ctx->sign_selfcheck;
+}
 extern "C" int plume_get_sign_uniform(const plume_ctx* ctx) {
     if (!ctx) return fail(PLUME_ERR_ARG, "plume_get_sign_uniform: null context");
     return ctx->sign_uniform;
@@ -748,15 +769,32 @@ static int pre_events(plume_ctx* ctx, size_t k) {
 static int side_stream(plume_ctx* ctx) { if (!ctx->side) HIPCHK(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking)); return 0; }
 static int pre_stream(plume_ctx* ctx) { if (!ctx->pre) HIPCHK(hipStreamCreateWithFlags(&ctx->pre, hipStreamNonBlocking)); return 0; }
 
+// Equation 1 in its short form (plume_eis.h) whenever the call GIVES r_point as a 64-byte record -- V1 verify and verify_non_zk; the SEC1 ingest keeps R compressed
+// (a square root per item would cost more than the form saves) and V2 verify has no R: the long form.  One more table job per item (R), the comb of G.
+static bool verify_eq1_short(const plume_ctx* ctx, int version, int mode, size_t n, bool rpt64) {
+    return ctx->eq1_short != 0 && (n >= ctx->eq1_short_min || ctx->eq1_short >= 2) && rpt64 && (version == 1 || mode == PLUME_MODE_NON_ZK);
+}
+// the workspace of a verify call of n items cut at `cut`, J table jobs per item (4 with the short first equation, else 3).  The self-checking signer calls it before it
+// launches anything, so that the check behind its sign stages cannot fail on -- or wait for -- an allocation.
+static int verify_workspace(plume_ctx* ctx, size_t n, size_t J, const std::vector<size_t>& cut) {
+    const size_t nsub = cut.size() - 1;
+    size_t scr_bytes = 0;
+    for (size_t k = 0; k < nsub; k++) scr_bytes = std::max(scr_bytes, table_stage_scratch(ctx, J * (cut[k + 1] - cut[k]), 3 * (cut[k + 1] - cut[k])));
+    if (ctx->bases.ensure((size_t)PLUME_BASE_WORDS * 4 * J * n) || ctx->jobflags.ensure(J * n) || ctx->itemflags.ensure(n) || ctx->tab.ensure((size_t)PLUME_TAB_WORDS * 4 * J * n) ||
+        ctx->tabscr.ensure(scr_bytes) ||
+        ctx->res.ensure((size_t)PLUME_JAC_WORDS * 4 * 2 * n) || ctx->resinf.ensure(2 * n) || ctx->redo.ensure((2 * n + nsub) * 4) || ctx->digs.ensure((size_t)PLUME_VDIG_ROWS * n) ||
+        (J == 4 && (ctx->eq1fall.ensure(n) || ctx->eq1k.ensure(32 * n))))
+        return PLUME_ERR_HIP;
+    return 0;
+}
+
 static int verify_device(plume_ctx* ctx, int version, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, const uint8_t* pk, const uint8_t* nul,
                          const uint8_t* c, const uint8_t* s, const uint8_t* rpt, const uint8_t* hr, uint8_t* ok, hipStream_t st,
                          const uint8_t* preflags = nullptr, bool continue_timer = false, const uint8_t* rpt33 = nullptr, const uint8_t* hr33 = nullptr) {
     if (n == 0) return 0;
     if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
     if (int rc = need_gtab(ctx)) return rc;
-    // Equation 1 in its short form (plume_eis.h) whenever the call GIVES r_point as a 64-byte record -- V1 verify and verify_non_zk; the SEC1 ingest keeps R compressed
-    // (a square root per item would cost more than the form saves) and V2 verify has no R: the long form.  One more table job per item (R), the comb of G.
-    const bool eq1short = ctx->eq1_short != 0 && (n >= ctx->eq1_short_min || ctx->eq1_short >= 2) && rpt != nullptr && rpt33 == nullptr && (version == 1 || mode == PLUME_MODE_NON_ZK);
+    const bool eq1short = verify_eq1_short(ctx, version, mode, n, rpt != nullptr && rpt33 == nullptr);
     if (eq1short) { if (int rc = need_gcomb(ctx)) return rc; }
     const size_t J = eq1short ? 4 : 3;
     if (!continue_timer) { if (int rc = ws_acquire(ctx, st)) return rc; }     // continue_timer: the caller (SEC1 ingest) holds the workspace already
@@ -764,13 +802,7 @@ static int verify_device(plume_ctx* ctx, int version, int mode, size_t n, const 
     const std::vector<size_t> cut = sub_batch_bounds(ctx, n);
     const size_t nsub = cut.size() - 1;
     const bool overlapped = nsub > 1;
-    size_t scr_bytes = 0;
-    for (size_t k = 0; k < nsub; k++) scr_bytes = std::max(scr_bytes, table_stage_scratch(ctx, J * (cut[k + 1] - cut[k]), 3 * (cut[k + 1] - cut[k])));
-    if (ctx->bases.ensure((size_t)PLUME_BASE_WORDS * 4 * J * n) || ctx->jobflags.ensure(J * n) || ctx->itemflags.ensure(n) || ctx->tab.ensure((size_t)PLUME_TAB_WORDS * 4 * J * n) ||
-        ctx->tabscr.ensure(scr_bytes) ||
-        ctx->res.ensure((size_t)PLUME_JAC_WORDS * 4 * 2 * n) || ctx->resinf.ensure(2 * n) || ctx->redo.ensure((2 * n + nsub) * 4) || ctx->digs.ensure((size_t)PLUME_VDIG_ROWS * n) ||
-        (eq1short && (ctx->eq1fall.ensure(n) || ctx->eq1k.ensure(32 * n))))
-        return PLUME_ERR_HIP;
+    if (int rc = verify_workspace(ctx, n, J, cut)) return rc;
     if (overlapped) { if (int rc = pre_events(ctx, nsub)) return rc; if (int rc = pre_stream(ctx)) return rc; }
     StageTimer& t = ctx->timer;
     if (!continue_timer) t.begin(st);
@@ -831,9 +863,28 @@ static int sign_device(plume_ctx* ctx, int version, size_t n, const uint8_t* msg
     if (n == 0) return 0;
     if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
     if (int rc = need_sign_tables(ctx)) return rc;
+    // The self-check (plume_set_sign_selfcheck): the sign kernels write ctx->scstage instead of the caller's arrays, always 64-byte records; verify_device checks the
+    // staging as a verify_non_zk call (digest_private = c) on this workspace and this stream; the release kernel writes the caller's arrays; the staging is wiped.
+    const bool selfcheck = ctx->sign_selfcheck != 0;
+    const SignReleaseLaunch release_fn = selfcheck ? g_sign_release.load() : nullptr;
+    if (selfcheck && !release_fn) return fail(PLUME_ERR_ARG, "the signer's self-check is on but its release kernel is not part of this build");
+    const bool sc_eq1short = selfcheck && verify_eq1_short(ctx, version, PLUME_MODE_NON_ZK, n, true);
+    if (selfcheck) { if (int rc = need_fixed(ctx, true, sc_eq1short, false)) return rc; }   // the tables the check's verify needs, built before anything is queued
     if (int rc = ws_acquire(ctx, st)) return rc;
     WsHold hold(ctx, st);
     const std::vector<size_t> cut = sub_batch_bounds(ctx, n);
+    constexpr size_t kStageBytes = 4 * 64 + 2 * 32 + 2;                         // per item: pk, nul, rpt, hr | c, s | status, verdict -- arrays in that order, each 16-byte aligned but the last
+    if (selfcheck && (verify_workspace(ctx, n, sc_eq1short ? 4 : 3, cut) || ctx->scstage.ensure(kStageBytes * n) || (ctx->timer.on && ctx->clk.ensure(16)))) return PLUME_ERR_HIP;
+    uint8_t* const stg = ctx->scstage.as<uint8_t>();
+    uint8_t *const g_pk = stg, *const g_nul = stg + 64 * n, *const g_rpt = stg + 128 * n, *const g_hr = stg + 192 * n, *const g_c = stg + 256 * n, *const g_s = stg + 288 * n,
+            *const g_status = stg + 320 * n, *const g_ok = stg + 321 * n;
+    struct StageWipe {                                                          // failure paths only: a call that fails behind the sign kernels still wipes what they staged, in front of ws_free (~WsHold)
+        plume_ctx* ctx; size_t bytes; hipStream_t st;
+        ~StageWipe() { if (bytes) (void)hipMemsetAsync(ctx->scstage.p, 0, bytes, st); }
+    } stage_wipe{ctx, selfcheck ? kStageBytes * n : 0, st};
+    uint8_t *const u_pk = pk, *const u_nul = nul, *const u_c = c, *const u_s = s, *const u_rpt = rpt, *const u_hr = hr, *const u_status = status;   // the caller's arrays
+    const bool u_out33 = out33;
+    if (selfcheck) { pk = g_pk; nul = g_nul; c = g_c; s = g_s; rpt = g_rpt; hr = g_hr; status = g_status; out33 = false; }
     const size_t nsub = cut.size() - 1;
     const bool overlapped = nsub > 1;
     size_t scr_bytes = 0;
@@ -888,6 +939,18 @@ static int sign_device(plume_ctx* ctx, int version, size_t n, const uint8_t* msg
     HIPCHK(hipMemsetAsync(ctx->res.p, 0, (size_t)PLUME_JAC_WORDS * 4 * 2 * n, st));
     if (nonce_fn) HIPCHK(hipMemsetAsync(ctx->nonce.p, 0, 32 * n, st));      // ... and the derived nonces themselves, which never leave the device
     HIPCHK(hipGetLastError());
+    if (selfcheck) {
+        if (int rc = verify_device(ctx, version, PLUME_MODE_NON_ZK, n, msgs, msg_off, msgs_bytes, g_pk, g_nul, g_c, g_s, g_rpt, g_hr, g_ok, st, nullptr, true)) return rc;
+        ReleaseArgs ra;
+        ra.n = (uint32_t)n; ra.out33 = u_out33 ? 1 : 0; ra.stage_status = g_status; ra.verdict = g_ok; ra.status = u_status;
+        const uint8_t* const from[6] = {g_pk, g_nul, g_c, g_s, g_rpt, g_hr};
+        uint8_t* const to[6] = {u_pk, u_nul, u_c, u_s, u_rpt, u_hr};
+        for (int k = 0; k < 6; k++) { ra.stage[k] = from[k]; ra.out[k] = to[k]; }
+        release_fn(ra, st); t.stage("sign_release", st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(ctx->scstage.p, 0, kStageBytes * n, st));        // a withheld (c, s) is precisely the value that must not linger
+        stage_wipe.bytes = 0;
+    }
     return hold.release();
 }
 

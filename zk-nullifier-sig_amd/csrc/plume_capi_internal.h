@@ -1,4 +1,4 @@
-// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
+// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -27,5 +27,13 @@ __attribute__((visibility("hidden"))) int capi_sign_derived_device(plume_ctx* ct
                                                                    const uint8_t* sk, const uint8_t* aux, const uint8_t* pk_in, uint8_t* pk, uint8_t* nullifier, uint8_t* c,
                                                                    uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* status, void* stream,
                                                                    SignNonceLaunch nonce_fn);
+
+// The signer's self-check (plume_set_sign_selfcheck): with mode 1 every sign entry point stages its outputs in the context, checks them with the verifier's stages and
+// lets the release kernel write the caller's arrays.  That kernel's launcher comes in as a hook, like the nonce kernel's: plume_capi.hip never names it.
+// capi_sign_release_hook files the launcher for contexts that take their mode from the environment (returns 0); capi_set_sign_selfcheck is the setter's body.
+struct ReleaseArgs;
+typedef void (*SignReleaseLaunch)(const ReleaseArgs& a, hipStream_t st);
+__attribute__((visibility("hidden"))) int capi_sign_release_hook(SignReleaseLaunch release_fn);
+__attribute__((visibility("hidden"))) int capi_set_sign_selfcheck(plume_ctx* ctx, int mode, SignReleaseLaunch release_fn);
 
 }  // namespace plume

@@ -11,6 +11,7 @@ Everything cryptographic (hash_to_curve, the scalar multiplications, the c-hash,
 kernels; this module only marshals bytes and reproduces the reference's error behaviour:
   * `expect(..)` panics of the signer (randomizedsigner.rs:61,91,95) -> PlumePanic
   * `signature::Error` (randomizedsigner.rs:59) -> SignatureError (unreachable for this DST, as in the reference)
+  * the signer's self-check, when the engine has it on (Engine.set_sign_selfcheck), withholding a signature -> PlumeSelfCheckError
   * NonZeroScalar / on-curve invariants of the Rust types -> ValueError at construction
 A single sign/verify is a batch of one; callers with many signatures should use Engine.verify_batch / sign_batch.
 """
@@ -29,6 +30,14 @@ _N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
 
 class PlumePanic(RuntimeError):
     """the reference signer would `panic!` here (randomizedsigner.rs:61,91,95)"""
+
+
+class PlumeSelfCheckError(RuntimeError):
+    """the signer's self-check (Engine.set_sign_selfcheck(1)) withheld the signature: the signer called it good but its records do not verify
+    (status bit 8, PLUME_STATUS_SELFCHECK_FAILED).  Not one of the reference's panics: the reference releases such a signature."""
+
+
+STATUS_SELFCHECK_FAILED = 8
 
 
 class SignatureError(Exception):
@@ -161,6 +170,8 @@ class PlumeSigner:  # rust-k256/src/randomizedsigner.rs:25-41
 
     def _signature(self, o, msg: bytes) -> PlumeSignature:
         st = int(o["status"][0])
+        if st & STATUS_SELFCHECK_FAILED:
+            raise PlumeSelfCheckError("the signature does not verify and was withheld")
         if st & 4 and AffinePoint.from_bytes64(o["nullifier"][0]).is_identity:
             raise PlumePanic("something is drammatically wrong if the input hashed to the identity")               # :61
         if st & 1:
@@ -226,6 +237,8 @@ def sign_with_r(keypair: Tuple[AffinePoint, int], message: bytes, r_scalar: int,
     msgs, off = pack_messages([bytes(message)])
     a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
     o = eng.sign_batch(version.value, msgs, off, a((sk % _N).to_bytes(32, "big")), a((r_scalar % _N).to_bytes(32, "big")), pk_in=a(pk.to_bytes64()))
+    if int(o["status"][0]) & STATUS_SELFCHECK_FAILED:                       # Engine.set_sign_selfcheck(1): e.g. a pk that is not sk G
+        raise PlumeSelfCheckError("the signature does not verify under the supplied pk and was withheld")
     pt = lambda k: AffinePoint.from_bytes64(o[k][0].tobytes())  # noqa: E731
     return (PlumeSignaturePublic(bytes(message), int.from_bytes(o["s"][0].tobytes(), "big"), pt("nullifier"), version),
             PlumeSignaturePrivate(pt("hashed_to_curve_r"), pt("r_point"), int.from_bytes(o["c"][0].tobytes(), "big"), version))

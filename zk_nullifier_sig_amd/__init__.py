@@ -10,6 +10,7 @@ from .plume import (  # noqa: E402,F401
     AffinePoint,
     NonZeroScalar,
     PlumePanic,
+    PlumeSelfCheckError,
     PlumeSignature,
     PlumeSignaturePrivate,
     PlumeSignaturePublic,
