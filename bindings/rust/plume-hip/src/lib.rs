@@ -72,6 +72,12 @@ pub const PLUME_STATUS_C_NOT_CANONICAL: u8 = 1;
 pub const PLUME_STATUS_BAD_SCALAR: u8 = 2;
 pub const PLUME_STATUS_IDENTITY: u8 = 4;
 pub const PLUME_STATUS_SELFCHECK_FAILED: u8 = 8;
+pub const PLUME_RECOVER_MISMATCH: u8 = 0;
+pub const PLUME_RECOVER_MATCH: u8 = 1;
+pub const PLUME_RECOVER_INVALID: u8 = 3;
+pub const PLUME_RECOVER_FMT_AFFINE64: c_int = 0;
+pub const PLUME_RECOVER_FMT_SEC1: c_int = 1;
+pub const PLUME_RECOVER_FMT_REGISTERS: c_int = 2;
 
 #[link(name = "plume_hip")]
 extern "C" {
@@ -120,6 +126,11 @@ extern "C" {
         pk: *mut u8, nullifier: *mut u8, c: *mut u8, s: *mut u8, r_point: *mut u8, hashed_to_curve_r: *mut u8, status: *mut u8) -> c_int;
     fn plume_sign_batch_rfc6979_device(ctx: *mut plume_ctx, version: c_int, n: usize, msgs: *const u8, msg_off: *const u64, msgs_bytes: usize, sk: *const u8, aux: *const u8,
         pk_in: *const u8, pk: *mut u8, nullifier: *mut u8, c: *mut u8, s: *mut u8, r_point: *mut u8, hashed_to_curve_r: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_recover_batch(ctx: *mut plume_ctx, version: c_int, format: c_int, n: usize, msgs: *const u8, msg_off: *const u64, pk: *const u8, nullifier: *const u8,
+        c: *const u8, s: *const u8, r_point: *mut u8, hashed_to_curve_r: *mut u8, hashed_to_curve: *mut u8, status: *mut u8) -> c_int;
+    fn plume_recover_batch_device(ctx: *mut plume_ctx, version: c_int, format: c_int, n: usize, msgs: *const u8, msg_off: *const u64, msgs_bytes: usize, pk: *const u8,
+        nullifier: *const u8, c: *const u8, s: *const u8, r_point: *mut u8, hashed_to_curve_r: *mut u8, hashed_to_curve: *mut u8, status: *mut u8,
+        stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -187,6 +198,23 @@ impl HipEngine {
                                              p.s.as_ptr(), if p.v1 { p.rp.as_ptr() } else { null }, if p.v1 { p.hr.as_ptr() } else { null }, ok.as_mut_ptr()) };
         if rc != 0 { return Err(last_error()); }
         Ok(ok.into_iter().map(|b| b == 1).collect())
+    }
+
+    /// What a V2 signature leaves out (`plume_recover_batch`): `r_point = s G - c pk` and `hashed_to_curve_r = s H - c nullifier`, recomputed on the GPU as
+    /// `check_ec_equations` recomputes them (circuits/circom/verify_nullifier.circom:140-222), with `H = hash_to_curve(msg, pk)` and whether `c` is the hash
+    /// of them that `v1` asks for (the six-encoding hash, or V2's three).  `result[i]` is `None` where the library rejects the item's inputs -- which the
+    /// types here cannot express, so only for an identity nullifier the library accepts and `Some` carries.  The signatures' own `v1specific` is ignored.
+    pub fn recover_batch(&self, sigs: &[PlumeSignature], v1: bool) -> Result<Vec<Option<(PlumeSignatureV1Fields, AffinePoint, bool)>>, HipError> {
+        let n = sigs.len();
+        let stripped: Vec<PlumeSignature> = sigs.iter().map(|s| PlumeSignature { v1specific: None, ..s.clone() }).collect();
+        let p = pack(&stripped);
+        let (mut rp, mut hr, mut h, mut status) = (vec![0u8; 64 * n], vec![0u8; 64 * n], vec![0u8; 64 * n], vec![0u8; n]);
+        let rc = unsafe { plume_recover_batch(self.0, if v1 { 1 } else { 2 }, PLUME_RECOVER_FMT_AFFINE64, n, p.msgs.as_ptr(), p.off.as_ptr(), p.pk.as_ptr(), p.nul.as_ptr(),
+                                              p.c.as_ptr(), p.s.as_ptr(), rp.as_mut_ptr(), hr.as_mut_ptr(), h.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        Ok((0..n).map(|i| if status[i] == PLUME_RECOVER_INVALID { None } else {
+            Some((PlumeSignatureV1Fields { r_point: get_point(&rp[64 * i..]), hashed_to_curve_r: get_point(&hr[64 * i..]) }, get_point(&h[64 * i..]), status[i] == PLUME_RECOVER_MATCH))
+        }).collect())
     }
 
     /// Aggregate pre-filter (no reference counterpart; include/plume_hip.h `plume_aggregate_check`): `Ok(true)` iff every V1 signature of the batch would
@@ -445,6 +473,15 @@ impl NullifierSet {
 impl PlumeSignature {
     /// `PlumeSignature::verify` (rust-k256/src/lib.rs:93-145) on the GPU — a batch of one; use `HipEngine::verify_batch` for throughput.
     pub fn verify(&self, engine: &HipEngine) -> bool { engine.verify_batch(std::slice::from_ref(self)).map(|v| v[0]).unwrap_or(false) }
+    /// The V1-specific fields this signature's `pk, nullifier, c, s` imply (`HipEngine::recover_batch`), for a `c` that is the V1 hash of them: upgrades a compact
+    /// four-field record to a V1 record.  An error when the library rejects the inputs or `c` is not that hash -- never a silent pair of points that do not verify.
+    pub fn recover_v1specific(&self, engine: &HipEngine) -> Result<PlumeSignatureV1Fields, HipError> {
+        match engine.recover_batch(std::slice::from_ref(self), true)?.pop().flatten() {
+            Some((fields, _h, true)) => Ok(fields),
+            Some(_) => Err(HipError("recover_v1specific: c is not the V1 hash of the recovered points".to_string())),
+            None => Err(HipError("recover_v1specific: an input is no value of the reference's types".to_string())),
+        }
+    }
     /// `PlumeSignature::sign_v1` (rust-k256/src/lib.rs:149-151; the doc comments of sign_v1 / sign_v2 are swapped there, the behaviour is this)
     pub fn sign_v1(engine: &HipEngine, secret_key: &SecretKey, msg: &[u8], rng: &mut impl CryptoRngCore) -> Self { PlumeSigner::new(secret_key, true).sign_with_rng(engine, rng, msg) }
     /// `PlumeSignature::sign_v2` (rust-k256/src/lib.rs:154-156)

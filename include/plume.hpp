@@ -270,6 +270,10 @@ struct PlumeSignature {
 
     // PlumeSignature::verify (rust-k256/src/lib.rs:93-145)
     bool verify(Engine& eng = Engine::shared()) const;
+    // The V1-specific fields that pk, nullifier, c, s imply -- r_point = s G - c pk, hashed_to_curve_r = s H - c nullifier, recomputed on the GPU
+    // (plume_hip.h plume_recover_batch) -- for a c that is the V1 hash of them: upgrades a compact four-field record to a V1 record.  Throws SignatureError when an
+    // input is no value of the reference's types and when c is NOT that hash (a V2 signature, a forgery): never a silent pair of points that do not verify.
+    PlumeSignatureV1Fields recover_v1specific(Engine& eng = Engine::shared()) const;
     // rust-k256/src/lib.rs:149-156
     template <class Rng> static PlumeSignature sign_v1(const SecretKey& secret_key, const Bytes& msg, Rng& rng, Engine& eng = Engine::shared());
     template <class Rng> static PlumeSignature sign_v2(const SecretKey& secret_key, const Bytes& msg, Rng& rng, Engine& eng = Engine::shared());
@@ -305,6 +309,15 @@ inline std::vector<bool> verify_batch(const std::vector<PlumeSignature>& sigs, E
     return out;
 }
 inline bool PlumeSignature::verify(Engine& eng) const { return verify_batch(std::vector<PlumeSignature>{*this}, eng)[0]; }
+inline PlumeSignatureV1Fields PlumeSignature::recover_v1specific(Engine& eng) const {
+    plume_hip::PackedMessages m;
+    m.push(message.data(), message.size());
+    uint8_t rp[64], hr[64], st = 0xFF;
+    plume_hip::check(plume_recover_batch(eng.ctx(), 1, PLUME_RECOVER_FMT_AFFINE64, 1, m.data(), m.off.data(), pk.xy.data(), nullifier.xy.data(), c.to_bytes().data(),
+                                         s.to_bytes().data(), rp, hr, nullptr, &st), "plume_recover_batch");
+    if (st != PLUME_RECOVER_MATCH) throw SignatureError();          // PLUME_RECOVER_INVALID, or a c that is not the V1 hash of the recovered points
+    return PlumeSignatureV1Fields{AffinePoint::from_bytes64(rp), AffinePoint::from_bytes64(hr)};
+}
 
 // rust-k256/src/randomizedsigner.rs:25-41: a borrowed secret key and the variant
 class PlumeSigner {

@@ -75,7 +75,8 @@ int plume_shard_numa_node(const plume_ctx* ctx, int shard);
 void plume_destroy(plume_ctx* ctx);
 /* Last error text of this thread (valid until the next failing call on the thread). */
 const char* plume_last_error(void);
-/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.9: the signer's self-check (plume_set_sign_selfcheck, PLUME_STATUS_SELFCHECK_FAILED); 0.8: derived signing nonces (plume_sign_batch_rfc6979*); 0.7: the persistent nullifier set (plume_nullset_*); 0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
+/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.10: point recovery (plume_recover_batch*: r_point, hashed_to_curve_r and hashed_to_curve from pk, nullifier, c, s);
+ * 0.9: the signer's self-check (plume_set_sign_selfcheck, PLUME_STATUS_SELFCHECK_FAILED); 0.8: derived signing nonces (plume_sign_batch_rfc6979*); 0.7: the persistent nullifier set (plume_nullset_*); 0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
  * the signer defaults to uniform level 1; the generator tables are built by the first call that needs them; stream = NULL means the stream of the context the caller
  * holds; plume_destroy waits for the context's own work only (its last call on any stream and its private streams), not for the whole device. */
 const char* plume_version(void);
@@ -430,6 +431,38 @@ int plume_sign_batch_rfc6979_device(plume_ctx* ctx, int version, size_t n,
                                     const uint8_t* sk, const uint8_t* aux, const uint8_t* pk_in,
                                     uint8_t* pk, uint8_t* nullifier, uint8_t* c, uint8_t* s,
                                     uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* status, void* stream);
+
+/* ---- point recovery: r_point and hashed_to_curve_r from c and s  (library 0.10) -------------------------------
+ * A V2 signature drops r_point and hashed_to_curve_r because they follow from the rest (circuits/circom/verify_nullifier.circom:140-222, check_ec_equations):
+ *     r_point = s G - c pk          hashed_to_curve_r = s H - c nullifier          H = hash_to_curve(msg, pk)
+ * plume_verify_batch(version 2) computes both for every item and hashes them; this call runs the same pipeline and RETURNS them, with H, in the requested record
+ * format: the public outputs of the plume_v2 circuit, the missing half of a V1 record, or the points plume_verify_non_zk_batch / plume_aggregate_check want given.
+ * Any of the four outputs may be NULL (it is then neither computed past what the others need nor written); at least one must not be.  For item i:
+ *   validation  exactly plume_verify_batch(version 2)'s: c, s in [1, n-1]; coordinates below p; pk and nullifier on the curve or the all-zero identity; in the
+ *               device form the message offsets.  A rejected item gets status PLUME_RECOVER_INVALID and all-zero records, and in the device form its lane never
+ *               reads msgs.  An identity pk is accepted, with the single 00 byte in the preimages, as verify does.
+ *   points      an accepted item gets the three points whatever the hash says.  s G = c pk and s H = c nullifier give identity records.
+ *   status      version 2: PLUME_RECOVER_MATCH iff c == SHA256(enc(nullifier), enc(r_point), enc(hashed_to_curve_r)) mod n, i.e. iff plume_verify_batch(2, ...) gives
+ *               ok = 1;  version 1: the six-encoding hash (G, pk, H, nullifier, r_point, hashed_to_curve_r), i.e. iff plume_verify_batch(1, ...) gives ok = 1 when
+ *               handed the recovered points.  PLUME_RECOVER_MISMATCH otherwise.
+ * Inputs are 64-byte points and 32-byte scalars as for plume_verify_batch.  Argument checks, error codes, the chunk limit, workspace waits, in-flight lanes,
+ * plume_set_sub_batches, the small-call rules and sharding over plume_init_multi are those of plume_verify_batch / plume_verify_batch_device; the measurement hooks
+ * report the call as a V2 verify whose last stage is "recover_finalize".  Output arrays of the 64-byte formats should be 16-byte aligned (hipMalloc, torch and numpy
+ * arrays are): the records are then written with 16-byte stores; any alignment is correct. */
+#define PLUME_RECOVER_MISMATCH 0   /* points computed; c is not the version's hash of them */
+#define PLUME_RECOVER_MATCH    1   /* points computed; c matches */
+#define PLUME_RECOVER_INVALID  3   /* an input is no value of the reference's types; every output record of the item is all zero */
+#define PLUME_RECOVER_FMT_AFFINE64  0   /* 64 B x||y big-endian, zeros = identity */
+#define PLUME_RECOVER_FMT_SEC1      1   /* 33 B, 02|03||x; identity = 00 + 32 zero bytes */
+#define PLUME_RECOVER_FMT_REGISTERS 2   /* 64 B = uint64_t[2][4]: x then y as four little-endian registers (circuits/circom/utils.ts pointToCircuitValue); identity = zeros */
+int plume_recover_batch(plume_ctx* ctx, int version, int format, size_t n,
+                        const uint8_t* msgs, const uint64_t* msg_off,
+                        const uint8_t* pk, const uint8_t* nullifier, const uint8_t* c, const uint8_t* s,
+                        uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* hashed_to_curve, uint8_t* status);
+int plume_recover_batch_device(plume_ctx* ctx, int version, int format, size_t n,
+                               const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes,
+                               const uint8_t* pk, const uint8_t* nullifier, const uint8_t* c, const uint8_t* s,
+                               uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* hashed_to_curve, uint8_t* status, void* stream);
 
 /* ---- persistent nullifier set: reject repeats across batches  (library 0.7) ----------------------------------
  * A consumer that verifies a STREAM of batches (a vote tally, a claim relayer, a rate limiter) must reject a nullifier it accepted any number of

@@ -137,10 +137,15 @@ def _load():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
+    # point recovery (library 0.10; Engine.recover_batch* raise PlumeHipError on an older build selected through PLUME_HIP_LIB)
+    for name, args in (("plume_recover_batch", [vp, i, i, sz] + [vp] * 10), ("plume_recover_batch_device", [vp, i, i, sz, vp, vp, sz] + [vp] * 9)):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
     _lib = lib
-    if _version(lib) < (0, 9) and not os.environ.get("PLUME_HIP_LIB"):
+    if _version(lib) < (0, 10) and not os.environ.get("PLUME_HIP_LIB"):
         _lib = None
-        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.9 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.10 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
     return lib
 
 
@@ -154,7 +159,7 @@ def exported_symbols():
             "plume_last_stage_times", "plume_microbench", "plume_microbench_last_ticks",
             "plume_nullset_create", "plume_nullset_destroy", "plume_nullset_reserve", "plume_nullset_clear", "plume_nullset_size", "plume_nullset_insert", "plume_nullset_contains",
             "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device", "plume_sign_batch_rfc6979", "plume_sign_batch_rfc6979_device",
-            "plume_set_sign_selfcheck", "plume_get_sign_selfcheck"]
+            "plume_set_sign_selfcheck", "plume_get_sign_selfcheck", "plume_recover_batch", "plume_recover_batch_device"]
 
 
 def pack_messages(msgs):
@@ -178,6 +183,10 @@ def _ptr(a):
 
 
 AGG_RESULT_BYTES = 72
+# plume_recover_batch (include/plume_hip.h): the status of an item and the record formats of the recovered points
+RECOVER_MISMATCH, RECOVER_MATCH, RECOVER_INVALID = 0, 1, 3
+RECOVER_FMT_AFFINE64, RECOVER_FMT_SEC1, RECOVER_FMT_REGISTERS = 0, 1, 2
+RECOVER_OUTPUTS = ("r_point", "hashed_to_curve_r", "hashed_to_curve")
 
 
 def parse_aggregate_record(rec):
@@ -429,6 +438,33 @@ class Engine:
                                                _ptr(r_point), _ptr(hashed_to_curve_r), _ptr(ok)), "plume_verify_batch")
         return ok
 
+    def _recover_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None or _version(self._lib) < (0, 10):
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no point recovery: {name} needs plume_hip >= 0.10 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    def recover_batch(self, version, msgs, msg_off, pk, nullifier, c, s, fmt=RECOVER_FMT_AFFINE64, want=RECOVER_OUTPUTS + ("status",)):
+        """r_point = s G - c pk, hashed_to_curve_r = s H - c nullifier and H = hash_to_curve(msg, pk) of every item (plume_recover_batch): what a V2 signature leaves out.
+        fmt: RECOVER_FMT_AFFINE64 (n x 64 bytes), RECOVER_FMT_SEC1 (n x 33) or RECOVER_FMT_REGISTERS (n x 2 x 4 uint64, the circuit's registers).  want: which of
+        r_point, hashed_to_curve_r, hashed_to_curve, status to compute.  Returns a dict of those; status[i] is RECOVER_MATCH (c is version's hash of the points),
+        RECOVER_MISMATCH (points written all the same) or RECOVER_INVALID (an input is no value of the reference's types: zero records)."""
+        fn = self._recover_fn("plume_recover_batch")
+        want = tuple(want)
+        if not want or any(k not in RECOVER_OUTPUTS + ("status",) for k in want):
+            raise ValueError("want: a non-empty subset of r_point, hashed_to_curve_r, hashed_to_curve, status")
+        n = len(msg_off) - 1
+        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
+        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        pk, nullifier, c, s = _np(pk, 64, n, "pk"), _np(nullifier, 64, n, "nullifier"), _np(c, 32, n, "c"), _np(s, 32, n, "s")
+        shape, dt = {RECOVER_FMT_AFFINE64: ((n, 64), np.uint8), RECOVER_FMT_SEC1: ((n, 33), np.uint8), RECOVER_FMT_REGISTERS: ((n, 2, 4), np.uint64)}[int(fmt)]
+        o = {k: np.zeros(shape, dtype=dt) for k in RECOVER_OUTPUTS if k in want}
+        if "status" in want:
+            o["status"] = np.zeros(n, dtype=np.uint8)
+        self._chk(fn(self._ctx, int(version), int(fmt), n, _ptr(msgs), _ptr(msg_off), _ptr(pk), _ptr(nullifier), _ptr(c), _ptr(s), _ptr(o.get("r_point")),
+                     _ptr(o.get("hashed_to_curve_r")), _ptr(o.get("hashed_to_curve")), _ptr(o.get("status"))), "plume_recover_batch")
+        return o
+
     def verify_batch_sec1(self, version, msgs, msg_off, pk33, nullifier33, c, s, r_point33=None, hashed_to_curve_r33=None):
         """verify with 33-byte SEC1-compressed points (decompressed and validated on the GPU)"""
         n = len(msg_off) - 1
@@ -577,6 +613,17 @@ class Engine:
         d = self._dp
         self._chk(self._lib.plume_verify_batch_device(self._ctx, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(c), d(s),
                                                       d(r_point), d(hashed_to_curve_r), d(ok), C.c_void_p(st)), "plume_verify_batch_device")
+
+    def recover_batch_device(self, version, n, msgs, msg_off, msgs_bytes, pk, nullifier, c, s, r_point, hashed_to_curve_r, hashed_to_curve, status,
+                             fmt=RECOVER_FMT_AFFINE64, stream=None):
+        """the device form of recover_batch on torch tensors; each of the four outputs may be None (at least one is not); enqueues on `stream` (None = current
+        stream); does not synchronise"""
+        import torch
+        fn = self._recover_fn("plume_recover_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, int(version), int(fmt), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(c), d(s), d(r_point), d(hashed_to_curve_r),
+                     d(hashed_to_curve), d(status), C.c_void_p(st)), "plume_recover_batch_device")
 
     def verify_non_zk_batch_device(self, version, n, msgs, msg_off, msgs_bytes, pk, nullifier, s, r_point, hashed_to_curve_r, digest_private, ok, stream=None):
         import torch

@@ -29,6 +29,7 @@
 #include "plume_host_logic.h"
 #include "plume_launch.h"
 #include "plume_nonce.h"
+#include "plume_recover.h"
 #include "plume_selfcheck.h"
 
 using namespace plume;
@@ -281,7 +282,7 @@ extern "C" const char* plume_last_error(void) { return g_err.c_str(); }
 #ifndef PLUME_BUILD_ID
 #define PLUME_BUILD_ID "unknown"
 #endif
-extern "C" const char* plume_version(void) { return "plume_hip 0.9 gfx950 build=" PLUME_BUILD_ID; }
+extern "C" const char* plume_version(void) { return "plume_hip 0.10 gfx950 build=" PLUME_BUILD_ID; }
 
 static void destroy_single(plume_ctx* ctx) {
     for (plume_ctx* l : ctx->lanes) destroy_single(l);
@@ -788,9 +789,19 @@ static int verify_workspace(plume_ctx* ctx, size_t n, size_t J, const std::vecto
     return 0;
 }
 
+// The point recovery (plume_recover_batch*, plume_recover.h): a V2 verify call whose last kernel writes the two recomputed points, H and a status instead of a verdict.
+// fn is k_recover_finalize's launcher, a hook that plume_recover_capi.hip hands in (plume_capi_internal.h); version is the hash the status compares c with.
+struct RecoverCall {
+    RecoverLaunch fn;
+    int version, format;
+    uint8_t *rpt, *hr, *h, *status;      // each optional
+};
+
+// rec: the call is a recovery -- version 2, PLUME_MODE_VERIFY, no r_point, no ok -- and ends in rec->fn instead of launch_verify_finalize
 static int verify_device(plume_ctx* ctx, int version, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, const uint8_t* pk, const uint8_t* nul,
                          const uint8_t* c, const uint8_t* s, const uint8_t* rpt, const uint8_t* hr, uint8_t* ok, hipStream_t st,
-                         const uint8_t* preflags = nullptr, bool continue_timer = false, const uint8_t* rpt33 = nullptr, const uint8_t* hr33 = nullptr) {
+                         const uint8_t* preflags = nullptr, bool continue_timer = false, const uint8_t* rpt33 = nullptr, const uint8_t* hr33 = nullptr,
+                         const RecoverCall* rec = nullptr) {
     if (n == 0) return 0;
     if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
     if (int rc = need_gtab(ctx)) return rc;
@@ -816,7 +827,7 @@ static int verify_device(plume_ctx* ctx, int version, int mode, size_t n, const 
         VerifyArgs a;                                                         // the slice [lo, lo + cnt) as a batch of its own: every array and every scratch region starts at the slice
         memset(&a, 0, sizeof a);
         a.version = version; a.mode = mode; a.n = (uint32_t)cnt; a.msgs = msgs; a.msg_off = msg_off + lo; a.msgs_bytes = msgs_bytes;
-        a.pk = pk + 64 * lo; a.nul = nul + 64 * lo; a.c = c + 32 * lo; a.s = s + 32 * lo; a.rpt = rpt ? rpt + 64 * lo : nullptr; a.hr = hr ? hr + 64 * lo : nullptr; a.ok = ok + lo;
+        a.pk = pk + 64 * lo; a.nul = nul + 64 * lo; a.c = c + 32 * lo; a.s = s + 32 * lo; a.rpt = rpt ? rpt + 64 * lo : nullptr; a.hr = hr ? hr + 64 * lo : nullptr; a.ok = ok ? ok + lo : nullptr;
         a.preflags = preflags ? preflags + lo : nullptr; a.rpt33 = rpt33 ? rpt33 + 33 * lo : nullptr; a.hr33 = hr33 ? hr33 + 33 * lo : nullptr;
         a.bases = ctx->bases.as<uint32_t>() + (size_t)PLUME_BASE_WORDS * J * lo; a.jobflags = ctx->jobflags.as<uint8_t>() + J * lo; a.itemflags = ctx->itemflags.as<uint8_t>() + lo;
         a.tab = ctx->tab.as<uint32_t>() + (size_t)PLUME_TAB_WORDS * J * lo; a.res = ctx->res.as<uint32_t>() + (size_t)PLUME_JAC_WORDS * 2 * lo; a.resinf = ctx->resinf.as<uint8_t>() + 2 * lo;
@@ -849,7 +860,18 @@ static int verify_device(plume_ctx* ctx, int version, int mode, size_t n, const 
         }
         launch_verify_msm(a, st); if (!overlapped) t.stage("verify_msm", st);
         if (version == 2 && mode == PLUME_MODE_VERIFY) { launch_normalize(a.res, a.resinf, 2 * cnt, st); if (!overlapped) t.stage("to_affine", st); }   // V2 hashes the computed R', Hr'
-        launch_verify_finalize(a, st); if (!overlapped) t.stage("verify_finalize", st);
+        if (rec) {
+            const size_t P = recover_width(rec->format);
+            RecoverArgs ra;
+            memset(&ra, 0, sizeof ra);
+            ra.version = rec->version; ra.format = rec->format; ra.n = a.n; ra.pk = a.pk; ra.nul = a.nul; ra.c = a.c;
+            ra.itemflags = a.itemflags; ra.jobflags = a.jobflags; ra.tab = a.tab; ra.res = a.res; ra.resinf = a.resinf;
+            ra.rpt = rec->rpt ? rec->rpt + P * lo : nullptr; ra.hr = rec->hr ? rec->hr + P * lo : nullptr; ra.h = rec->h ? rec->h + P * lo : nullptr;
+            ra.status = rec->status ? rec->status + lo : nullptr;
+            rec->fn(ra, st); if (!overlapped) t.stage("recover_finalize", st);
+        } else {
+            launch_verify_finalize(a, st); if (!overlapped) t.stage("verify_finalize", st);
+        }
     }
     if (overlapped) t.stage("verify_overlapped", st);                         // per-stage times exist in the serial mode only (plume_set_sub_batches(ctx, 1) / PLUME_SERIAL=1)
     HIPCHK(hipGetLastError());
@@ -1579,6 +1601,39 @@ static int verify_host(plume_ctx* ctx, int version, int mode, bool sec1, size_t 
         return verify_device(on, version, mode, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
                              sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(), rp, hp, sl.out[0].as<uint8_t>(), on->stream);
     });
+}
+
+// the point recovery (plume_capi_internal.h): the ABI and the launcher live in plume_recover_capi.hip
+static int recover_args_ok(int version, int format, size_t n, const void* msgs, const void* off, const void* pk, const void* nul, const void* c, const void* s, const void* rpt,
+                           const void* hr, const void* h, const void* status, RecoverLaunch fn) {
+    if (int rc = args_ok(version, n, msgs, off)) return rc;
+    if (format != PLUME_RCV_FMT_AFFINE64 && format != PLUME_RCV_FMT_SEC1 && format != PLUME_RCV_FMT_REGISTERS) return fail(PLUME_ERR_ARG, "format must be 0, 1 or 2");
+    if (!fn) return fail(PLUME_ERR_ARG, "the recovery kernel is not part of this build");
+    if (n && (!pk || !nul || !c || !s)) return fail(PLUME_ERR_ARG, "null array");
+    if (n && !rpt && !hr && !h && !status) return fail(PLUME_ERR_ARG, "no output array");
+    return 0;
+}
+int plume::capi_recover(plume_ctx* ctx, int version, int format, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, const uint8_t* nullifier,
+                        const uint8_t* c, const uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* hashed_to_curve, uint8_t* status, RecoverLaunch recover_fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = recover_args_ok(version, format, n, msgs, msg_off, pk, nullifier, c, s, r_point, hashed_to_curve_r, hashed_to_curve, status, recover_fn)) return rc;
+    const size_t P = recover_width(format);
+    const HostCall call{msgs, msg_off, {{pk, 64}, {nullifier, 64}, {c, 32}, {s, 32}}, {{r_point, P}, {hashed_to_curve_r, P}, {hashed_to_curve, P}, {status, 1}}, true, true};
+    return host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        const RecoverCall rec{recover_fn, version, format, r_point ? sl.out[0].as<uint8_t>() : nullptr, hashed_to_curve_r ? sl.out[1].as<uint8_t>() : nullptr,
+                              hashed_to_curve ? sl.out[2].as<uint8_t>() : nullptr, status ? sl.out[3].as<uint8_t>() : nullptr};
+        return verify_device(on, 2, PLUME_MODE_VERIFY, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(),
+                             sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(), nullptr, nullptr, nullptr, on->stream, nullptr, false, nullptr, nullptr, &rec);
+    });
+}
+int plume::capi_recover_device(plume_ctx* ctx, int version, int format, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, const uint8_t* pk,
+                               const uint8_t* nullifier, const uint8_t* c, const uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* hashed_to_curve,
+                               uint8_t* status, void* stream, RecoverLaunch recover_fn) {
+    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = recover_args_ok(version, format, n, msgs, msg_off, pk, nullifier, c, s, r_point, hashed_to_curve_r, hashed_to_curve, status, recover_fn)) return rc;
+    const RecoverCall rec{recover_fn, version, format, r_point, hashed_to_curve_r, hashed_to_curve, status};
+    return verify_device(ctx, 2, PLUME_MODE_VERIFY, n, msgs, msg_off, msgs_bytes, pk, nullifier, c, s, nullptr, nullptr, nullptr, st_, nullptr, false, nullptr, nullptr, &rec);
 }
 
 extern "C" int plume_verify_batch(plume_ctx* ctx, int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk,

@@ -1,4 +1,4 @@
-// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
+// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -35,5 +35,17 @@ struct ReleaseArgs;
 typedef void (*SignReleaseLaunch)(const ReleaseArgs& a, hipStream_t st);
 __attribute__((visibility("hidden"))) int capi_sign_release_hook(SignReleaseLaunch release_fn);
 __attribute__((visibility("hidden"))) int capi_set_sign_selfcheck(plume_ctx* ctx, int mode, SignReleaseLaunch release_fn);
+
+// The point recovery (plume_recover_batch*): the V2 verify pipeline with k_recover_finalize in place of k_verify_finalize.  That kernel's launcher comes in as a hook, like
+// the two above: plume_capi.hip never names it.  It is called once per sub-batch, on the caller's stream, behind the conversion of the two results to affine.
+// Arguments, routing, sharding and error codes are those of plume_verify_batch / plume_verify_batch_device.
+struct RecoverArgs;
+typedef void (*RecoverLaunch)(const RecoverArgs& a, hipStream_t st);
+__attribute__((visibility("hidden"))) int capi_recover(plume_ctx* ctx, int version, int format, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk,
+                                                       const uint8_t* nullifier, const uint8_t* c, const uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r,
+                                                       uint8_t* hashed_to_curve, uint8_t* status, RecoverLaunch recover_fn);
+__attribute__((visibility("hidden"))) int capi_recover_device(plume_ctx* ctx, int version, int format, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes,
+                                                              const uint8_t* pk, const uint8_t* nullifier, const uint8_t* c, const uint8_t* s, uint8_t* r_point,
+                                                              uint8_t* hashed_to_curve_r, uint8_t* hashed_to_curve, uint8_t* status, void* stream, RecoverLaunch recover_fn);
 
 }  // namespace plume

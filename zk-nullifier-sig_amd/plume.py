@@ -21,7 +21,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .capi import Engine, default_engine, pack_messages
+from .capi import RECOVER_INVALID, RECOVER_MATCH, Engine, default_engine, pack_messages
 
 DST = b"QUUX-V01-CS02-with-secp256k1_XMD:SHA-256_SSWU_RO_"  # rust-k256/src/lib.rs:61
 _P = 2**256 - 2**32 - 977
@@ -144,6 +144,22 @@ class PlumeSignature:  # rust-k256/src/lib.rs:67-80
         ok = eng.verify_batch(1 if v1 else 2, msgs, off, a(self.pk.to_bytes64()), a(self.nullifier.to_bytes64()), a(self.c.to_bytes()), a(self.s.to_bytes()),
                               a(v1.r_point.to_bytes64()) if v1 else None, a(v1.hashed_to_curve_r.to_bytes64()) if v1 else None)
         return bool(ok[0])
+
+    def recover_v1specific(self, engine: Optional[Engine] = None) -> PlumeSignatureV1Fields:
+        """The V1-specific fields that pk, nullifier, c, s imply -- r_point = s G - c pk, hashed_to_curve_r = s H - c nullifier, recomputed on the GPU
+        (include/plume_hip.h, plume_recover_batch) -- for a c that is the V1 hash of them: upgrades a compact four-field record to a V1 record.  Raises SignatureError
+        when an input is no value of the reference's types, and when c is NOT that hash (a V2 signature, a forgery): never a silent pair of points that do not verify."""
+        eng = engine or default_engine()
+        msgs, off = pack_messages([bytes(self.message)])
+        a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
+        o = eng.recover_batch(1, msgs, off, a(self.pk.to_bytes64()), a(self.nullifier.to_bytes64()), a(self.c.to_bytes()), a(self.s.to_bytes()),
+                              want=("r_point", "hashed_to_curve_r", "status"))
+        st = int(o["status"][0])
+        if st == RECOVER_INVALID:
+            raise SignatureError("recover_v1specific: an input is no value of the reference's types")
+        if st != RECOVER_MATCH:
+            raise SignatureError("recover_v1specific: c is not the V1 hash of the recovered points")
+        return PlumeSignatureV1Fields(AffinePoint.from_bytes64(o["r_point"][0].tobytes()), AffinePoint.from_bytes64(o["hashed_to_curve_r"][0].tobytes()))
 
     @staticmethod
     def sign_v1(secret_key: SecretKey, msg: bytes, rng, engine: Optional[Engine] = None) -> "PlumeSignature":  # lib.rs:149-151
@@ -275,6 +291,22 @@ def circuit_inputs(sig: "PlumeSignature", engine: Optional[Engine] = None) -> di
     hints = {k: [int(x) for x in v[0]] for k, v in eng.h2c_hints_batch(msgs, off, a(sig.pk.to_bytes64()), registers=True).items()}
     return {**hints, "c": reg(sig.c.to_bytes()), "s": reg(sig.s.to_bytes()), "plume_message": list(bytes(sig.message)), "pk": pt(sig.pk), "nullifier": pt(sig.nullifier),
             "q0_x_mapped": [int(x) for x in m[0]], "q0_y_mapped": [int(x) for x in m[1]], "q1_x_mapped": [int(x) for x in m[2]], "q1_y_mapped": [int(x) for x in m[3]]}
+
+
+def circuit_outputs(sig: "PlumeSignature", engine: Optional[Engine] = None) -> dict:
+    """The public outputs of the plume_v2 circuit for one signature (circuits/circom/verify_nullifier.circom:140-222; test/v2.test.ts:56-59): r_point,
+    hashed_to_curve_r and hashed_to_curve as [x, y] lists of four 64-bit little-endian registers, recomputed on the GPU from pk, nullifier, c, s
+    (plume_recover_batch, register format).  Raises SignatureError when an input is no value of the reference's types; whether c is the hash of the points is
+    the verifier's business (sig.verify), not this function's."""
+    from .capi import RECOVER_FMT_REGISTERS
+    eng = engine or default_engine()
+    msgs, off = pack_messages([bytes(sig.message)])
+    a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
+    o = eng.recover_batch(1 if sig.v1specific else 2, msgs, off, a(sig.pk.to_bytes64()), a(sig.nullifier.to_bytes64()), a(sig.c.to_bytes()), a(sig.s.to_bytes()),
+                          fmt=RECOVER_FMT_REGISTERS)
+    if int(o["status"][0]) == RECOVER_INVALID:
+        raise SignatureError("circuit_outputs: an input is no value of the reference's types")
+    return {k: [[int(x) for x in o[k][0][j]] for j in range(2)] for k in ("r_point", "hashed_to_curve_r", "hashed_to_curve")}
 
 
 def sign(rng, keypair: Tuple[AffinePoint, int], message: bytes, version: PlumeVersion, engine: Optional[Engine] = None):

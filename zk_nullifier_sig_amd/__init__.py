@@ -20,6 +20,7 @@ from .plume import (  # noqa: E402,F401
     SecretKey,
     SignatureError,
     circuit_inputs,
+    circuit_outputs,
     sign,
     sign_with_r,
     verify_non_zk,
