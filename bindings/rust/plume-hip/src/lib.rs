@@ -78,6 +78,14 @@ pub const PLUME_RECOVER_INVALID: u8 = 3;
 pub const PLUME_RECOVER_FMT_AFFINE64: c_int = 0;
 pub const PLUME_RECOVER_FMT_SEC1: c_int = 1;
 pub const PLUME_RECOVER_FMT_REGISTERS: c_int = 2;
+pub const PLUME_ETH_MISMATCH: u8 = 0;
+pub const PLUME_ETH_MATCH: u8 = 1;
+pub const PLUME_ETH_INVALID: u8 = 3;
+pub const PLUME_ETH_PK_AFFINE64: c_int = 0;
+pub const PLUME_ETH_PK_SEC1: c_int = 1;
+pub const PLUME_ETH_ADDR_RAW20: c_int = 0;
+pub const PLUME_ETH_ADDR_RECORD64: c_int = 1;
+pub const PLUME_ETH_ADDR_EIP55: c_int = 2;
 
 #[link(name = "plume_hip")]
 extern "C" {
@@ -131,6 +139,10 @@ extern "C" {
     fn plume_recover_batch_device(ctx: *mut plume_ctx, version: c_int, format: c_int, n: usize, msgs: *const u8, msg_off: *const u64, msgs_bytes: usize, pk: *const u8,
         nullifier: *const u8, c: *const u8, s: *const u8, r_point: *mut u8, hashed_to_curve_r: *mut u8, hashed_to_curve: *mut u8, status: *mut u8,
         stream: *mut c_void) -> c_int;
+    fn plume_eth_address_batch(ctx: *mut plume_ctx, pk_format: c_int, addr_format: c_int, n: usize, pk: *const u8, expect: *const u8, address: *mut u8,
+        status: *mut u8) -> c_int;
+    fn plume_eth_address_batch_device(ctx: *mut plume_ctx, pk_format: c_int, addr_format: c_int, n: usize, pk: *const u8, expect: *const u8, address: *mut u8,
+        status: *mut u8, stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -215,6 +227,37 @@ impl HipEngine {
         Ok((0..n).map(|i| if status[i] == PLUME_RECOVER_INVALID { None } else {
             Some((PlumeSignatureV1Fields { r_point: get_point(&rp[64 * i..]), hashed_to_curve_r: get_point(&hr[64 * i..]) }, get_point(&h[64 * i..]), status[i] == PLUME_RECOVER_MATCH))
         }).collect())
+    }
+
+    /// The Ethereum address of every public key, `Keccak-256(x || y)[12..32)` (`plume_eth_address_batch`): `result[i]` is `None` for a key that is no non-identity curve
+    /// point -- the identity, which `verify` accepts, has no address -- and otherwise the 20 bytes and, when `expect` is given, whether they equal `expect[i]`
+    /// (`true` without `expect`).
+    pub fn eth_address_batch(&self, pks: &[AffinePoint], expect: Option<&[[u8; 20]]>) -> Result<Vec<Option<([u8; 20], bool)>>, HipError> {
+        let n = pks.len();
+        if let Some(e) = expect { if e.len() != n { return Err(HipError("eth_address_batch: expect must hold one address per key".to_string())); } }
+        let mut pk = vec![0u8; 64 * n];
+        for (i, p) in pks.iter().enumerate() { put_point(&mut pk[64 * i..64 * i + 64], p); }
+        let want: Vec<u8> = expect.map(|e| e.concat()).unwrap_or_default();
+        let (mut addr, mut status) = (vec![0u8; 20 * n], vec![0u8; n]);
+        let rc = unsafe { plume_eth_address_batch(self.0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, n, pk.as_ptr(), if expect.is_some() { want.as_ptr() } else { std::ptr::null() },
+                                                  addr.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        Ok((0..n).map(|i| if status[i] == PLUME_ETH_INVALID { None } else {
+            let mut a = [0u8; 20];
+            a.copy_from_slice(&addr[20 * i..20 * i + 20]);
+            Some((a, status[i] == PLUME_ETH_MATCH))
+        }).collect())
+    }
+
+    /// The addresses as `"0x"` + 40 hex digits with the EIP-55 mixed-case checksum, computed on the GPU as well; `None` as in `eth_address_batch`.
+    pub fn eth_address_eip55_batch(&self, pks: &[AffinePoint]) -> Result<Vec<Option<String>>, HipError> {
+        let n = pks.len();
+        let mut pk = vec![0u8; 64 * n];
+        for (i, p) in pks.iter().enumerate() { put_point(&mut pk[64 * i..64 * i + 64], p); }
+        let (mut addr, mut status) = (vec![0u8; 42 * n], vec![0u8; n]);
+        let rc = unsafe { plume_eth_address_batch(self.0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_EIP55, n, pk.as_ptr(), std::ptr::null(), addr.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        Ok((0..n).map(|i| if status[i] == PLUME_ETH_INVALID { None } else { Some(String::from_utf8_lossy(&addr[42 * i..42 * i + 42]).into_owned()) }).collect())
     }
 
     /// Aggregate pre-filter (no reference counterpart; include/plume_hip.h `plume_aggregate_check`): `Ok(true)` iff every V1 signature of the batch would
@@ -473,6 +516,19 @@ impl NullifierSet {
 impl PlumeSignature {
     /// `PlumeSignature::verify` (rust-k256/src/lib.rs:93-145) on the GPU — a batch of one; use `HipEngine::verify_batch` for throughput.
     pub fn verify(&self, engine: &HipEngine) -> bool { engine.verify_batch(std::slice::from_ref(self)).map(|v| v[0]).unwrap_or(false) }
+    /// The 20-byte Ethereum address of `pk` (`HipEngine::eth_address_batch`); an error when `pk` is no Ethereum key (off the curve, or the identity).
+    pub fn eth_address(&self, engine: &HipEngine) -> Result<[u8; 20], HipError> {
+        engine.eth_address_batch(std::slice::from_ref(&self.pk), None)?.pop().flatten().map(|(a, _)| a).ok_or_else(|| HipError("eth_address: pk is not a non-identity curve point".to_string()))
+    }
+    /// `eth_address` as `"0x"` + 40 hex digits with the EIP-55 checksum.
+    pub fn eth_address_eip55(&self, engine: &HipEngine) -> Result<String, HipError> {
+        engine.eth_address_eip55_batch(std::slice::from_ref(&self.pk))?.pop().flatten().ok_or_else(|| HipError("eth_address_eip55: pk is not a non-identity curve point".to_string()))
+    }
+    /// `verify()` AND "`pk` is the key of `addr20`": the gate of a consumer that holds addresses, not public keys.  `false` for a `pk` that has no address.
+    pub fn verify_for_address(&self, engine: &HipEngine, addr20: &[u8; 20]) -> bool {
+        let matches = engine.eth_address_batch(std::slice::from_ref(&self.pk), Some(std::slice::from_ref(addr20))).ok().and_then(|mut v| v.pop().flatten()).map(|(_, m)| m).unwrap_or(false);
+        matches && self.verify(engine)
+    }
     /// The V1-specific fields this signature's `pk, nullifier, c, s` imply (`HipEngine::recover_batch`), for a `c` that is the V1 hash of them: upgrades a compact
     /// four-field record to a V1 record.  An error when the library rejects the inputs or `c` is not that hash -- never a silent pair of points that do not verify.
     pub fn recover_v1specific(&self, engine: &HipEngine) -> Result<PlumeSignatureV1Fields, HipError> {

@@ -274,6 +274,12 @@ struct PlumeSignature {
     // (plume_hip.h plume_recover_batch) -- for a c that is the V1 hash of them: upgrades a compact four-field record to a V1 record.  Throws SignatureError when an
     // input is no value of the reference's types and when c is NOT that hash (a V2 signature, a forgery): never a silent pair of points that do not verify.
     PlumeSignatureV1Fields recover_v1specific(Engine& eng = Engine::shared()) const;
+    // The Ethereum address of pk, Keccak-256(x || y)[12..32), computed on the GPU (plume_hip.h plume_eth_address_batch): 20 raw bytes, and "0x" + 40 hex digits with
+    // the EIP-55 mixed-case checksum.  Both throw SignatureError when pk is no Ethereum key: off the curve, a coordinate not below p, or the identity, which verify()
+    // accepts but which has no address.  verify_for_address = verify() AND "pk is the key of addr20"; false for a pk that has no address.
+    std::array<uint8_t, 20> eth_address(Engine& eng = Engine::shared()) const;
+    std::string eth_address_eip55(Engine& eng = Engine::shared()) const;
+    bool verify_for_address(const std::array<uint8_t, 20>& addr20, Engine& eng = Engine::shared()) const;
     // rust-k256/src/lib.rs:149-156
     template <class Rng> static PlumeSignature sign_v1(const SecretKey& secret_key, const Bytes& msg, Rng& rng, Engine& eng = Engine::shared());
     template <class Rng> static PlumeSignature sign_v2(const SecretKey& secret_key, const Bytes& msg, Rng& rng, Engine& eng = Engine::shared());
@@ -317,6 +323,26 @@ inline PlumeSignatureV1Fields PlumeSignature::recover_v1specific(Engine& eng) co
                                          s.to_bytes().data(), rp, hr, nullptr, &st), "plume_recover_batch");
     if (st != PLUME_RECOVER_MATCH) throw SignatureError();          // PLUME_RECOVER_INVALID, or a c that is not the V1 hash of the recovered points
     return PlumeSignatureV1Fields{AffinePoint::from_bytes64(rp), AffinePoint::from_bytes64(hr)};
+}
+inline std::array<uint8_t, 20> PlumeSignature::eth_address(Engine& eng) const {
+    std::array<uint8_t, 20> out{};
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_eth_address_batch(eng.ctx(), PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, pk.xy.data(), nullptr, out.data(), &st), "plume_eth_address_batch");
+    if (st == PLUME_ETH_INVALID) throw SignatureError();
+    return out;
+}
+inline std::string PlumeSignature::eth_address_eip55(Engine& eng) const {
+    char out[42];
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_eth_address_batch(eng.ctx(), PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_EIP55, 1, pk.xy.data(), nullptr, reinterpret_cast<uint8_t*>(out), &st),
+                     "plume_eth_address_batch");
+    if (st == PLUME_ETH_INVALID) throw SignatureError();
+    return std::string(out, 42);
+}
+inline bool PlumeSignature::verify_for_address(const std::array<uint8_t, 20>& addr20, Engine& eng) const {
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_eth_address_batch(eng.ctx(), PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, pk.xy.data(), addr20.data(), nullptr, &st), "plume_eth_address_batch");
+    return st == PLUME_ETH_MATCH && verify(eng);
 }
 
 // rust-k256/src/randomizedsigner.rs:25-41: a borrowed secret key and the variant

@@ -75,7 +75,8 @@ int plume_shard_numa_node(const plume_ctx* ctx, int shard);
 void plume_destroy(plume_ctx* ctx);
 /* Last error text of this thread (valid until the next failing call on the thread). */
 const char* plume_last_error(void);
-/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.10: point recovery (plume_recover_batch*: r_point, hashed_to_curve_r and hashed_to_curve from pk, nullifier, c, s);
+/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.11: Ethereum addresses of public keys (plume_eth_address_batch*: Keccak-256);
+ * 0.10: point recovery (plume_recover_batch*: r_point, hashed_to_curve_r and hashed_to_curve from pk, nullifier, c, s);
  * 0.9: the signer's self-check (plume_set_sign_selfcheck, PLUME_STATUS_SELFCHECK_FAILED); 0.8: derived signing nonces (plume_sign_batch_rfc6979*); 0.7: the persistent nullifier set (plume_nullset_*); 0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
  * the signer defaults to uniform level 1; the generator tables are built by the first call that needs them; stream = NULL means the stream of the context the caller
  * holds; plume_destroy waits for the context's own work only (its last call on any stream and its private streams), not for the whole device. */
@@ -463,6 +464,37 @@ int plume_recover_batch_device(plume_ctx* ctx, int version, int format, size_t n
                                const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes,
                                const uint8_t* pk, const uint8_t* nullifier, const uint8_t* c, const uint8_t* s,
                                uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* hashed_to_curve, uint8_t* status, void* stream);
+
+/* ---- Ethereum addresses of public keys (Keccak-256)  (library 0.11) ------------------------------------------
+ * The identity an application holds for an Ethereum key is its 20-byte address: allow-lists (airdrop snapshots, voter rolls, token holders) are lists of addresses and
+ * ERC-7524's wallet call names the signing key by its address.  For item i:
+ *     address = Keccak-256(x || y)[12..32)      x || y: the 64 big-endian bytes of the affine point
+ * Keccak-256 is the ORIGINAL padding (0x01 ... 0x80, rate 136), not SHA3-256.
+ *   pk        PLUME_ETH_PK_AFFINE64: 64 B x||y as everywhere else; PLUME_ETH_PK_SEC1: 33 B 02|03||x.  A key is valid when its coordinates are below p and the point is on the
+ *             curve and is NOT the identity: the all-zero record is PLUME_ETH_INVALID here, because an Ethereum key has no identity, although plume_verify_batch accepts
+ *             it as a public key.  SEC1 input is invalid when the prefix byte is not 02 / 03 (00, the verifier's identity, included), when x >= p, or when x^3 + 7 has no
+ *             square root.
+ *   expect    optional (NULL): the address each key is claimed to have, ALWAYS 20 raw bytes per item whatever addr_format is.
+ *   address   optional when expect is given: PLUME_ETH_ADDR_RAW20 20 B; PLUME_ETH_ADDR_RECORD64 64 B = 44 zero bytes, then the address -- a record plume_nullset_* and
+ *             plume_nullifier_first_occurrence take as is (an allow-list is a nullifier set of such records, the gate is plume_nullset_contains);
+ *             PLUME_ETH_ADDR_EIP55 42 ASCII bytes "0x" + 40 hex digits with the EIP-55 mixed-case checksum (a second Keccak-256 over the 40 lower-case digits; digit i is
+ *             upper-cased iff nibble i of that hash is at least 8), no terminator.
+ *   status    optional when address is given.  An invalid item has status PLUME_ETH_INVALID and an all-zero record whatever expect holds.
+ * At least one of address and status must be given.  The call needs no table and no workspace and builds none: a context that only ever computes addresses never pays for
+ * the verifier's 1 GiB window table.  The host form cuts the batch into pieces of at most plume_set_chunk items and splits it over the shards of a plume_init_multi
+ * context, as plume_scalars_to_sec1_der_batch does; the device form (a single-device context) takes any n < 2^32 - 16, enqueues one kernel on `stream` and does not
+ * synchronise.  The arrays may sit at any byte offset; a 16-byte aligned pk array of 64-byte records is read with 16-byte loads. */
+#define PLUME_ETH_MISMATCH 0   /* address computed; differs from expect[i] */
+#define PLUME_ETH_MATCH    1   /* address computed; expect is NULL or equals it */
+#define PLUME_ETH_INVALID  3   /* pk is not a non-identity curve point in the given format; the output record is all zero */
+#define PLUME_ETH_PK_AFFINE64 0   /* 64 B x||y big-endian, as everywhere else */
+#define PLUME_ETH_PK_SEC1     1   /* 33 B 02|03||x */
+#define PLUME_ETH_ADDR_RAW20    0 /* 20 B */
+#define PLUME_ETH_ADDR_RECORD64 1 /* 64 B: 44 zero bytes, then the 20 address bytes -- a record plume_nullset_* / plume_nullifier_first_occurrence take as is */
+#define PLUME_ETH_ADDR_EIP55    2 /* 42 ASCII bytes: "0x" + 40 hex digits with the EIP-55 mixed-case checksum; no terminator */
+int plume_eth_address_batch(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status);
+int plume_eth_address_batch_device(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status,
+                                   void* stream);
 
 /* ---- persistent nullifier set: reject repeats across batches  (library 0.7) ----------------------------------
  * A consumer that verifies a STREAM of batches (a vote tally, a claim relayer, a rate limiter) must reject a nullifier it accepted any number of

@@ -142,10 +142,15 @@ def _load():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
+    # Ethereum addresses (library 0.11; Engine.eth_address_batch* raise PlumeHipError on an older build selected through PLUME_HIP_LIB)
+    for name, args in (("plume_eth_address_batch", [vp, i, i, sz] + [vp] * 4), ("plume_eth_address_batch_device", [vp, i, i, sz] + [vp] * 5)):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
     _lib = lib
-    if _version(lib) < (0, 10) and not os.environ.get("PLUME_HIP_LIB"):
+    if _version(lib) < (0, 11) and not os.environ.get("PLUME_HIP_LIB"):
         _lib = None
-        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.10 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.11 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
     return lib
 
 
@@ -159,7 +164,8 @@ def exported_symbols():
             "plume_last_stage_times", "plume_microbench", "plume_microbench_last_ticks",
             "plume_nullset_create", "plume_nullset_destroy", "plume_nullset_reserve", "plume_nullset_clear", "plume_nullset_size", "plume_nullset_insert", "plume_nullset_contains",
             "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device", "plume_sign_batch_rfc6979", "plume_sign_batch_rfc6979_device",
-            "plume_set_sign_selfcheck", "plume_get_sign_selfcheck", "plume_recover_batch", "plume_recover_batch_device"]
+            "plume_set_sign_selfcheck", "plume_get_sign_selfcheck", "plume_recover_batch", "plume_recover_batch_device",
+            "plume_eth_address_batch", "plume_eth_address_batch_device"]
 
 
 def pack_messages(msgs):
@@ -187,6 +193,10 @@ AGG_RESULT_BYTES = 72
 RECOVER_MISMATCH, RECOVER_MATCH, RECOVER_INVALID = 0, 1, 3
 RECOVER_FMT_AFFINE64, RECOVER_FMT_SEC1, RECOVER_FMT_REGISTERS = 0, 1, 2
 RECOVER_OUTPUTS = ("r_point", "hashed_to_curve_r", "hashed_to_curve")
+# plume_eth_address_batch (include/plume_hip.h): the status of an item, the formats of the keys and of the address records
+ETH_MISMATCH, ETH_MATCH, ETH_INVALID = 0, 1, 3
+ETH_PK_FORMATS = {"affine64": (0, 64), "sec1": (1, 33)}                       # name -> (PLUME_ETH_PK_*, bytes per key)
+ETH_ADDR_FORMATS = {"raw20": (0, 20), "record64": (1, 64), "eip55": (2, 42)}   # name -> (PLUME_ETH_ADDR_*, bytes per record)
 
 
 def parse_aggregate_record(rec):
@@ -465,6 +475,29 @@ class Engine:
                      _ptr(o.get("hashed_to_curve_r")), _ptr(o.get("hashed_to_curve")), _ptr(o.get("status"))), "plume_recover_batch")
         return o
 
+    def _eth_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None or _version(self._lib) < (0, 11):
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no Ethereum addresses: {name} needs plume_hip >= 0.11 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    def eth_address_batch(self, pk, expect=None, pk_format="affine64", addr_format="raw20"):
+        """The Ethereum address of every public key, Keccak-256(x || y)[12:] (plume_eth_address_batch).  pk: n x 64 bytes ("affine64") or n x 33 ("sec1"); expect:
+        None or n x 20 raw bytes, the address each key is claimed to have.  Returns (address, status): address is n x 20 ("raw20"), n x 64 ("record64": 44 zero bytes
+        then the address, a record Engine.nullifier_set() takes as is) or n x 42 ASCII ("eip55": "0x" + checksummed hex); status[i] is ETH_MATCH (expect is None or
+        equals the address), ETH_MISMATCH, or ETH_INVALID (no non-identity curve point: a zero record)."""
+        fn = self._eth_fn("plume_eth_address_batch")
+        pf, P = ETH_PK_FORMATS[pk_format]
+        af, W = ETH_ADDR_FORMATS[addr_format]
+        pk = np.ascontiguousarray(pk, dtype=np.uint8)
+        if pk.size % P:
+            raise ValueError(f"pk: expected records of {P} bytes, got {pk.size} bytes")
+        n = pk.size // P
+        expect = None if expect is None else _np(expect, 20, n, "expect")
+        address, status = np.zeros((n, W), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        self._chk(fn(self._ctx, pf, af, n, _ptr(pk), _ptr(expect), _ptr(address), _ptr(status)), "plume_eth_address_batch")
+        return address, status
+
     def verify_batch_sec1(self, version, msgs, msg_off, pk33, nullifier33, c, s, r_point33=None, hashed_to_curve_r33=None):
         """verify with 33-byte SEC1-compressed points (decompressed and validated on the GPU)"""
         n = len(msg_off) - 1
@@ -624,6 +657,16 @@ class Engine:
         d = self._dp
         self._chk(fn(self._ctx, int(version), int(fmt), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(c), d(s), d(r_point), d(hashed_to_curve_r),
                      d(hashed_to_curve), d(status), C.c_void_p(st)), "plume_recover_batch_device")
+
+    def eth_address_batch_device(self, n, pk, expect, address, status, pk_format="affine64", addr_format="raw20", stream=None):
+        """the device form of eth_address_batch on torch tensors; expect may be None, and one of address and status; enqueues on `stream` (None = current stream); does
+        not synchronise"""
+        import torch
+        fn = self._eth_fn("plume_eth_address_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(pk), d(expect), d(address), d(status), C.c_void_p(st)),
+                  "plume_eth_address_batch_device")
 
     def verify_non_zk_batch_device(self, version, n, msgs, msg_off, msgs_bytes, pk, nullifier, s, r_point, hashed_to_curve_r, digest_private, ok, stream=None):
         import torch

@@ -27,6 +27,7 @@
 #include "plume_agg_launch.h"
 #include "plume_capi_internal.h"
 #include "plume_host_logic.h"
+#include "plume_keccak.h"
 #include "plume_launch.h"
 #include "plume_nonce.h"
 #include "plume_recover.h"
@@ -282,7 +283,7 @@ extern "C" const char* plume_last_error(void) { return g_err.c_str(); }
 #ifndef PLUME_BUILD_ID
 #define PLUME_BUILD_ID "unknown"
 #endif
-extern "C" const char* plume_version(void) { return "plume_hip 0.10 gfx950 build=" PLUME_BUILD_ID; }
+extern "C" const char* plume_version(void) { return "plume_hip 0.11 gfx950 build=" PLUME_BUILD_ID; }
 
 static void destroy_single(plume_ctx* ctx) {
     for (plume_ctx* l : ctx->lanes) destroy_single(l);
@@ -1799,6 +1800,67 @@ extern "C" int plume_scalars_to_sec1_der_batch(plume_ctx* ctx, size_t n, const u
     if (n == 0) return 0;
     if (ctx->shards.empty()) return der_host(ctx, n, scalars, der109, status);
     return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int { return der_host(sh, hi - lo, scalars + 32 * lo, der109 + PLUME_DER_LEN * lo, status + lo); });
+}
+// The Ethereum-address call (plume_capi_internal.h): the ABI and the launcher live in plume_eth_capi.hip.  No table is needed and no workspace is touched -- the kernel
+// reads and writes the caller's arrays only -- so the call neither builds anything nor joins the ws_free chain.
+static int eth_args_ok(int pk_format, int addr_format, size_t n, const void* pk, const void* address, const void* status, EthLaunch fn) {
+    if (pk_format != PLUME_ETHK_PK_AFFINE64 && pk_format != PLUME_ETHK_PK_SEC1) return fail(PLUME_ERR_ARG, "pk_format must be 0 or 1");
+    if (addr_format != PLUME_ETHK_ADDR_RAW20 && addr_format != PLUME_ETHK_ADDR_RECORD64 && addr_format != PLUME_ETHK_ADDR_EIP55) return fail(PLUME_ERR_ARG, "addr_format must be 0, 1 or 2");
+    if (!fn) return fail(PLUME_ERR_ARG, "the address kernel is not part of this build");
+    if (n && !pk) return fail(PLUME_ERR_ARG, "null array");
+    if (n && !address && !status) return fail(PLUME_ERR_ARG, "no output array");
+    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
+    return 0;
+}
+static int eth_device(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status, hipStream_t st,
+                      EthLaunch fn) {
+    if (n == 0) return 0;
+    EthArgs a; a.pk_format = pk_format; a.addr_format = addr_format; a.n = (uint32_t)n; a.pk = pk; a.expect = expect; a.address = address; a.status = status;
+    ctx->timer.begin(st);
+    fn(a, st); ctx->timer.stage("eth_address", st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int plume::capi_eth_address_device(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status,
+                                   void* stream, EthLaunch eth_fn) {
+    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = eth_args_ok(pk_format, addr_format, n, pk, address, status, eth_fn)) return rc;
+    return eth_device(ctx, pk_format, addr_format, n, pk, expect, address, status, st_, eth_fn);
+}
+static int eth_host(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status, EthLaunch fn) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HostSlot& sl = ctx->slot[0];
+    hipStream_t st = ctx->stream;
+    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
+    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
+        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
+        if (sl.in[0].ensure(P * cnt) || (expect && sl.in[1].ensure(20 * cnt)) || (address && sl.out[0].ensure(W * cnt)) || (status && sl.out[1].ensure(cnt))) return PLUME_ERR_HIP;
+        HIPCHK(hipMemcpyAsync(sl.in[0].p, pk + P * i0, P * cnt, hipMemcpyHostToDevice, st));
+        if (expect) HIPCHK(hipMemcpyAsync(sl.in[1].p, expect + 20 * i0, 20 * cnt, hipMemcpyHostToDevice, st));
+        int rc = eth_device(ctx, pk_format, addr_format, cnt, sl.in[0].as<uint8_t>(), expect ? sl.in[1].as<uint8_t>() : nullptr, address ? sl.out[0].as<uint8_t>() : nullptr,
+                            status ? sl.out[1].as<uint8_t>() : nullptr, st, fn);
+        hipError_t e = hipSuccess;
+        if (!rc && address) e = hipMemcpyAsync(address + W * i0, sl.out[0].p, W * cnt, hipMemcpyDeviceToHost, st);
+        if (!rc && e == hipSuccess && status) e = hipMemcpyAsync(status + i0, sl.out[1].p, cnt, hipMemcpyDeviceToHost, st);
+        const hipError_t es = hipStreamSynchronize(st);                            // on failure too: the slot's buffers are reused by the next call
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(PLUME_ERR_HIP, std::string("address download: ") + hipGetErrorString(e));
+        if (es != hipSuccess) return fail(PLUME_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
+    }
+    return 0;
+}
+int plume::capi_eth_address(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status,
+                            EthLaunch eth_fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = eth_args_ok(pk_format, addr_format, n, pk, address, status, eth_fn)) return rc;
+    if (n == 0) return 0;
+    if (ctx->shards.empty()) return eth_host(ctx, pk_format, addr_format, n, pk, expect, address, status, eth_fn);
+    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
+    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
+        return eth_host(sh, pk_format, addr_format, hi - lo, pk + P * lo, expect ? expect + 20 * lo : nullptr, address ? address + W * lo : nullptr, status ? status + lo : nullptr,
+                        eth_fn);
+    });
 }
 // The STRUCTURE half of SecretKey::from_sec1_der for the fixed 109-byte form above (what the wasm layer emits): ok[i] = 1 iff the record has that exact shape and
 // its scalar is in [1, n-1].  The embedded public key is NOT compared with scalar * G here -- the reference does compare it and returns Err on a mismatch:

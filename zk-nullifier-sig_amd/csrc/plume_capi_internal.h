@@ -1,4 +1,4 @@
-// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
+// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -47,5 +47,15 @@ __attribute__((visibility("hidden"))) int capi_recover(plume_ctx* ctx, int versi
 __attribute__((visibility("hidden"))) int capi_recover_device(plume_ctx* ctx, int version, int format, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes,
                                                               const uint8_t* pk, const uint8_t* nullifier, const uint8_t* c, const uint8_t* s, uint8_t* r_point,
                                                               uint8_t* hashed_to_curve_r, uint8_t* hashed_to_curve, uint8_t* status, void* stream, RecoverLaunch recover_fn);
+
+// The Ethereum-address call (plume_eth_address_batch*): one kernel on the caller's arrays, no tables and no workspace.  Its launcher comes in as a hook, like the three
+// above.  The host-pointer form stages chunks of at most plume_set_chunk items through the context's first slot and splits over the shards of a plume_init_multi context, as
+// plume_scalars_to_sec1_der_batch does; the device form enqueues on the caller's stream and does not synchronise.
+struct EthArgs;
+typedef void (*EthLaunch)(const EthArgs& a, hipStream_t st);
+__attribute__((visibility("hidden"))) int capi_eth_address(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect,
+                                                           uint8_t* address, uint8_t* status, EthLaunch eth_fn);
+__attribute__((visibility("hidden"))) int capi_eth_address_device(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect,
+                                                                  uint8_t* address, uint8_t* status, void* stream, EthLaunch eth_fn);
 
 }  // namespace plume

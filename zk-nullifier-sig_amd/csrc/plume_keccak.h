@@ -1,0 +1,182 @@
+// Ethereum addresses of public keys (plume_eth_address_batch, include/plume_hip.h): address = Keccak-256(x || y)[12..32) over the 64 big-endian bytes of the affine
+// point.  Keccak-256 is the ORIGINAL padding (first pad byte 0x01, last 0x80, rate 136 bytes), not SHA3-256 (0x06).  One lane per item (k_eth_address,
+// plume_eth_kernels.hip): validate the key, one permutation for the address, a second one over the 40 lower-case hex digits when the EIP-55 form is asked for, compare
+// with the expected address, WRITE the record and a status byte.
+//     status 3 (PLUME_ETH_INVALID)   pk is not a non-identity curve point in the given format: the record is all zero, whatever expect holds
+//     status 1 (PLUME_ETH_MATCH)     expect is NULL or equals the address
+//     status 0 (PLUME_ETH_MISMATCH)  the address is written all the same
+// A key is valid when its coordinates are below p, the point is on the curve and is NOT the identity: the all-zero record, which the verifier takes as the identity, has no
+// address.  SEC1 input goes through decompress_point (plume_stages.h), 64-byte input through affine_on_curve (plume_ec.h): the verifier's own checks.
+// The 25 lanes of the state are a local array that only ever sees literal indices: the 24 rounds are 24 expansions of one macro, every rotation amount and every rho/pi
+// index is written out, so the state lives in registers (a run-time index would put it in scratch).  A 64-byte message is one absorb: lanes 0-7 are the message, lane 8
+// is the 0x01 pad byte, lane 16 ends the 136-byte rate with 0x80 in its top byte.  Every value here is public: plain branches.
+// Records are written the way k_recover_finalize writes its own (recover_store, plume_recover.h): strides 20 and 42 are no multiples of 16 and the caller's array may sit
+// at any byte offset, so a record is byte stores up to the first 16-byte boundary inside it, 16-byte stores for the whole quads, byte stores for the rest.
+// Compiles as plain C++ for the host (tests/eth, tests/hostsim), like the other headers.
+#pragma once
+#include "plume_recover.h"
+
+#define PLUME_ETHK_MISMATCH 0u         // PLUME_ETH_* (include/plume_hip.h)
+#define PLUME_ETHK_MATCH 1u
+#define PLUME_ETHK_INVALID 3u
+#define PLUME_ETHK_PK_AFFINE64 0       // 64 B x || y big-endian
+#define PLUME_ETHK_PK_SEC1 1           // 33 B 02|03 || x
+#define PLUME_ETHK_ADDR_RAW20 0        // 20 B
+#define PLUME_ETHK_ADDR_RECORD64 1     // 44 zero bytes, then the 20 address bytes
+#define PLUME_ETHK_ADDR_EIP55 2        // "0x" + 40 hex digits, mixed-case checksum, no terminator
+
+namespace plume {
+
+struct EthArgs {
+    int pk_format, addr_format;       // PLUME_ETHK_PK_*, PLUME_ETHK_ADDR_*
+    uint32_t n;
+    const uint8_t* pk;                // 64 or 33 bytes per item
+    const uint8_t* expect;            // 20 bytes per item, or NULL
+    uint8_t* address;                 // eth_address_width(addr_format) bytes per item, or NULL
+    uint8_t* status;                  // 1 byte per item, or NULL
+};
+
+PLUME_HD uint32_t eth_pk_width(int pk_format) { return pk_format == PLUME_ETHK_PK_SEC1 ? 33u : 64u; }
+PLUME_HD uint32_t eth_address_width(int addr_format) { return addr_format == PLUME_ETHK_ADDR_RECORD64 ? 64u : addr_format == PLUME_ETHK_ADDR_EIP55 ? 42u : 20u; }
+
+PLUME_HD uint64_t keccak_rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
+
+// one round of Keccak-f[1600] on a[25] (lane x + 5 y), round constant rc; b, c, d are the caller's temporaries.  Literal indices only.
+#define PLUME_KECCAK_CHI(y)                                                                                                                        \
+    a[y + 0] = b[y + 0] ^ (~b[y + 1] & b[y + 2]); a[y + 1] = b[y + 1] ^ (~b[y + 2] & b[y + 3]); a[y + 2] = b[y + 2] ^ (~b[y + 3] & b[y + 4]);        \
+    a[y + 3] = b[y + 3] ^ (~b[y + 4] & b[y + 0]); a[y + 4] = b[y + 4] ^ (~b[y + 0] & b[y + 1]);
+#define PLUME_KECCAK_ROUND(rc)                                                                                                                     \
+    c[0] = a[0] ^ a[5] ^ a[10] ^ a[15] ^ a[20]; c[1] = a[1] ^ a[6] ^ a[11] ^ a[16] ^ a[21]; c[2] = a[2] ^ a[7] ^ a[12] ^ a[17] ^ a[22];              \
+    c[3] = a[3] ^ a[8] ^ a[13] ^ a[18] ^ a[23]; c[4] = a[4] ^ a[9] ^ a[14] ^ a[19] ^ a[24];                                                         \
+    d[0] = c[4] ^ keccak_rotl(c[1], 1); d[1] = c[0] ^ keccak_rotl(c[2], 1); d[2] = c[1] ^ keccak_rotl(c[3], 1);                                     \
+    d[3] = c[2] ^ keccak_rotl(c[4], 1); d[4] = c[3] ^ keccak_rotl(c[0], 1);                                                                         \
+    b[0] = a[0] ^ d[0];                          b[10] = keccak_rotl(a[1] ^ d[1], 1);    b[20] = keccak_rotl(a[2] ^ d[2], 62);                       \
+    b[5] = keccak_rotl(a[3] ^ d[3], 28);         b[15] = keccak_rotl(a[4] ^ d[4], 27);   b[16] = keccak_rotl(a[5] ^ d[0], 36);                       \
+    b[1] = keccak_rotl(a[6] ^ d[1], 44);         b[11] = keccak_rotl(a[7] ^ d[2], 6);    b[21] = keccak_rotl(a[8] ^ d[3], 55);                       \
+    b[6] = keccak_rotl(a[9] ^ d[4], 20);         b[7] = keccak_rotl(a[10] ^ d[0], 3);    b[17] = keccak_rotl(a[11] ^ d[1], 10);                      \
+    b[2] = keccak_rotl(a[12] ^ d[2], 43);        b[12] = keccak_rotl(a[13] ^ d[3], 25);  b[22] = keccak_rotl(a[14] ^ d[4], 39);                      \
+    b[23] = keccak_rotl(a[15] ^ d[0], 41);       b[8] = keccak_rotl(a[16] ^ d[1], 45);   b[18] = keccak_rotl(a[17] ^ d[2], 15);                      \
+    b[3] = keccak_rotl(a[18] ^ d[3], 21);        b[13] = keccak_rotl(a[19] ^ d[4], 8);   b[14] = keccak_rotl(a[20] ^ d[0], 18);                      \
+    b[24] = keccak_rotl(a[21] ^ d[1], 2);        b[9] = keccak_rotl(a[22] ^ d[2], 61);   b[19] = keccak_rotl(a[23] ^ d[3], 56);                      \
+    b[4] = keccak_rotl(a[24] ^ d[4], 14);                                                                                                          \
+    PLUME_KECCAK_CHI(0) PLUME_KECCAK_CHI(5) PLUME_KECCAK_CHI(10) PLUME_KECCAK_CHI(15) PLUME_KECCAK_CHI(20)                                        \
+    a[0] ^= rc;
+
+// Keccak-f[1600]
+PLUME_HD void keccak_f1600(uint64_t a[25]) {
+    uint64_t b[25], c[5], d[5];
+    PLUME_KECCAK_ROUND(0x0000000000000001ull) PLUME_KECCAK_ROUND(0x0000000000008082ull) PLUME_KECCAK_ROUND(0x800000000000808Aull) PLUME_KECCAK_ROUND(0x8000000080008000ull)
+    PLUME_KECCAK_ROUND(0x000000000000808Bull) PLUME_KECCAK_ROUND(0x0000000080000001ull) PLUME_KECCAK_ROUND(0x8000000080008081ull) PLUME_KECCAK_ROUND(0x8000000000008009ull)
+    PLUME_KECCAK_ROUND(0x000000000000008Aull) PLUME_KECCAK_ROUND(0x0000000000000088ull) PLUME_KECCAK_ROUND(0x0000000080008009ull) PLUME_KECCAK_ROUND(0x000000008000000Aull)
+    PLUME_KECCAK_ROUND(0x000000008000808Bull) PLUME_KECCAK_ROUND(0x800000000000008Bull) PLUME_KECCAK_ROUND(0x8000000000008089ull) PLUME_KECCAK_ROUND(0x8000000000008003ull)
+    PLUME_KECCAK_ROUND(0x8000000000008002ull) PLUME_KECCAK_ROUND(0x8000000000000080ull) PLUME_KECCAK_ROUND(0x000000000000800Aull) PLUME_KECCAK_ROUND(0x800000008000000Aull)
+    PLUME_KECCAK_ROUND(0x8000000080008081ull) PLUME_KECCAK_ROUND(0x8000000000008080ull) PLUME_KECCAK_ROUND(0x0000000080000001ull) PLUME_KECCAK_ROUND(0x8000000080008008ull)
+}
+#undef PLUME_KECCAK_ROUND
+#undef PLUME_KECCAK_CHI
+
+// Keccak-256 of a message of NL whole 8-byte lanes (NL <= 15: one absorb); m: the message as little-endian 32-bit words in memory order; out: the first 20 or 32 bytes
+// of the digest the same way (OW words)
+template <int NL, int OW>
+PLUME_HD void keccak256_lanes(uint32_t* out, const uint32_t* m) {
+    uint64_t a[25];
+    PLUME_UNROLL for (int k = 0; k < 25; k++) a[k] = 0;
+    PLUME_UNROLL for (int k = 0; k < NL; k++) a[k] = (uint64_t)m[2 * k] | ((uint64_t)m[2 * k + 1] << 32);
+    a[NL] = 0x01ull;                                                                     // the pad's first byte follows the message
+    a[16] ^= 0x80ull << 56;                                                              // ... its last one ends the rate: byte 135
+    keccak_f1600(a);
+    PLUME_UNROLL for (int k = 0; k < OW; k++) out[k] = (uint32_t)(a[k >> 1] >> (32 * (k & 1)));
+}
+
+// the four lower-case hex digits of two bytes (v = b0 | b1 << 8), in memory order; up: the two bytes of the checksum hash at the same place -- a LETTER is upper-cased
+// when its nibble of the hash is at least 8 (EIP-55)
+PLUME_HD uint32_t eth_hex4(uint32_t v, uint32_t up) {
+    const uint32_t x = (v & 0xFFu) | ((v & 0xFF00u) << 8), y = (up & 0xFFu) | ((up & 0xFF00u) << 8);
+    const uint32_t nib = ((x >> 4) & 0x000F000Fu) | ((x & 0x000F000Fu) << 8);             // one nibble per byte, high nibble first
+    const uint32_t hn = ((y >> 4) & 0x000F000Fu) | ((y & 0x000F000Fu) << 8);
+    const uint32_t letter = ((nib + 0x06060606u) >> 4) & 0x01010101u;                    // nibble >= 10
+    const uint32_t upper = letter & (hn >> 3);
+    return nib + 0x30303030u + letter * 39u - upper * 32u;
+}
+
+// 20 bytes at any alignment as five little-endian words
+PLUME_HD void eth_load20(uint32_t w[5], const uint8_t* p) {
+    if (((uintptr_t)p & 3u) == 0) {
+        PLUME_UNROLL for (int k = 0; k < 5; k++) w[k] = ((const uint32_t*)p)[k];
+    } else {
+        PLUME_UNROLL for (int k = 0; k < 5; k++) w[k] = (uint32_t)p[4 * k] | ((uint32_t)p[4 * k + 1] << 8) | ((uint32_t)p[4 * k + 2] << 16) | ((uint32_t)p[4 * k + 3] << 24);
+    }
+}
+
+// the key of item i as the 16 memory-order words of x || y big-endian; false: no Ethereum key
+PLUME_HD bool eth_load_pk(uint32_t q[16], const EthArgs& a, uint32_t i) {
+    if (a.pk_format == PLUME_ETHK_PK_SEC1) {
+        const uint8_t* in = a.pk + 33 * (size_t)i;
+        alignas(16) uint8_t rec[64];
+        const bool ok = decompress_point(rec, in) && in[0] != 0u;                       // (tag 00 decodes to the identity there)
+        PLUME_UNROLL for (int k = 0; k < 16; k++) q[k] = ((const uint32_t*)rec)[k];
+        return ok;
+    }
+    const uint8_t* in = a.pk + 64 * (size_t)i;
+    if (((uintptr_t)in & 15u) == 0) {
+        PLUME_UNROLL for (int k = 0; k < 4; k++) {
+            const recover_quad v = ((const recover_quad*)in)[k];
+            PLUME_UNROLL for (int j = 0; j < 4; j++) q[4 * k + j] = v.w[j];
+        }
+    } else {
+        PLUME_UNROLL for (int k = 0; k < 16; k++) q[k] = (uint32_t)in[4 * k] | ((uint32_t)in[4 * k + 1] << 8) | ((uint32_t)in[4 * k + 2] << 16) | ((uint32_t)in[4 * k + 3] << 24);
+    }
+    uint32_t wx[8], wy[8], nz = 0;
+    PLUME_UNROLL for (int k = 0; k < 8; k++) { wx[k] = bswap32(q[7 - k]); wy[k] = bswap32(q[15 - k]); nz |= wx[k] | wy[k]; }
+    if (nz == 0 || !words_lt_p(wx) || !words_lt_p(wy)) return false;
+    fe x, y;
+    fe_from_words(x, wx); fe_from_words(y, wy);
+    return affine_on_curve(x, y);
+}
+
+PLUME_HD void eth_put(const EthArgs& a, uint32_t i, const uint32_t r[16]) {
+    if (!a.address) return;
+    if (a.addr_format == PLUME_ETHK_ADDR_RECORD64) recover_store<64>(a.address + 64 * (size_t)i, r);
+    else if (a.addr_format == PLUME_ETHK_ADDR_EIP55) recover_store<42>(a.address + 42 * (size_t)i, r);
+    else recover_store<20>(a.address + 20 * (size_t)i, r);
+}
+
+// lane i of k_eth_address
+PLUME_HD void eth_address_item(const EthArgs& a, uint32_t i) {
+    uint32_t q[16], r[16];
+    PLUME_UNROLL for (int k = 0; k < 16; k++) r[k] = 0u;
+    if (!eth_load_pk(q, a, i)) {
+        eth_put(a, i, r);
+        if (a.status) a.status[i] = (uint8_t)PLUME_ETHK_INVALID;
+        return;
+    }
+    uint32_t dg[8], ad[5];
+    keccak256_lanes<8, 8>(dg, q);
+    PLUME_UNROLL for (int k = 0; k < 5; k++) ad[k] = dg[3 + k];                           // bytes 12 .. 31
+    if (a.address) {
+        if (a.addr_format == PLUME_ETHK_ADDR_EIP55) {
+            uint32_t hex[10], up[5];
+            PLUME_UNROLL for (int k = 0; k < 10; k++) hex[k] = eth_hex4(ad[k >> 1] >> (16 * (k & 1)), 0u);
+            keccak256_lanes<5, 5>(up, hex);
+            PLUME_UNROLL for (int k = 0; k < 10; k++) hex[k] = eth_hex4(ad[k >> 1] >> (16 * (k & 1)), up[k >> 1] >> (16 * (k & 1)));
+            r[0] = 0x7830u | (hex[0] << 16);                                            // "0x"
+            PLUME_UNROLL for (int k = 1; k < 10; k++) r[k] = (hex[k - 1] >> 16) | (hex[k] << 16);
+            r[10] = hex[9] >> 16;
+        } else if (a.addr_format == PLUME_ETHK_ADDR_RECORD64) {
+            PLUME_UNROLL for (int k = 0; k < 5; k++) r[11 + k] = ad[k];
+        } else {
+            PLUME_UNROLL for (int k = 0; k < 5; k++) r[k] = ad[k];
+        }
+        eth_put(a, i, r);
+    }
+    if (!a.status) return;
+    uint32_t diff = 0;
+    if (a.expect) {
+        uint32_t e[5];
+        eth_load20(e, a.expect + 20 * (size_t)i);
+        PLUME_UNROLL for (int k = 0; k < 5; k++) diff |= e[k] ^ ad[k];
+    }
+    a.status[i] = (uint8_t)(diff == 0 ? PLUME_ETHK_MATCH : PLUME_ETHK_MISMATCH);
+}
+
+}  // namespace plume

@@ -21,7 +21,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .capi import RECOVER_INVALID, RECOVER_MATCH, Engine, default_engine, pack_messages
+from .capi import ETH_INVALID, ETH_MATCH, RECOVER_INVALID, RECOVER_MATCH, Engine, default_engine, pack_messages
 
 DST = b"QUUX-V01-CS02-with-secp256k1_XMD:SHA-256_SSWU_RO_"  # rust-k256/src/lib.rs:61
 _P = 2**256 - 2**32 - 977
@@ -144,6 +144,34 @@ class PlumeSignature:  # rust-k256/src/lib.rs:67-80
         ok = eng.verify_batch(1 if v1 else 2, msgs, off, a(self.pk.to_bytes64()), a(self.nullifier.to_bytes64()), a(self.c.to_bytes()), a(self.s.to_bytes()),
                               a(v1.r_point.to_bytes64()) if v1 else None, a(v1.hashed_to_curve_r.to_bytes64()) if v1 else None)
         return bool(ok[0])
+
+    def _eth(self, engine, addr_format, expect=None):
+        eng = engine or default_engine()
+        a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
+        return eng.eth_address_batch(a(self.pk.to_bytes64()), None if expect is None else a(bytes(expect)), addr_format=addr_format)
+
+    def eth_address(self, engine: Optional[Engine] = None) -> bytes:
+        """The 20-byte Ethereum address of pk, Keccak-256(x || y)[12:], computed on the GPU (include/plume_hip.h, plume_eth_address_batch).  Raises SignatureError when pk
+        is no Ethereum key: off the curve, a coordinate not below p, or the identity, which verify() accepts but which has no address."""
+        address, status = self._eth(engine, "raw20")
+        if int(status[0]) == ETH_INVALID:
+            raise SignatureError("eth_address: pk is not a non-identity curve point")
+        return address[0].tobytes()
+
+    def eth_address_eip55(self, engine: Optional[Engine] = None) -> str:
+        """eth_address() as "0x" + 40 hex digits with the EIP-55 mixed-case checksum"""
+        address, status = self._eth(engine, "eip55")
+        if int(status[0]) == ETH_INVALID:
+            raise SignatureError("eth_address_eip55: pk is not a non-identity curve point")
+        return address[0].tobytes().decode("ascii")
+
+    def verify_for_address(self, addr20: bytes, engine: Optional[Engine] = None) -> bool:
+        """verify() AND "pk is the key of the 20-byte address addr20": the gate of a consumer that holds addresses (an allow-list, ERC-7524's signing address), not
+        public keys.  False for a pk that has no address."""
+        if len(bytes(addr20)) != 20:
+            raise ValueError("addr20: 20 raw bytes")
+        _, status = self._eth(engine, "raw20", expect=addr20)
+        return int(status[0]) == ETH_MATCH and self.verify(engine)
 
     def recover_v1specific(self, engine: Optional[Engine] = None) -> PlumeSignatureV1Fields:
         """The V1-specific fields that pk, nullifier, c, s imply -- r_point = s G - c pk, hashed_to_curve_r = s H - c nullifier, recomputed on the GPU

@@ -4,7 +4,7 @@ from pathlib import Path as _Path
 
 __path__.append(str(_Path(__file__).resolve().parent.parent / "zk-nullifier-sig_amd"))
 
-from .capi import Engine, NullifierSet, PlumeHipError, default_engine, library_path  # noqa: E402,F401
+from .capi import ETH_INVALID, ETH_MATCH, ETH_MISMATCH, Engine, NullifierSet, PlumeHipError, default_engine, library_path  # noqa: E402,F401
 from .plume import (  # noqa: E402,F401
     DST,
     AffinePoint,
