@@ -86,6 +86,10 @@ pub const PLUME_ETH_PK_SEC1: c_int = 1;
 pub const PLUME_ETH_ADDR_RAW20: c_int = 0;
 pub const PLUME_ETH_ADDR_RECORD64: c_int = 1;
 pub const PLUME_ETH_ADDR_EIP55: c_int = 2;
+pub const PLUME_ECDSA_MISMATCH: u8 = 0;
+pub const PLUME_ECDSA_MATCH: u8 = 1;
+pub const PLUME_ECDSA_INVALID: u8 = 3;
+pub const PLUME_ECDSA_LOW_S: c_int = 1;
 
 #[link(name = "plume_hip")]
 extern "C" {
@@ -143,6 +147,10 @@ extern "C" {
         status: *mut u8) -> c_int;
     fn plume_eth_address_batch_device(ctx: *mut plume_ctx, pk_format: c_int, addr_format: c_int, n: usize, pk: *const u8, expect: *const u8, address: *mut u8,
         status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_ecdsa_recover_batch(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, hash: *const u8, r: *const u8, s: *const u8, v: *const u8,
+        expect: *const u8, pk: *mut u8, address: *mut u8, status: *mut u8) -> c_int;
+    fn plume_ecdsa_recover_batch_device(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, hash: *const u8, r: *const u8, s: *const u8,
+        v: *const u8, expect: *const u8, pk: *mut u8, address: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -258,6 +266,28 @@ impl HipEngine {
         let rc = unsafe { plume_eth_address_batch(self.0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_EIP55, n, pk.as_ptr(), std::ptr::null(), addr.as_mut_ptr(), status.as_mut_ptr()) };
         if rc != 0 { return Err(last_error()); }
         Ok((0..n).map(|i| if status[i] == PLUME_ETH_INVALID { None } else { Some(String::from_utf8_lossy(&addr[42 * i..42 * i + 42]).into_owned()) }).collect())
+    }
+
+    /// The public key and the Ethereum address behind one ECDSA signature over a 32-byte digest (`plume_ecdsa_recover_batch`, Ethereum's `ecrecover`): `v` is 0, 1, 27 or
+    /// 28.  An error when the library rejects the item: `v`, `r` or `s` out of range, no curve point with x = `r`, or a key that comes out as the identity.
+    pub fn ecdsa_recover(&self, hash32: &[u8; 32], r: &[u8; 32], s: &[u8; 32], v: u8) -> Result<(AffinePoint, [u8; 20]), HipError> {
+        let (mut pk, mut addr, mut status) = ([0u8; 64], [0u8; 20], [0u8; 1]);
+        let vs = [v];
+        let rc = unsafe { plume_ecdsa_recover_batch(self.0, 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, hash32.as_ptr(), r.as_ptr(), s.as_ptr(), vs.as_ptr(), std::ptr::null(),
+                                                    pk.as_mut_ptr(), addr.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        if status[0] == PLUME_ECDSA_INVALID { return Err(HipError("ecdsa_recover: the signature recovers no public key".to_string())); }
+        Ok((get_point(&pk), addr))
+    }
+    /// `ecdsa_recover` for callers that want the 20 address bytes only.
+    pub fn ecdsa_recover_address(&self, hash32: &[u8; 32], r: &[u8; 32], s: &[u8; 32], v: u8) -> Result<[u8; 20], HipError> {
+        let (mut addr, mut status) = ([0u8; 20], [0u8; 1]);
+        let vs = [v];
+        let rc = unsafe { plume_ecdsa_recover_batch(self.0, 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, hash32.as_ptr(), r.as_ptr(), s.as_ptr(), vs.as_ptr(), std::ptr::null(),
+                                                    std::ptr::null_mut(), addr.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        if status[0] == PLUME_ECDSA_INVALID { return Err(HipError("ecdsa_recover_address: the signature recovers no public key".to_string())); }
+        Ok(addr)
     }
 
     /// Aggregate pre-filter (no reference counterpart; include/plume_hip.h `plume_aggregate_check`): `Ok(true)` iff every V1 signature of the batch would

@@ -345,6 +345,26 @@ inline bool PlumeSignature::verify_for_address(const std::array<uint8_t, 20>& ad
     return st == PLUME_ETH_MATCH && verify(eng);
 }
 
+// The public key and the 20-byte Ethereum address behind one ECDSA signature over the 32-byte digest hash32, recovered on the GPU (plume_hip.h
+// plume_ecdsa_recover_batch: Ethereum's ecrecover).  r, s: 32 big-endian bytes; v: 0, 1, 27 or 28.  Both throw SignatureError when the library rejects the item: v, r or
+// s out of range, no curve point with x = r, or a key that comes out as the identity.  ecdsa_recover_address is for callers that want the 20 bytes only.
+inline std::pair<AffinePoint, std::array<uint8_t, 20>> ecdsa_recover(const Bytes32& hash32, const Bytes32& r, const Bytes32& s, uint8_t v, Engine& eng = Engine::shared()) {
+    uint8_t pk[64], st = 0xFF;
+    std::array<uint8_t, 20> addr{};
+    plume_hip::check(plume_ecdsa_recover_batch(eng.ctx(), 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, hash32.data(), r.data(), s.data(), &v, nullptr, pk, addr.data(), &st),
+                     "plume_ecdsa_recover_batch");
+    if (st == PLUME_ECDSA_INVALID) throw SignatureError();
+    return {AffinePoint::from_bytes64(pk), addr};
+}
+inline std::array<uint8_t, 20> ecdsa_recover_address(const Bytes32& hash32, const Bytes32& r, const Bytes32& s, uint8_t v, Engine& eng = Engine::shared()) {
+    uint8_t st = 0xFF;
+    std::array<uint8_t, 20> addr{};
+    plume_hip::check(plume_ecdsa_recover_batch(eng.ctx(), 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, hash32.data(), r.data(), s.data(), &v, nullptr, nullptr, addr.data(), &st),
+                     "plume_ecdsa_recover_batch");
+    if (st == PLUME_ECDSA_INVALID) throw SignatureError();
+    return addr;
+}
+
 // rust-k256/src/randomizedsigner.rs:25-41: a borrowed secret key and the variant
 class PlumeSigner {
   public:

@@ -75,7 +75,8 @@ int plume_shard_numa_node(const plume_ctx* ctx, int shard);
 void plume_destroy(plume_ctx* ctx);
 /* Last error text of this thread (valid until the next failing call on the thread). */
 const char* plume_last_error(void);
-/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.11: Ethereum addresses of public keys (plume_eth_address_batch*: Keccak-256);
+/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.12: public keys and addresses from ECDSA signatures
+ * (plume_ecdsa_recover_batch*: ecrecover); 0.11: Ethereum addresses of public keys (plume_eth_address_batch*: Keccak-256);
  * 0.10: point recovery (plume_recover_batch*: r_point, hashed_to_curve_r and hashed_to_curve from pk, nullifier, c, s);
  * 0.9: the signer's self-check (plume_set_sign_selfcheck, PLUME_STATUS_SELFCHECK_FAILED); 0.8: derived signing nonces (plume_sign_batch_rfc6979*); 0.7: the persistent nullifier set (plume_nullset_*); 0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
  * the signer defaults to uniform level 1; the generator tables are built by the first call that needs them; stream = NULL means the stream of the context the caller
@@ -495,6 +496,40 @@ int plume_recover_batch_device(plume_ctx* ctx, int version, int format, size_t n
 int plume_eth_address_batch(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status);
 int plume_eth_address_batch_device(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status,
                                    void* stream);
+
+/* ---- public keys and addresses from ECDSA signatures (ecrecover)  (library 0.12) --------------------------------
+ * Every other call here takes a public key, and an application holds addresses: the only place the key of an Ethereum account is ever published is an ECDSA signature by
+ * that account -- a transaction, a personal_sign, the "proof of ECDSA" the reference's README pairs with a PLUME proof.  This call recovers the key, and its address, from
+ * such signatures: building the anonymity set of a list of addresses, or binding a claimed pk to an account, without leaving the GPU.  The semantics are those of Ethereum's
+ * ecrecover precompile, except that v is ONE byte and may also be 0 or 1.  For item i:
+ *   v        0, 1, 27 or 28: the parity of R's y is v & 1 for 0 / 1, v - 27 for 27 / 28.  Any other byte is invalid; EIP-155 values are the caller's to normalise.  The two
+ *            candidates with x = r + n are not produced, as in the precompile.
+ *   r, s     32 big-endian bytes each, 1 <= r < n and 1 <= s < n, else invalid.  With PLUME_ECDSA_LOW_S in flags (the EIP-2 rule for transactions) s > (n - 1) / 2 is
+ *            invalid as well.
+ *   R        the curve point with x = r and y of the given parity; no square root means invalid.
+ *   hash     any 32 bytes: z = hash mod n.
+ *   Q        r^-1 (s R - z G) = u1 G + u2 R with u1 = -z r^-1 and u2 = s r^-1 (mod n); Q = identity means invalid.
+ *   address  Keccak-256(Qx || Qy)[12..32).
+ *   expect   optional (NULL): the address each signer is claimed to have, ALWAYS 20 raw bytes per item whatever addr_format is, as for plume_eth_address_batch.
+ *   pk       optional: PLUME_ETH_PK_AFFINE64 64 B x||y, or PLUME_ETH_PK_SEC1 33 B 02|03||x.
+ *   address  optional: PLUME_ETH_ADDR_RAW20, PLUME_ETH_ADDR_RECORD64 (a record plume_nullset_* take as is) or PLUME_ETH_ADDR_EIP55, byte for byte what
+ *            plume_eth_address_batch writes for the recovered key.
+ *   status   optional: PLUME_ECDSA_MATCH -- recovered, and the address equals expect[i] or no expect was given; PLUME_ECDSA_MISMATCH -- recovered, and the address
+ *            differs: pk and address are written all the same; PLUME_ECDSA_INVALID -- every record of the item is all zero, whatever expect holds.
+ * At least one of pk, address and status must be given.  Unknown flags bits or formats return PLUME_ERR_ARG; n = 0 is a successful no-op.  Everything here is public data.
+ * The call builds the comb of G on its first use (252 MiB, shared with the signer) and never the verifier's 1 GiB window table; its workspace is the context's.  The host
+ * form cuts the batch into pieces of at most plume_set_chunk items and splits it over the shards of a plume_init_multi context; the device form (a single-device context,
+ * n at most the chunk size) enqueues on `stream`, waits for and leaves behind the workspace event like plume_verify_batch_device, honours plume_set_sub_batches and does
+ * not synchronise.  The arrays may sit at any byte offset; 16-byte aligned arrays of 64-byte records are written with 16-byte stores.  With stage timing on the stages are
+ * "ecdsa_prepare", "tables", "ecdsa_mul", "to_affine", "ecdsa_finalize". */
+#define PLUME_ECDSA_MISMATCH 0   /* key recovered; its address differs from expect[i] */
+#define PLUME_ECDSA_MATCH    1   /* key recovered; expect is NULL or equals its address */
+#define PLUME_ECDSA_INVALID  3   /* v, r or s out of range, no point with x = r, or Q is the identity; every output record is all zero */
+#define PLUME_ECDSA_LOW_S    1   /* flags bit 0: s > (n - 1) / 2 is invalid (EIP-2) */
+int plume_ecdsa_recover_batch(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s, const uint8_t* v,
+                              const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status);
+int plume_ecdsa_recover_batch_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s,
+                                     const uint8_t* v, const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, void* stream);
 
 /* ---- persistent nullifier set: reject repeats across batches  (library 0.7) ----------------------------------
  * A consumer that verifies a STREAM of batches (a vote tally, a claim relayer, a rate limiter) must reject a nullifier it accepted any number of

@@ -147,10 +147,15 @@ def _load():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
+    # ECDSA public-key recovery (library 0.12; Engine.ecdsa_recover_batch* raise PlumeHipError on an older build selected through PLUME_HIP_LIB)
+    for name, args in (("plume_ecdsa_recover_batch", [vp, i, i, i, sz] + [vp] * 8), ("plume_ecdsa_recover_batch_device", [vp, i, i, i, sz] + [vp] * 9)):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
     _lib = lib
-    if _version(lib) < (0, 11) and not os.environ.get("PLUME_HIP_LIB"):
+    if _version(lib) < (0, 12) and not os.environ.get("PLUME_HIP_LIB"):
         _lib = None
-        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.11 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.12 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
     return lib
 
 
@@ -165,7 +170,7 @@ def exported_symbols():
             "plume_nullset_create", "plume_nullset_destroy", "plume_nullset_reserve", "plume_nullset_clear", "plume_nullset_size", "plume_nullset_insert", "plume_nullset_contains",
             "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device", "plume_sign_batch_rfc6979", "plume_sign_batch_rfc6979_device",
             "plume_set_sign_selfcheck", "plume_get_sign_selfcheck", "plume_recover_batch", "plume_recover_batch_device",
-            "plume_eth_address_batch", "plume_eth_address_batch_device"]
+            "plume_eth_address_batch", "plume_eth_address_batch_device", "plume_ecdsa_recover_batch", "plume_ecdsa_recover_batch_device"]
 
 
 def pack_messages(msgs):
@@ -197,6 +202,9 @@ RECOVER_OUTPUTS = ("r_point", "hashed_to_curve_r", "hashed_to_curve")
 ETH_MISMATCH, ETH_MATCH, ETH_INVALID = 0, 1, 3
 ETH_PK_FORMATS = {"affine64": (0, 64), "sec1": (1, 33)}                       # name -> (PLUME_ETH_PK_*, bytes per key)
 ETH_ADDR_FORMATS = {"raw20": (0, 20), "record64": (1, 64), "eip55": (2, 42)}   # name -> (PLUME_ETH_ADDR_*, bytes per record)
+# plume_ecdsa_recover_batch (include/plume_hip.h): the status of an item, the flag bits; keys and addresses come in the formats above
+ECDSA_MISMATCH, ECDSA_MATCH, ECDSA_INVALID = 0, 1, 3
+ECDSA_LOW_S = 1
 
 
 def parse_aggregate_record(rec):
@@ -498,6 +506,32 @@ class Engine:
         self._chk(fn(self._ctx, pf, af, n, _ptr(pk), _ptr(expect), _ptr(address), _ptr(status)), "plume_eth_address_batch")
         return address, status
 
+    def _ecdsa_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None or _version(self._lib) < (0, 12):
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no ECDSA recovery: {name} needs plume_hip >= 0.12 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    def ecdsa_recover_batch(self, hash, r, s, v, expect=None, pk_format="affine64", addr_format="raw20", low_s=False, want=("pk", "address", "status")):
+        """The public key and the Ethereum address behind every ECDSA signature (plume_ecdsa_recover_batch): Ethereum's ecrecover with a one-byte v in {0, 1, 27, 28}.
+        hash, r, s: n x 32 big-endian bytes; v: n bytes; expect: None or n x 20 raw bytes, the address each signer is claimed to have; low_s: s > (n - 1) / 2 is invalid
+        (EIP-2).  Returns (pk, address, status) -- None for an output not named in `want`: pk is n x 64 ("affine64") or n x 33 ("sec1"), address as
+        eth_address_batch writes it for addr_format, status[i] is ECDSA_MATCH (expect is None or equals the address), ECDSA_MISMATCH (pk and address are written all the
+        same), or ECDSA_INVALID (v, r or s out of range, no point with x = r, or the key comes out as the identity: zero records)."""
+        fn = self._ecdsa_fn("plume_ecdsa_recover_batch")
+        pf, P = ETH_PK_FORMATS[pk_format]
+        af, W = ETH_ADDR_FORMATS[addr_format]
+        v = np.ascontiguousarray(v, dtype=np.uint8).reshape(-1)
+        n = v.size
+        hash, r, s = _np(hash, 32, n, "hash"), _np(r, 32, n, "r"), _np(s, 32, n, "s")
+        expect = None if expect is None else _np(expect, 20, n, "expect")
+        pk = np.zeros((n, P), dtype=np.uint8) if "pk" in want else None
+        address = np.zeros((n, W), dtype=np.uint8) if "address" in want else None
+        status = np.zeros(n, dtype=np.uint8) if "status" in want else None
+        self._chk(fn(self._ctx, ECDSA_LOW_S if low_s else 0, pf, af, n, _ptr(hash), _ptr(r), _ptr(s), _ptr(v), _ptr(expect), _ptr(pk), _ptr(address), _ptr(status)),
+                  "plume_ecdsa_recover_batch")
+        return pk, address, status
+
     def verify_batch_sec1(self, version, msgs, msg_off, pk33, nullifier33, c, s, r_point33=None, hashed_to_curve_r33=None):
         """verify with 33-byte SEC1-compressed points (decompressed and validated on the GPU)"""
         n = len(msg_off) - 1
@@ -667,6 +701,16 @@ class Engine:
         d = self._dp
         self._chk(fn(self._ctx, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(pk), d(expect), d(address), d(status), C.c_void_p(st)),
                   "plume_eth_address_batch_device")
+
+    def ecdsa_recover_batch_device(self, n, hash, r, s, v, expect, pk, address, status, pk_format="affine64", addr_format="raw20", low_s=False, stream=None):
+        """the device form of ecdsa_recover_batch on torch tensors; expect may be None, and any two of pk, address and status; enqueues on `stream` (None = current
+        stream); does not synchronise"""
+        import torch
+        fn = self._ecdsa_fn("plume_ecdsa_recover_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, ECDSA_LOW_S if low_s else 0, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(hash), d(r), d(s), d(v), d(expect),
+                     d(pk), d(address), d(status), C.c_void_p(st)), "plume_ecdsa_recover_batch_device")
 
     def verify_non_zk_batch_device(self, version, n, msgs, msg_off, msgs_bytes, pk, nullifier, s, r_point, hashed_to_curve_r, digest_private, ok, stream=None):
         import torch

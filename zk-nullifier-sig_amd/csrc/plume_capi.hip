@@ -26,6 +26,7 @@
 #include "../../include/plume_hip.h"
 #include "plume_agg_launch.h"
 #include "plume_capi_internal.h"
+#include "plume_ecdsa.h"
 #include "plume_host_logic.h"
 #include "plume_keccak.h"
 #include "plume_launch.h"
@@ -283,7 +284,7 @@ extern "C" const char* plume_last_error(void) { return g_err.c_str(); }
 #ifndef PLUME_BUILD_ID
 #define PLUME_BUILD_ID "unknown"
 #endif
-extern "C" const char* plume_version(void) { return "plume_hip 0.11 gfx950 build=" PLUME_BUILD_ID; }
+extern "C" const char* plume_version(void) { return "plume_hip 0.12 gfx950 build=" PLUME_BUILD_ID; }
 
 static void destroy_single(plume_ctx* ctx) {
     for (plume_ctx* l : ctx->lanes) destroy_single(l);
@@ -1860,6 +1861,108 @@ int plume::capi_eth_address(plume_ctx* ctx, int pk_format, int addr_format, size
     return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
         return eth_host(sh, pk_format, addr_format, hi - lo, pk + P * lo, expect ? expect + 20 * lo : nullptr, address ? address + W * lo : nullptr, status ? status + lo : nullptr,
                         eth_fn);
+    });
+}
+// The ECDSA recovery (plume_capi_internal.h): the ABI and the launchers live in plume_ecdsa_capi.hip.  The comb of G is the only fixed table (never the 1 GiB window table);
+// the workspace is the verifier's own buffers, one table job per item, so the device form joins the ws_free chain.  plume_set_sub_batches cuts the call as it cuts a verify
+// call (sub_batch_bounds); the slices follow one another on the caller's stream.
+static int ecdsa_args_ok(int flags, int pk_format, int addr_format, size_t n, const void* hash, const void* r, const void* s, const void* v, const void* pk, const void* address,
+                         const void* status, const EcdsaLaunch* fn) {
+    if (flags & ~PLUME_ECDSAK_LOW_S) return fail(PLUME_ERR_ARG, "unknown flag bits");
+    if (pk_format != PLUME_ETHK_PK_AFFINE64 && pk_format != PLUME_ETHK_PK_SEC1) return fail(PLUME_ERR_ARG, "pk_format must be 0 or 1");
+    if (addr_format != PLUME_ETHK_ADDR_RAW20 && addr_format != PLUME_ETHK_ADDR_RECORD64 && addr_format != PLUME_ETHK_ADDR_EIP55) return fail(PLUME_ERR_ARG, "addr_format must be 0, 1 or 2");
+    if (!fn || !fn->prepare || !fn->mul || !fn->finalize) return fail(PLUME_ERR_ARG, "the ECDSA recovery kernels are not part of this build");
+    if (n && (!hash || !r || !s || !v)) return fail(PLUME_ERR_ARG, "null array");
+    if (n && !pk && !address && !status) return fail(PLUME_ERR_ARG, "no output array");
+    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
+    return 0;
+}
+static int ecdsa_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s, const uint8_t* v,
+                        const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, hipStream_t st, const EcdsaLaunch* fn) {
+    if (n == 0) return 0;
+    if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
+    if (int rc = need_gcomb(ctx)) return rc;
+    if (int rc = ws_acquire(ctx, st)) return rc;
+    WsHold hold(ctx, st);
+    const std::vector<size_t> cut = sub_batch_bounds(ctx, n);
+    const size_t nsub = cut.size() - 1;
+    size_t scr_bytes = 0;
+    for (size_t k = 0; k < nsub; k++) scr_bytes = std::max(scr_bytes, table_stage_scratch(ctx, cut[k + 1] - cut[k], 0));
+    if (ctx->bases.ensure((size_t)PLUME_BASE_WORDS * 4 * n) || ctx->jobflags.ensure(n) || ctx->itemflags.ensure(n) || ctx->tab.ensure((size_t)PLUME_TAB_WORDS * 4 * n) ||
+        ctx->tabscr.ensure(scr_bytes) || ctx->res.ensure((size_t)PLUME_JAC_WORDS * 4 * n) || ctx->resinf.ensure(n) || ctx->redo.ensure((n + nsub) * 4) ||
+        ctx->digs.ensure((size_t)PLUME_NPOS * n) || ctx->eq1k.ensure(32 * n))
+        return PLUME_ERR_HIP;
+    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
+    StageTimer& t = ctx->timer;
+    t.begin(st);
+    for (size_t k = 0; k < nsub; k++) {
+        const size_t lo = cut[k], cnt = cut[k + 1] - cut[k];
+        EcdsaArgs a;                                                          // the slice [lo, lo + cnt) as a batch of its own: every array and every scratch region starts at the slice
+        memset(&a, 0, sizeof a);
+        a.flags = flags; a.pk_format = pk_format; a.addr_format = addr_format; a.n = (uint32_t)cnt;
+        a.hash = hash + 32 * lo; a.r = r + 32 * lo; a.s = s + 32 * lo; a.v = v + lo; a.expect = expect ? expect + 20 * lo : nullptr;
+        a.pk = pk ? pk + P * lo : nullptr; a.address = address ? address + W * lo : nullptr; a.status = status ? status + lo : nullptr;
+        a.bases = ctx->bases.as<uint32_t>() + (size_t)PLUME_BASE_WORDS * lo; a.jobflags = ctx->jobflags.as<uint8_t>() + lo; a.itemflags = ctx->itemflags.as<uint8_t>() + lo;
+        a.tab = ctx->tab.as<uint32_t>() + (size_t)PLUME_TAB_WORDS * lo; a.digs = ctx->digs.as<int8_t>() + (size_t)PLUME_NPOS * lo; a.u1 = ctx->eq1k.as<uint32_t>() + 8 * lo;
+        a.res = ctx->res.as<uint32_t>() + (size_t)PLUME_JAC_WORDS * lo; a.resinf = ctx->resinf.as<uint8_t>() + lo;
+        a.redo = ctx->redo.as<uint32_t>() + lo + k;                          // the slice's redo list: counter + up to cnt items
+        a.gcomb = ctx->fixed->gcomb.as<uint32_t>();
+        fn->prepare(a, st); t.stage("ecdsa_prepare", st);
+        table_stage(ctx, a.tab, a.bases, a.jobflags, cnt, 0, st); t.stage("tables", st);
+        fn->mul(a, st); t.stage("ecdsa_mul", st);
+        launch_normalize(a.res, a.resinf, cnt, st); t.stage("to_affine", st);
+        fn->finalize(a, st); t.stage("ecdsa_finalize", st);
+    }
+    HIPCHK(hipGetLastError());
+    return hold.release();
+}
+int plume::capi_ecdsa_recover_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s,
+                                     const uint8_t* v, const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, void* stream, const EcdsaLaunch* fn) {
+    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = ecdsa_args_ok(flags, pk_format, addr_format, n, hash, r, s, v, pk, address, status, fn)) return rc;
+    return ecdsa_device(ctx, flags, pk_format, addr_format, n, hash, r, s, v, expect, pk, address, status, st_, fn);
+}
+static int ecdsa_host(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s, const uint8_t* v,
+                      const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, const EcdsaLaunch* fn) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HostSlot& sl = ctx->slot[0];
+    hipStream_t st = ctx->stream;
+    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
+    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
+        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
+        if (sl.in[0].ensure(32 * cnt) || sl.in[1].ensure(32 * cnt) || sl.in[2].ensure(32 * cnt) || sl.in[3].ensure(cnt) || (expect && sl.in[4].ensure(20 * cnt)) ||
+            (pk && sl.out[0].ensure(P * cnt)) || (address && sl.out[1].ensure(W * cnt)) || (status && sl.out[2].ensure(cnt)))
+            return PLUME_ERR_HIP;
+        HIPCHK(hipMemcpyAsync(sl.in[0].p, hash + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(sl.in[1].p, r + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(sl.in[2].p, s + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(sl.in[3].p, v + i0, cnt, hipMemcpyHostToDevice, st));
+        if (expect) HIPCHK(hipMemcpyAsync(sl.in[4].p, expect + 20 * i0, 20 * cnt, hipMemcpyHostToDevice, st));
+        int rc = ecdsa_device(ctx, flags, pk_format, addr_format, cnt, sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(), sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(),
+                              expect ? sl.in[4].as<uint8_t>() : nullptr, pk ? sl.out[0].as<uint8_t>() : nullptr, address ? sl.out[1].as<uint8_t>() : nullptr,
+                              status ? sl.out[2].as<uint8_t>() : nullptr, st, fn);
+        hipError_t e = hipSuccess;
+        if (!rc && pk) e = hipMemcpyAsync(pk + P * i0, sl.out[0].p, P * cnt, hipMemcpyDeviceToHost, st);
+        if (!rc && e == hipSuccess && address) e = hipMemcpyAsync(address + W * i0, sl.out[1].p, W * cnt, hipMemcpyDeviceToHost, st);
+        if (!rc && e == hipSuccess && status) e = hipMemcpyAsync(status + i0, sl.out[2].p, cnt, hipMemcpyDeviceToHost, st);
+        const hipError_t es = hipStreamSynchronize(st);                            // on failure too: the slot's buffers are reused by the next call
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(PLUME_ERR_HIP, std::string("recovery download: ") + hipGetErrorString(e));
+        if (es != hipSuccess) return fail(PLUME_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
+    }
+    return 0;
+}
+int plume::capi_ecdsa_recover(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s, const uint8_t* v,
+                              const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, const EcdsaLaunch* fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = ecdsa_args_ok(flags, pk_format, addr_format, n, hash, r, s, v, pk, address, status, fn)) return rc;
+    if (n == 0) return 0;
+    if (ctx->shards.empty()) return ecdsa_host(ctx, flags, pk_format, addr_format, n, hash, r, s, v, expect, pk, address, status, fn);
+    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
+    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
+        return ecdsa_host(sh, flags, pk_format, addr_format, hi - lo, hash + 32 * lo, r + 32 * lo, s + 32 * lo, v + lo, expect ? expect + 20 * lo : nullptr,
+                          pk ? pk + P * lo : nullptr, address ? address + W * lo : nullptr, status ? status + lo : nullptr, fn);
     });
 }
 // The STRUCTURE half of SecretKey::from_sec1_der for the fixed 109-byte form above (what the wasm layer emits): ok[i] = 1 iff the record has that exact shape and

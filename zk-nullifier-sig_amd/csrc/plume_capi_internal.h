@@ -1,4 +1,4 @@
-// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
+// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_ecdsa_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -57,5 +57,22 @@ __attribute__((visibility("hidden"))) int capi_eth_address(plume_ctx* ctx, int p
                                                            uint8_t* address, uint8_t* status, EthLaunch eth_fn);
 __attribute__((visibility("hidden"))) int capi_eth_address_device(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect,
                                                                   uint8_t* address, uint8_t* status, void* stream, EthLaunch eth_fn);
+
+// The ECDSA recovery (plume_ecdsa_recover_batch*): prepare, the table stage, the multiplication and its redo launch, the conversion to affine, finalize.  The three launchers
+// of its own kernels come in as a hook struct, like the four above; the table stage and the conversion are plume_capi.hip's own.  The device form takes its workspace from the
+// context (it joins the ws_free chain), honours plume_set_sub_batches and does not synchronise; the host-pointer form stages chunks of at most plume_set_chunk items through
+// the context's first slot and splits over the shards of a plume_init_multi context, as plume_eth_address_batch does.
+struct EcdsaArgs;
+struct EcdsaLaunch {
+    void (*prepare)(const EcdsaArgs& a, hipStream_t st);
+    void (*mul)(const EcdsaArgs& a, hipStream_t st);
+    void (*finalize)(const EcdsaArgs& a, hipStream_t st);
+};
+__attribute__((visibility("hidden"))) int capi_ecdsa_recover(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r,
+                                                             const uint8_t* s, const uint8_t* v, const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status,
+                                                             const EcdsaLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_ecdsa_recover_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r,
+                                                                    const uint8_t* s, const uint8_t* v, const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status,
+                                                                    void* stream, const EcdsaLaunch* fn);
 
 }  // namespace plume

@@ -21,7 +21,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .capi import ETH_INVALID, ETH_MATCH, RECOVER_INVALID, RECOVER_MATCH, Engine, default_engine, pack_messages
+from .capi import ECDSA_INVALID, ETH_INVALID, ETH_MATCH, RECOVER_INVALID, RECOVER_MATCH, Engine, default_engine, pack_messages
 
 DST = b"QUUX-V01-CS02-with-secp256k1_XMD:SHA-256_SSWU_RO_"  # rust-k256/src/lib.rs:61
 _P = 2**256 - 2**32 - 977
@@ -302,6 +302,32 @@ def verify_non_zk(sig: Tuple[PlumeSignaturePublic, PlumeSignaturePrivate], pk: A
     if int(ok[0]) == 2:
         raise SignatureError("`pk` shouldn't be the identity element")
     return bool(ok[0])
+
+
+def _ecdsa_recover(what: str, want, hash32: bytes, r: bytes, s: bytes, v: int, engine: Optional[Engine]):
+    hash32, r, s = bytes(hash32), bytes(r), bytes(s)
+    if len(hash32) != 32 or len(r) != 32 or len(s) != 32:
+        raise ValueError(f"{what}: hash32, r and s are 32 big-endian bytes each")
+    if not 0 <= int(v) <= 255:
+        raise ValueError(f"{what}: v is one byte")
+    a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
+    pk, address, status = (engine or default_engine()).ecdsa_recover_batch(a(hash32), a(r), a(s), np.array([int(v)], dtype=np.uint8), want=want)
+    if int(status[0]) == ECDSA_INVALID:
+        raise SignatureError(f"{what}: the signature recovers no public key")
+    return pk, address
+
+
+def ecdsa_recover(hash32: bytes, r: bytes, s: bytes, v: int, engine: Optional[Engine] = None) -> Tuple[AffinePoint, bytes]:
+    """The public key and the 20-byte Ethereum address behind one ECDSA signature over the 32-byte digest hash32, recovered on the GPU (include/plume_hip.h,
+    plume_ecdsa_recover_batch: Ethereum's ecrecover).  r, s: 32 big-endian bytes; v: 0, 1, 27 or 28.  Raises SignatureError when the library rejects the item: v, r or s
+    out of range, no curve point with x = r, or a key that comes out as the identity."""
+    pk, address = _ecdsa_recover("ecdsa_recover", ("pk", "address", "status"), hash32, r, s, v, engine)
+    return AffinePoint.from_bytes64(pk[0].tobytes()), address[0].tobytes()
+
+
+def ecdsa_recover_address(hash32: bytes, r: bytes, s: bytes, v: int, engine: Optional[Engine] = None) -> bytes:
+    """ecdsa_recover for callers that want the 20 address bytes only"""
+    return _ecdsa_recover("ecdsa_recover_address", ("address", "status"), hash32, r, s, v, engine)[1][0].tobytes()
 
 
 def circuit_inputs(sig: "PlumeSignature", engine: Optional[Engine] = None) -> dict:
