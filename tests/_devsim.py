@@ -21,7 +21,7 @@ def lib():
         if os.environ.get("PLUME_DEVSIM_SO"):           # another build of the same harness (tests/test_devsim.py: the 5-bit-window build)
             _lib = C.CDLL(os.environ["PLUME_DEVSIM_SO"])
             return _lib
-        srcs = [_DIR / "devsim.cpp"] + list((ROOT / "zk-nullifier-sig_amd" / "csrc").glob("*.h"))
+        srcs = [_DIR / "devsim.cpp", _DIR / "lane_ops.h"] + list((ROOT / "zk-nullifier-sig_amd" / "csrc").glob("*.h"))
         if not _SO.exists() or _SO.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
             subprocess.check_call(["make", "-s", "-C", str(_DIR)])
         _lib = C.CDLL(str(_SO))
@@ -41,42 +41,110 @@ def from_limbs(a):
     return [sum(int(a[r, i]) << (32 * i) for i in range(a.shape[1])) for r in range(a.shape[0])]
 
 
-def fe_op(op, a, b=None):
-    A = to_limbs(a)
-    Bm = to_limbs(b if b is not None else [0] * len(a))
-    out = np.zeros_like(A)
-    lib().ds_fe_op(C.c_int(op), C.c_size_t(len(a)), _p(A, u32p), _p(Bm, u32p), _p(out, u32p))
-    return from_limbs(out)
-
-
-def fe_raw(op, a, b=None, c=None, e=None):
-    """products on raw 9 x 29-bit limb vectors (lists of 9 ints per element, any magnitude the contract allows) -> raw result limbs"""
-    n = len(a)
-    arrs = [np.ascontiguousarray(np.array(v if v is not None else [[0] * 9] * n, dtype=np.uint32).reshape(n, 9)) for v in (a, b, c, e)]
-    out = np.zeros((n, 9), dtype=np.uint32)
-    lib().ds_fe_raw(C.c_int(op), C.c_size_t(n), *[_p(x, u32p) for x in arrs], _p(out, u32p))
-    return [[int(w) for w in row] for row in out]
-
-
-def group_raw(op, px, py, pz, qx, qy):
-    """jac_dbl / jac_dbl_neg / jac_madd / jac_add on raw limb vectors (lists of 9 ints): the host build's limb-bound assertions abort the process on a violation"""
-    n = len(px)
-    arrs = [np.ascontiguousarray(np.array(v, dtype=np.uint32).reshape(n, 9)) for v in (px, py, pz, qx, qy)]
-    out = np.zeros((n, 27), dtype=np.uint32)
-    lib().ds_group_raw(C.c_int(op), C.c_size_t(n), *[_p(x, u32p) for x in arrs], _p(out, u32p))
-    return [[int(w) for w in row] for row in out]
-
-
-def sc_op(op, a, b=None):
-    A = to_limbs(a)
-    Bm = to_limbs(b if b is not None else [0] * len(a))
-    out = np.zeros_like(A)
-    lib().ds_sc_op(C.c_int(op), C.c_size_t(len(a)), _p(A, u32p), _p(Bm, u32p), _p(out, u32p))
-    return from_limbs(out)
-
-
 NPOS = 65          # PLUME_NPOS: positions of the Eisenstein digits of a pair of 128-bit halves
 
+
+class Lanes:
+    """The field, scalar, group-law, recoding, SHA-256 and half-GCD unit entry points of ONE build of tests/devsim/lane_ops.h: the host build (prefix ds_, this module's
+    library) or the GPU build (prefix dg_, tests/_devgpu.py).  `lib` is a callable that returns the loaded library (and may refuse to), `failed(name, rc)` is called
+    with every non-zero return value.  tests/_lane_cases.py holds the checks that take one of these as their backend."""
+
+    def __init__(self, lib, prefix, failed):
+        self._lib, self._prefix, self._failed = lib, prefix, failed
+
+    def _call(self, name, *args):
+        fn = getattr(self._lib(), self._prefix + name)
+        fn.restype = C.c_int
+        rc = fn(*args)
+        if rc != 0:
+            self._failed(self._prefix + name, rc)
+
+    def fe_op(self, op, a, b=None):
+        A = to_limbs(a)
+        Bm = to_limbs(b if b is not None else [0] * len(a))
+        out = np.zeros_like(A)
+        self._call("fe_op", C.c_int(op), C.c_size_t(len(a)), _p(A, u32p), _p(Bm, u32p), _p(out, u32p))
+        return from_limbs(out)
+
+    def fe_raw(self, op, a, b=None, c=None, e=None):
+        """products on raw 9 x 29-bit limb vectors (lists of 9 ints per element, any magnitude the contract allows) -> raw result limbs; fe_sqr_d / fe_sqr2_d (ops 8, 9)
+        return 18: the result, then the doubled operand"""
+        n = len(a)
+        arrs = [np.ascontiguousarray(np.array(v if v is not None else [[0] * 9] * n, dtype=np.uint32).reshape(n, 9)) for v in (a, b, c, e)]
+        out = np.zeros((n, 18), dtype=np.uint32)
+        self._call("fe_raw", C.c_int(op), C.c_size_t(n), *[_p(x, u32p) for x in arrs], _p(out, u32p))
+        w = 18 if op in (8, 9) else 9
+        assert w == 18 or not out[:, 9:].any()
+        return [[int(x) for x in row[:w]] for row in out]
+
+    def group_raw(self, op, px, py, pz, qx, qy):
+        """jac_dbl / jac_dbl_neg / jac_madd / jac_add on raw limb vectors (lists of 9 ints): the host build's limb-bound assertions abort the process on a violation"""
+        n = len(px)
+        arrs = [np.ascontiguousarray(np.array(v, dtype=np.uint32).reshape(n, 9)) for v in (px, py, pz, qx, qy)]
+        out = np.zeros((n, 27), dtype=np.uint32)
+        self._call("group_raw", C.c_int(op), C.c_size_t(n), *[_p(x, u32p) for x in arrs], _p(out, u32p))
+        return [[int(w) for w in row] for row in out]
+
+    def sc_op(self, op, a, b=None):
+        A = to_limbs(a)
+        Bm = to_limbs(b if b is not None else [0] * len(a))
+        out = np.zeros_like(A)
+        self._call("sc_op", C.c_int(op), C.c_size_t(len(a)), _p(A, u32p), _p(Bm, u32p), _p(out, u32p))
+        return from_limbs(out)
+
+    def glv(self, ks):
+        """k -> (|k1|, sign, |k2|, sign, the 65 digit codes of k1 + k2 w)"""
+        K = to_limbs(ks)
+        out = np.zeros((len(ks), 10), dtype=np.uint32)
+        dig = np.zeros((len(ks), NPOS), dtype=np.int8)
+        self._call("glv", C.c_size_t(len(ks)), _p(K, u32p), _p(out, u32p), dig.ctypes.data_as(C.POINTER(C.c_int8)))
+        res = []
+        for r in range(len(ks)):
+            m1 = sum(int(out[r, i]) << (32 * i) for i in range(4))
+            m2 = sum(int(out[r, 5 + i]) << (32 * i) for i in range(4))
+            res.append((m1, int(out[r, 4]), m2, int(out[r, 9]), dig[r].tolist()))
+        return res
+
+    def sha256(self, data: bytes):
+        out = (C.c_uint8 * 32)()
+        buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
+        self._call("sha256", buf, C.c_uint32(len(data)), out)
+        return bytes(out)
+
+    def eisd_entries(self):
+        """the digit table of eisd_store in its two forms for every t = (ta, tb) in [-4, 4]^2, ta-major: [(eisd_entry_table, eisd_entry)] x 81"""
+        out = np.zeros(162, dtype=np.uint32)
+        self._call("eisd_entries", _p(out, u32p))
+        return [(int(out[2 * k]), int(out[2 * k + 1])) for k in range(81)]
+
+    def eis_half_gcd(self, cs):
+        """the half-GCD in Z[w] for a list of challenges (ints mod n): [(t0 - 1, t1, u0, u1, tau mod n, ok)]"""
+        m = len(cs)
+        cb = np.frombuffer(b"".join(int(c).to_bytes(32, "big") for c in cs), dtype=np.uint8).copy()
+        out, tau, ok = np.zeros(64 * m, np.uint8), np.zeros(32 * m, np.uint8), np.zeros(m, np.uint8)
+        self._call("eis_half_gcd", C.c_uint32(m), _p(cb), _p(out), _p(tau), _p(ok))
+        res = []
+        for i in range(m):
+            v = [int.from_bytes(out[64 * i + 16 * k:64 * i + 16 * k + 16].tobytes(), "little", signed=True) for k in range(4)]
+            res.append((v[0], v[1], v[2], v[3], int.from_bytes(tau[32 * i:32 * i + 32].tobytes(), "big"), bool(ok[i])))
+        return res
+
+    def eis_consistent(self, cs, which=0):
+        """eis_consistent on the half-GCD's pair of each challenge, after tamper `which` (0 = none; tests/devsim/lane_ops.h eis_consistent_lane)"""
+        m = len(cs)
+        cb = np.frombuffer(b"".join(int(c).to_bytes(32, "big") for c in cs), dtype=np.uint8).copy()
+        out = np.zeros(m, np.uint8)
+        self._call("eis_consistent", C.c_uint32(m), _p(cb), C.c_int(which), _p(out))
+        return out.astype(bool)
+
+
+def _host_failed(name, rc):
+    raise AssertionError(f"{name} returned {rc}")
+
+
+HOST = Lanes(lib, "ds_", _host_failed)
+fe_op, fe_raw, group_raw, sc_op, glv, sha256 = HOST.fe_op, HOST.fe_raw, HOST.group_raw, HOST.sc_op, HOST.glv, HOST.sha256
+eisd_entries, eis_half_gcd, eis_consistent = HOST.eisd_entries, HOST.eis_half_gcd, HOST.eis_consistent
 
 def eis_digit(code):
     """digit code of csrc/plume_ec.h -> the Eisenstein integer (a, b) = a + b w it stands for: 0 -> 0; 1 + 6 row + 2 j + neg -> (-1)^neg w^j (1 | theta = 1 - w | 2)"""
@@ -90,31 +158,10 @@ def eis_digit(code):
     return (-a, -b) if neg else (a, b)
 
 
-def glv(ks):
-    """k -> (|k1|, sign, |k2|, sign, the 65 digit codes of k1 + k2 w)"""
-    K = to_limbs(ks)
-    out = np.zeros((len(ks), 10), dtype=np.uint32)
-    dig = np.zeros((len(ks), NPOS), dtype=np.int8)
-    lib().ds_glv(C.c_size_t(len(ks)), _p(K, u32p), _p(out, u32p), dig.ctypes.data_as(C.POINTER(C.c_int8)))
-    res = []
-    for r in range(len(ks)):
-        m1 = sum(int(out[r, i]) << (32 * i) for i in range(4))
-        m2 = sum(int(out[r, 5 + i]) << (32 * i) for i in range(4))
-        res.append((m1, int(out[r, 4]), m2, int(out[r, 9]), dig[r].tolist()))
-    return res
-
-
 def wbits():
     """window width of the build under test (PLUME_WBITS)"""
     lib().ds_wbits.restype = C.c_uint32
     return int(lib().ds_wbits())
-
-
-def sha256(data: bytes):
-    out = (C.c_uint8 * 32)()
-    buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
-    lib().ds_sha256(buf, C.c_uint32(len(data)), out)
-    return bytes(out)
 
 
 def _aligned(a):
@@ -259,28 +306,6 @@ def set_eq1_short(v):
     """the verifier's first equation where R is given: 1 = short form (plume_eis.h, the default), 0 = long form always, 2 = every item takes the scalar stage's fallback
     (filed as long form, run by the checked chain of the redo launch)"""
     lib().ds_set_eq1_short(C.c_int(int(v)))
-
-
-def eis_half_gcd(cs):
-    """the half-GCD in Z[w] for a list of challenges (ints mod n): [(t0 - 1, t1, u0, u1, tau mod n, ok)]"""
-    m = len(cs)
-    cb = np.frombuffer(b"".join(int(c).to_bytes(32, "big") for c in cs), dtype=np.uint8).copy()
-    out, tau, ok = np.zeros(64 * m, np.uint8), np.zeros(32 * m, np.uint8), np.zeros(m, np.uint8)
-    lib().ds_eis_half_gcd(C.c_uint32(m), _p(cb), _p(out), _p(tau), _p(ok))
-    res = []
-    for i in range(m):
-        v = [int.from_bytes(out[64 * i + 16 * k:64 * i + 16 * k + 16].tobytes(), "little", signed=True) for k in range(4)]
-        res.append((v[0], v[1], v[2], v[3], int.from_bytes(tau[32 * i:32 * i + 32].tobytes(), "big"), bool(ok[i])))
-    return res
-
-
-def eis_consistent(cs, which=0):
-    """eis_consistent on the half-GCD's pair of each challenge, after tamper `which` (0 = none; tests/devsim/devsim.cpp ds_eis_consistent)"""
-    m = len(cs)
-    cb = np.frombuffer(b"".join(int(c).to_bytes(32, "big") for c in cs), dtype=np.uint8).copy()
-    out = np.zeros(m, np.uint8)
-    lib().ds_eis_consistent(C.c_uint32(m), _p(cb), C.c_int(which), _p(out))
-    return out.astype(bool)
 
 
 def eq1_short(s: bytes, c: bytes, pk: bytes, r: bytes):

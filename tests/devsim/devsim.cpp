@@ -12,10 +12,11 @@
 #include "plume_stages.h"
 #include "plume_aggregate.h"
 #include "plume_dedup.h"
+#include "lane_ops.h"
 
 using namespace plume;
+namespace L = plume_lanes;
 
-static void fe_from_le_words(fe& r, const uint32_t* w) { fe_from_words(r, w); }   // any 256-bit integer, also >= p
 static int g_sign_uniform = 0;        // the signer's (and the DER export's) uniform-schedule bodies (plume_set_sign_uniform) instead of the default ones
 
 extern "C" {
@@ -24,114 +25,32 @@ void ds_set_sign_uniform(int on) { g_sign_uniform = on; }
 // how many multi-scalar chains were redone with checked additions since the library was loaded (p == +-q inside a chain)
 unsigned long ds_fallback_count(void) { return fallback_counter(); }
 
-// op: 0 mul, 1 sqr, 2 add, 3 sub, 4 neg, 5 inv, 6 pow_c1, 7 normalize, 8 mul_small(b[0]), 9 is_zero->out[0], 10 eq->out[0], 11 is_odd->out[0],
-//     12 (a+b)*(a+2p-b) on unreduced operands, 13 (a+4p-2b)^2 through fe_carry, 14 words round trip, 15 inversion by divsteps,
-//     16..20 the fused multiply-subtract forms of the group law (round 3): xy - x, x^2 - (2y + x), x^2 - 2y, x(y - x) - 2y^2, (x - y)(x + y) - y
-// operands/outputs: 256-bit integers as 8 little-endian 32-bit words (outputs canonical); count elements
-void ds_fe_op(int op, size_t count, const uint32_t* a, const uint32_t* b, uint32_t* out) {
-    for (size_t i = 0; i < count; i++) {
-        fe x, y, r = fe_zero();
-        bool flag = false;
-        fe_from_le_words(x, a + 8 * i);
-        fe_from_le_words(y, b + 8 * i);
-        switch (op) {
-            case 0: fe_mul(r, x, y); break;
-            case 1: fe_sqr(r, x); break;
-            case 2: fe_add(r, x, y); break;
-            case 3: fe_sub(r, x, y); break;
-            case 4: fe_neg(r, x); break;
-            case 5: fe_inv_fermat(r, x); break;
-            case 6: fe_pow_c1(r, x); break;
-            case 7: r = x; fe_normalize(r); break;
-            case 8: fe_mul_small(r, x, b[8 * i]); break;
-            case 9: flag = fe_is_zero(x); break;
-            case 10: flag = fe_eq(x, y); break;
-            case 11: flag = fe_is_odd(x); break;
-            case 12: { fe s, d; fe_add_lazy(s, x, y); fe_sub_lazy<2>(d, x, y); fe_mul(r, d, s); break; }          // (a+b)(a-b), both operands unreduced
-            case 13: { fe t; fe_add_lazy(t, y, y); fe_sub_lazy<4>(t, x, t); fe_carry(t); fe_sqr(r, t); break; }  // (a-2b)^2
-            case 14: r = x; break;
-            case 15: fe_inv_gcd(r, x); break;
-            case 16: fe_mul_sub<2>(r, x, y, x); break;                                                               // xy - x
-            case 17: { fe hh; fe_dbl_lazy(hh, y); fe_add_lazy(hh, hh, x); fe_sqr_sub<4>(r, x, hh); break; }           // x^2 - (2y + x): the mixed addition's X3
-            case 18: fe_sqr_sub2<2>(r, x, y); break;                                                                 // x^2 - 2y: the doubling's X'
-            case 19: { fe t, nb, db; fe_sub_lazy<2>(t, y, x); fe_neg_lazy(nb, y); fe_dbl_lazy(db, y); fe_muladd(r, x, t, nb, db); break; }   // x(y - x) - 2y^2: the doubling's Y' at its operand bounds
-            case 20: { fe d, sm; fe_add_lazy(sm, x, y); fe_sub_lazy<2>(d, x, y); fe_mul_sub<2>(r, d, sm, y); break; }  // (x - y)(x + y) - y, unreduced factors
-        }
-        if (op >= 9 && op <= 11) { for (int k = 0; k < 8; k++) out[8 * i + k] = k == 0 ? (uint32_t)flag : 0u; continue; }
-        fe_normalize(r);
-        fe_to_words(out + 8 * i, r);
-    }
+// The field, scalar, group-law, recoding, SHA-256 and half-GCD unit entry points: the per-element bodies live in lane_ops.h (shared with the GPU build of the same
+// bodies, tests/devgpu/devgpu.hip), here one after another on the host.  Each returns 0, or -1 for an op it does not know.
+int ds_fe_op(int op, size_t count, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+    return L::dispatch<L::kFeOps>(op, [&](auto OP) { for (size_t i = 0; i < count; i++) L::fe_op<decltype(OP)::value>(a + 8 * i, b + 8 * i, out + 8 * i); }) ? 0 : -1;
 }
-// The products on RAW limbs (9 words per operand, NOT canonical: whatever magnitudes the caller's contract allows) -> raw result limbs, so that a test can drive the
-// column sums to their bounds and look at the tightness of what comes back.  op: 0 fe_mul(a, b), 1 fe_sqr(a), 2 fe_muladd(a, b, c, e), 3 fe_mul_sub<2>(a, b, c), 4 fe_sqr_sub<4>(a, c),
-// 5 fe_sqr_sub2<2>(a, c), 6 fe_sqr3(a), 7 fe_sqr2(a)
-void ds_fe_raw(int op, size_t count, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* e, uint32_t* out) {
-    for (size_t i = 0; i < count; i++) {
-        fe x, y, z, w, r = fe_zero();
-        for (int k = 0; k < 9; k++) { x.v[k] = a[9 * i + k]; y.v[k] = b[9 * i + k]; z.v[k] = c[9 * i + k]; w.v[k] = e[9 * i + k]; }
-        switch (op) {
-            case 0: fe_mul(r, x, y); break;
-            case 1: fe_sqr(r, x); break;
-            case 2: fe_muladd(r, x, y, z, w); break;
-            case 3: fe_mul_sub<2>(r, x, y, z); break;
-            case 4: fe_sqr_sub<4>(r, x, z); break;
-            case 5: fe_sqr_sub2<2>(r, x, z); break;
-            case 6: fe_sqr3(r, x); break;
-            case 7: fe_sqr2(r, x); break;
-        }
-        for (int k = 0; k < 9; k++) out[9 * i + k] = r.v[k];
-    }
+// out: 18 words per element (the result, then the second output of fe_sqr_d / fe_sqr2_d)
+int ds_fe_raw(int op, size_t count, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* e, uint32_t* out) {
+    return L::dispatch<L::kFeRawOps>(op, [&](auto OP) {
+        for (size_t i = 0; i < count; i++) L::fe_raw<decltype(OP)::value>(a + 9 * i, b + 9 * i, c + 9 * i, e + 9 * i, out + L::kFeRawOutWords * i);
+    }) ? 0 : -1;
 }
-// The group law on RAW limbs: every lazy sum / difference that feeds a product inside jac_dbl / jac_dbl_neg / jac_madd / jac_add, driven by operands whose limbs
-// sit at the ends of the "tight" range -- the host build's PLUME_FE_CHECK assertions (fe_mul_inputs_ok: limbs 0..7 by the column bound, limb 8 <= 2^26) abort on a violation.
-// op: 0 jac_dbl, 1 jac_dbl_neg, 2 jac_madd<false>, 3 jac_madd<true>, 4 the same with the row's y negated lazily (what a negative digit does), 5 jac_add (q = (qx, qy, p.z)).
-// p = (x, y, z) and the affine (qx, qy): 9 words each; out: the resulting x, y, z (27 words).
-void ds_group_raw(int op, size_t count, const uint32_t* px, const uint32_t* py, const uint32_t* pz, const uint32_t* qx, const uint32_t* qy, uint32_t* out) {
-    for (size_t i = 0; i < count; i++) {
-        jac p; p.inf = 0;
-        fe ax, ay;
-        for (int k = 0; k < 9; k++) { p.x.v[k] = px[9 * i + k]; p.y.v[k] = py[9 * i + k]; p.z.v[k] = pz[9 * i + k]; ax.v[k] = qx[9 * i + k]; ay.v[k] = qy[9 * i + k]; }
-        switch (op) {
-            case 0: jac_dbl(p); break;
-            case 1: jac_dbl_neg(p); break;
-            case 2: jac_madd<false>(p, ax, ay); break;
-            case 3: jac_madd<true>(p, ax, ay); break;
-            case 4: { fe ny; fe_neg_lazy(ny, ay); jac_madd<false>(p, ax, ny); break; }
-            case 5: { jac q; q.inf = 0; q.x = ax; q.y = ay; q.z = p.z; jac_add(p, q); break; }
-        }
-        for (int k = 0; k < 9; k++) { out[27 * i + k] = p.x.v[k]; out[27 * i + 9 + k] = p.y.v[k]; out[27 * i + 18 + k] = p.z.v[k]; }
-    }
+int ds_group_raw(int op, size_t count, const uint32_t* px, const uint32_t* py, const uint32_t* pz, const uint32_t* qx, const uint32_t* qy, uint32_t* out) {
+    return L::dispatch<L::kGroupRawOps>(op, [&](auto OP) {
+        for (size_t i = 0; i < count; i++) L::group_raw<decltype(OP)::value>(px + 9 * i, py + 9 * i, pz + 9 * i, qx + 9 * i, qy + 9 * i, out + 27 * i);
+    }) ? 0 : -1;
 }
-// op: 0 mul, 1 add, 2 neg, 3 reduce of 512-bit a|b (a low)
-void ds_sc_op(int op, size_t count, const uint32_t* a, const uint32_t* b, uint32_t* out) {
-    for (size_t i = 0; i < count; i++) {
-        sc x, y, r;
-        for (int k = 0; k < 8; k++) { x.v[k] = a[8 * i + k]; y.v[k] = b[8 * i + k]; r.v[k] = 0; }
-        if (op == 0) sc_mul(r, x, y);
-        else if (op == 1) sc_add(r, x, y);
-        else if (op == 2) sc_neg(r, x);
-        else { uint32_t t[16]; for (int k = 0; k < 8; k++) { t[k] = x.v[k]; t[8 + k] = y.v[k]; } sc_reduce_wide(r, t); }
-        for (int k = 0; k < 8; k++) out[8 * i + k] = r.v[k];
-    }
+int ds_sc_op(int op, size_t count, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+    return L::dispatch<L::kScOps>(op, [&](auto OP) { for (size_t i = 0; i < count; i++) L::sc_op<decltype(OP)::value>(a + 8 * i, b + 8 * i, out + 8 * i); }) ? 0 : -1;
 }
 uint32_t ds_wbits() { return PLUME_WBITS; }                  // width of the grid the generator's wide digits sit on (4)
 // k (8 limbs) -> m1[4], neg1, m2[4], neg2 (10 words) and the PLUME_NPOS Eisenstein digit codes of the pair (int8, rows of 65)
-void ds_glv(size_t count, const uint32_t* k, uint32_t* out, int8_t* digits) {
-    for (size_t i = 0; i < count; i++) {
-        sc x; for (int j = 0; j < 8; j++) x.v[j] = k[8 * i + j];
-        glv_half h1, h2;
-        glv_split(h1, h2, x);
-        for (int j = 0; j < 4; j++) { out[10 * i + j] = h1.m[j]; out[10 * i + 5 + j] = h2.m[j]; }
-        out[10 * i + 4] = h1.neg; out[10 * i + 9] = h2.neg;
-        eisd_store_glv(digits + PLUME_NPOS * i, 1, h1, h2, false);
-    }
+int ds_glv(size_t count, const uint32_t* k, uint32_t* out, int8_t* digits) {
+    for (size_t i = 0; i < count; i++) L::glv(k + 8 * i, out + 10 * i, digits + PLUME_NPOS * i);
+    return 0;
 }
-void ds_sha256(const uint8_t* data, uint32_t len, uint8_t out[32]) {
-    uint32_t st[8];
-    sha256_init(st);
-    sha256_absorb_pad(st, 0u, len, [&](uint32_t pos) -> uint32_t { return data[pos]; });
-    for (int i = 0; i < 8; i++) { out[4 * i] = st[i] >> 24; out[4 * i + 1] = st[i] >> 16; out[4 * i + 2] = st[i] >> 8; out[4 * i + 3] = st[i]; }
-}
+int ds_sha256(const uint8_t* data, uint32_t len, uint8_t out[32]) { L::sha256(data, len, out); return 0; }
 
 // the generator's fixed tables exactly as the library builds them at plume_init (plume_ec.h fixed_window_base / fixed_table_lane: one entry per "lane")
 static void build_gtab(std::vector<uint32_t>& gtab) {
@@ -219,9 +138,9 @@ void ds_tables_raw(uint32_t nb, const uint8_t* pts, uint8_t* out) {
         }
 }
 // the digit table of eisd_store in its two forms (the 64-entry table, the register-resident packing the kernels run) for every t = (ta, tb) in [-4, 4]^2: 81 x 2 words
-void ds_eisd_entries(uint32_t* out) {
-    int k = 0;
-    for (int ta = -4; ta <= 4; ta++) for (int tb = -4; tb <= 4; tb++) { out[k++] = eisd_entry_table(ta, tb); out[k++] = eisd_entry(ta, tb); }
+int ds_eisd_entries(uint32_t* out) {
+    for (uint32_t idx = 0; idx < 81; idx++) L::eisd_entries_lane(idx, out + 2 * idx);
+    return 0;
 }
 uint32_t ds_tab_entries() { return PLUME_TAB_ENTRIES; }     // rows per window table (3: P, theta P = P - lambda P, 2P)
 
@@ -507,47 +426,13 @@ int ds_eq1(const uint8_t s_be[32], const uint8_t c_be[32], const uint8_t pk_be[6
 // the half-GCD in Z[w] (plume_eis.h) for n challenges c (32-byte big-endian, canonical): out[i] = t0 - 1, t1, u0, u1 as signed 128-bit little-endian integers (4 x 16 bytes),
 // tau[i] = t0 + t1 lambda mod n (32 bytes BE), okf[i] = the bound flag
 int ds_eis_half_gcd(uint32_t n, const uint8_t* c_be, uint8_t* out, uint8_t* tau_be, uint8_t* okf) {
-    for (uint32_t i = 0; i < n; i++) {
-        alignas(16) uint8_t cb[32], tb[32];
-        memcpy(cb, c_be + 32 * (size_t)i, 32);
-        sc c; sc_from_be_aligned(c, cb);
-        eis_short e;
-        glv_half g0, g1;
-        glv_split(g0, g1, c);
-        eis_half_gcd(e, g0, g1);
-        const uint32_t (*mags[4])[3] = {&e.t[0], &e.t[1], &e.u[0], &e.u[1]};
-        const uint32_t negs[4] = {e.tneg[0], e.tneg[1], e.uneg[0], e.uneg[1]};
-        for (int k = 0; k < 4; k++) {
-            __int128 v = 0;
-            for (int w = 2; w >= 0; w--) v = (v << 32) | (*mags[k])[w];
-            if (negs[k]) v = -v;
-            memcpy(out + 64 * (size_t)i + 16 * k, &v, 16);
-        }
-        sc_to_be_aligned(tb, e.tau);
-        memcpy(tau_be + 32 * (size_t)i, tb, 32);
-        okf[i] = e.ok ? 1 : 0;
-    }
+    for (uint32_t i = 0; i < n; i++) L::eis_half_gcd_lane(c_be + 32 * (size_t)i, out + 64 * (size_t)i, tau_be + 32 * (size_t)i, okf + i);
     return 0;
 }
 // eis_consistent(half-GCD of c, c) for n challenges, and the same after one tamper of the pair: which = 0 none, 1 upsilon's first coefficient + 1, 2 upsilon's second
 // coefficient's sign flipped, 3 tau + 1, 4 the pair of ANOTHER challenge (c + 1)
 int ds_eis_consistent(uint32_t n, const uint8_t* c_be, int which, uint8_t* out) {
-    for (uint32_t i = 0; i < n; i++) {
-        alignas(16) uint8_t cb[32];
-        memcpy(cb, c_be + 32 * (size_t)i, 32);
-        sc c; sc_from_be_aligned(c, cb);
-        sc c_for_pair = c;
-        if (which == 4) { sc one; for (int k = 0; k < 8; k++) one.v[k] = k == 0 ? 1u : 0u; sc_add(c_for_pair, c, one); }
-        eis_short e;
-        glv_half g0, g1;
-        glv_split(g0, g1, c_for_pair);
-        eis_half_gcd(e, g0, g1);
-        if (which == 1) e.u[0][0] ^= 1u;
-        if (which == 2) e.uneg[1] ^= 1u;
-        if (which == 3) { sc one; for (int k = 0; k < 8; k++) one.v[k] = k == 0 ? 1u : 0u; sc_add(e.tau, e.tau, one); }
-        out[i] = eis_consistent(e, c) ? 1 : 0;
-    }
-    return 0;
+    return L::dispatch<L::kEisTampers>(which, [&](auto W) { for (uint32_t i = 0; i < n; i++) L::eis_consistent_lane<decltype(W)::value>(c_be + 32 * (size_t)i, out + i); }) ? 0 : -1;
 }
 // equation 1 in its SHORT form for one item: returns k G - upsilon pk - (tau - 1) R (which a valid signature makes equal to R) through verify_scalars, the table stage
 // and the multi-scalar body; *used_long = the scalar stage fell back to the long form

@@ -1,6 +1,5 @@
 """The product's DEVICE code (zk-nullifier-sig_amd/csrc/plume_*.h), compiled for the host, against the oracles.
 No GPU needed: these pin the exact limb arithmetic, recoding, tables and pipeline logic that the HIP kernels run."""
-import hashlib
 import json
 import random
 from pathlib import Path
@@ -10,235 +9,93 @@ import pytest
 
 from oracle import plume_oracle as O
 from tests import _devsim as D
+from tests import _lane_cases as LC
 from tests import _oracle_c as OC
 from tests import synth
 
 ROOT = Path(__file__).resolve().parent.parent
 GOLD = json.loads((Path(__file__).parent / "golden" / "golden_batches.json").read_text())
 P, N = O.P, O.N
-PC = 2**32 + 977
-EDGE_FE = [0, 1, 2, PC - 1, PC, PC + 1, P - 2, P - 1, P, P + 1, P + PC - 1, 2**256 - PC, 2**256 - PC + 1, 2**256 - 2, 2**256 - 1,
-           2**255, 2**128, 2**128 - 1, (1 << 224) - 1, 0xFFFFFFFF, 0xFFFFFFFF00000000, int("f" * 56 + "0" * 8, 16)]
-
-
-def fe_cases(rng, nrand=300):
-    vals = list(EDGE_FE) + [rng.randrange(2**256) for _ in range(nrand)] + [rng.randrange(P) for _ in range(nrand)]
-    a, b = [], []
-    for x in EDGE_FE:
-        for y in EDGE_FE:
-            a.append(x); b.append(y)
-    for _ in range(nrand * 2):
-        a.append(rng.choice(vals)); b.append(rng.choice(vals))
-    return a, b
 
 
 def test_fe_arith():
-    rng = random.Random(1)
-    a, b = fe_cases(rng)
-    for op, fn in [(0, lambda x, y: x * y), (2, lambda x, y: x + y), (3, lambda x, y: x - y)]:
-        got = D.fe_op(op, a, b)
-        for x, y, g in zip(a, b, got):
-            assert g < 2**256 and g % P == fn(x, y) % P, (op, hex(x), hex(y), hex(g))
-    got = D.fe_op(1, a)
-    assert all(g % P == x * x % P for x, g in zip(a, got))
-    got = D.fe_op(4, a)
-    assert all(g % P == (-x) % P for x, g in zip(a, got))
-    got = D.fe_op(7, a)
-    assert all(g == x % P for x, g in zip(a, got))
-    ks = [1, 2, 3, 4, 8, 11, 1771, 65535, 2**20 - 1]
-    for k in ks:
-        got = D.fe_op(8, a, [k] * len(a))
-        assert all(g % P == x * k % P for x, g in zip(a, got)), k
-    assert [g for g in D.fe_op(9, a)] == [int(x % P == 0) for x in a]
-    assert [g for g in D.fe_op(10, a, b)] == [int((x - y) % P == 0) for x, y in zip(a, b)]
-    assert [g for g in D.fe_op(11, a)] == [(x % P) & 1 for x in a]
-    # round 3: products with a subtraction riding in their fold (plume_fe_mul.inc fe_mul_sub / fe_sqr_sub / fe_sqr_sub2) and the doubling's two-product Y'
-    for op, fn in [(16, lambda x, y: x * y - x), (17, lambda x, y: x * x - 2 * y - x), (18, lambda x, y: x * x - 2 * y), (19, lambda x, y: x * (y - x) - 2 * y * y),
-                   (20, lambda x, y: (x - y) * (x + y) - y)]:
-        got = D.fe_op(op, a, b)
-        for x, y, g in zip(a, b, got):
-            assert g == fn(x, y) % P, (op, hex(x), hex(y), hex(g))
+    LC.check_fe_arith(D.HOST)
 
 
 def test_products_at_their_operand_bounds_come_back_tight():
     """Round 4: the product's top columns run first (gen_fe_mul.py), so the excess over 2^256 is folded into limbs 0..2 before they are formed and limb 8 takes a
     remainder at the end.  Drive the column sums to the contract's bounds (plume_field.h: tight = limbs <= 2^29 + 2^19, limb 8 <= 2^24 + 2^10; multiplication inputs up
-    to 9 * max(a) * max(b) < 2^64 - 2^50 with limb 8 <= 2^26) and check value and tightness of every form; the host build asserts the intermediate bounds."""
-    val = lambda L: sum(x << (29 * i) for i, x in enumerate(L))
-    tight = lambda L: all(x <= 2**29 + 2**19 for x in L[:8]) and L[8] <= 2**24 + 2**10
-    T = 2**29 + 2**19
-    rng = random.Random(44)
-    big = int(((2**64 - 2**50) // 9) ** 0.5) - 1                       # both operands at the square root of the bound (~1.33 * 2^30)
-    shapes = [([T] * 8 + [2**24 + 2**10], [T] * 8 + [2**24 + 2**10]), ([big] * 8 + [2**26], [big] * 8 + [2**26]), ([2**31 - 1] * 8 + [2**26], [T] * 8 + [2**26]),
-              ([0] * 9, [big] * 8 + [2**26]), ([big] * 8 + [0], [0] * 8 + [2**26])]
-    for _ in range(200):
-        m = rng.choice([T, big, 2**29 - 1])
-        shapes.append(([rng.randrange(m + 1) for _ in range(8)] + [rng.randrange(2**26 + 1)], [rng.randrange(m + 1) for _ in range(8)] + [rng.randrange(2**26 + 1)]))
-    a, b = [s[0] for s in shapes], [s[1] for s in shapes]
-    for got, x, y in zip(D.fe_raw(0, a, b), a, b):
-        assert tight(got) and val(got) % P == val(x) * val(y) % P
-    sq = [x for x in a if max(x[:8]) <= big]
-    for got, x in zip(D.fe_raw(1, sq), sq):
-        assert tight(got) and val(got) % P == val(x) ** 2 % P
-    # tight operands for the scaled squarings; subtrahends up to 2p / 4p limbwise for the fused forms
-    ta = [x for x in a if tight(x)] + [[rng.randrange(T + 1) for _ in range(8)] + [rng.randrange(2**24 + 2**10 + 1)] for _ in range(100)]
-    for op, f in [(6, 3), (7, 2)]:
-        for got, x in zip(D.fe_raw(op, ta), ta):
-            assert tight(got) and val(got) % P == f * val(x) ** 2 % P
-    p_l = [0x1FFFFC2F, 0x1FFFFFF7] + [0x1FFFFFFF] * 6 + [0x00FFFFFF]
-    sub2 = [[rng.choice([0, 2 * q, rng.randrange(2 * q + 1)]) for q in p_l] for _ in a]
-    sub4 = [[rng.choice([0, 4 * q, rng.randrange(4 * q + 1)]) for q in p_l] for _ in a]
-    for got, x, y, s in zip(D.fe_raw(3, a, b, sub2), a, b, sub2):
-        assert tight(got) and val(got) % P == (val(x) * val(y) - val(s)) % P
-    for got, x, s in zip(D.fe_raw(4, sq, None, sub4[:len(sq)]), sq, sub4):
-        assert tight(got) and val(got) % P == (val(x) ** 2 - val(s)) % P
-    for got, x, s in zip(D.fe_raw(5, sq, None, sub2[:len(sq)]), sq, sub2):
-        assert tight(got) and val(got) % P == (val(x) ** 2 - 2 * val(s)) % P
-    # two products, one fold: the doubling's Y' at its bound (E * (D - X') + (-B) * 2B: 2^29 * 3 * 2^29 + 2^30 * 2^30 per column term)
-    e1, e2, e3, e4 = [T] * 8 + [2**24], [3 * 2**29 + 2**19] * 8 + [2**26], [2**30 - 2000] * 8 + [2**25], [2**30 + 2**20] * 8 + [2**25]
-    qa = [e1] + [[rng.randrange(v + 1) for v in e1] for _ in range(100)]
-    qb = [e2] + [[rng.randrange(v + 1) for v in e2] for _ in range(100)]
-    qc = [e3] + [[rng.randrange(v + 1) for v in e3] for _ in range(100)]
-    qe = [e4] + [[rng.randrange(v + 1) for v in e4] for _ in range(100)]
-    for got, x, y, z, w in zip(D.fe_raw(2, qa, qb, qc, qe), qa, qb, qc, qe):
-        assert tight(got) and val(got) % P == (val(x) * val(y) + val(z) * val(w)) % P
+    to 9 * max(a) * max(b) < 2^64 - 2^50 with limb 8 <= 2^26) and check value and tightness of every form, the aliasing forms included; the host build asserts the
+    intermediate bounds.  (The body is tests/_lane_cases.py's: tests/test_gpu_devlanes.py runs it on the device branch of the same products.)"""
+    LC.check_products_at_bounds(D.HOST)
 
 
 def test_group_law_compositions_keep_every_product_operand_in_bounds():
     """the product's limb-8 precondition (<= 2^26, since round 4's top-columns-first fold) is asserted in host builds only -- on whatever values a test happens to
     carry.  Here the group law's lazy sums and differences meet operands at the ENDS of the tight range (every limb 0 or its maximum, 2^29 + 2^19 and 2^24 + 2^10 on top, in
     every combination that matters plus random ones): each fe_mul / fe_sqr / fe_muladd inside jac_dbl, jac_dbl_neg, jac_madd (row y negated or not) and jac_add is checked by
-    fe_mul_inputs_ok (the process aborts on a violation), and what comes back must be tight again, so that the operations compose."""
-    T, T8 = 2**29 + 2**19, 2**24 + 2**10
-    rng = random.Random(99)
-    tight = lambda L: all(x <= T for x in L[:8]) and L[8] <= T8
-    hi, lo = [T] * 8 + [T8], [0] * 9
-
-    def pick():
-        r = rng.random()
-        if r < 0.3:
-            return list(hi)
-        if r < 0.45:
-            return list(lo)
-        if r < 0.8:
-            return [rng.choice([0, T]) for _ in range(8)] + [rng.choice([0, T8])]
-        return [rng.randrange(T + 1) for _ in range(8)] + [rng.randrange(T8 + 1)]
-    n = 600
-    ops = [[pick() for _ in range(n)] for _ in range(5)]
-    for k in range(5):                                   # the all-maximum and the all-but-one-maximum combinations first
-        for j in range(5):
-            ops[j][k] = list(hi if j != k else lo)
-    ops[0][5], ops[1][5], ops[2][5], ops[3][5], ops[4][5] = list(hi), list(hi), list(hi), list(hi), list(hi)
-    for op in range(6):
-        for row in D.group_raw(op, *ops):
-            assert tight(row[0:9]) and tight(row[9:18]) and tight(row[18:27]), op
-    # ... and composed: the outputs of one operation are the inputs of the next, twelve deep, every order
-    cur = [ops[0], ops[1], ops[2]]
-    for step in range(12):
-        op = rng.choice([0, 1, 2, 4, 5])
-        out = D.group_raw(op, cur[0], cur[1], cur[2], ops[3], ops[4])
-        cur = [[r[0:9] for r in out], [r[9:18] for r in out], [r[18:27] for r in out]]
-        assert all(tight(a) and tight(b) and tight(c) for a, b, c in zip(*cur)), (step, op)
+    fe_mul_inputs_ok (the process aborts on a violation), and what comes back must be tight again, so that the operations compose -- and every point that comes back is the
+    group law's over Python integers."""
+    LC.check_group_law_compositions(D.HOST)
 
 
 def test_fe_inv_pow():
-    rng = random.Random(2)
-    a = [1, 2, P - 1, P + 1, 2**256 - 1, PC] + [rng.randrange(1, 2**256) for _ in range(40)]
-    a = [x for x in a if x % P]
-    assert [g % P for g in D.fe_op(5, a)] == [pow(x, P - 2, P) for x in a]
-    assert [g % P for g in D.fe_op(6, a)] == [pow(x, (P - 3) // 4, P) for x in a]
-    assert D.fe_op(5, [0, P])[0] % P == 0
+    LC.check_fe_inv_pow(D.HOST)
 
 
 def test_sc_arith():
-    rng = random.Random(3)
-    edge = [0, 1, 2, N - 1, N - 2, (N - 1) // 2, 2**128, 2**255 % N, 2**256 - N]
-    a = edge * len(edge) + [rng.randrange(N) for _ in range(300)]
-    b = [y for y in edge for _ in edge] + [rng.randrange(N) for _ in range(300)]
-    assert D.sc_op(0, a, b) == [x * y % N for x, y in zip(a, b)]
-    assert D.sc_op(1, a, b) == [(x + y) % N for x, y in zip(a, b)]
-    assert D.sc_op(2, a) == [(-x) % N for x in a]
-    wide_lo = [rng.randrange(2**256) for _ in range(200)] + [2**256 - 1, 0, 2**256 - 1]
-    wide_hi = [rng.randrange(2**256) for _ in range(200)] + [2**256 - 1, 2**256 - 1, 0]
-    assert D.sc_op(3, wide_lo, wide_hi) == [(lo + (hi << 256)) % N for lo, hi in zip(wide_lo, wide_hi)]
+    LC.check_sc_arith(D.HOST)
 
 
 def test_glv_and_booth():
-    rng = random.Random(4)
-    lam = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
-    ks = [0, 1, 2, N - 1, N - 2, lam, lam + 1, N - lam, (N - 1) // 2, (N + 1) // 2, 2**128, 2**128 - 1, 2**255 % N] + [rng.randrange(N) for _ in range(2000)]
-    # round 4: the split is exact integer arithmetic on 29-bit limbs (plume_ec.h glv_split): k1 = k - c1 a1 - c2 a2, k2 = c1 (-b1) - c2 b2 with c_i = round(k g_i / 2^384)
-    g1 = 0x3086D221A7D46BCDE86C90E49284EB153DAA8A1471E8CA7FE893209A45DBB031
-    g2 = 0xE4437ED6010E88286F547FA90ABFE4C4221208AC9DF506C61571B4AE8AC47F71
-    a1, mb1, a2 = 0x3086D221A7D46BCDE86C90E49284EB15, 0xE4437ED6010E88286F547FA90ABFE4C3, 0x114CA50F7A8E2F3F657C1108D9D44CFD8
-    ks += [N - lam, 2**255, 2**256 % N, (1 << 174) - 1, 1 << 174, (1 << 174) + 1, (1 << 145) - 1, g1 % N, g2 % N] + [rng.randrange(N) for _ in range(6000)]
-    nonzero = total = 0
-    for k, (m1, n1, m2, n2, codes) in zip(ks, D.glv(ks)):
-        assert m1 < 2**128 and m2 < 2**128
-        k1 = -m1 if n1 else m1
-        k2 = -m2 if n2 else m2
-        assert (k1 + k2 * lam) % N == k
-        c1, c2 = (k * g1 + (1 << 383)) >> 384, (k * g2 + (1 << 383)) >> 384
-        assert (k1, k2) == (k - c1 * a1 - c2 * a2, c1 * mb1 - c2 * a1), hex(k)
-        # round 5: ONE Eisenstein digit per position (plume_ec.h eisd_store): k1 + k2 w = sum d_i 4^i, d_i in {0, units, associates of 1 - w, associates of 2}
-        assert len(codes) == D.NPOS and all(0 <= c <= 18 for c in codes)
-        va = vb = 0
-        for c in reversed(codes):
-            da, db = D.eis_digit(c)
-            va, vb = 4 * va + da, 4 * vb + db
-        assert (va, vb) == (k1, k2), hex(k)
-        nonzero += sum(1 for c in codes[:64] if c)
-        total += 64
-    assert 0.92 < nonzero / total < 0.95                       # fifteen of the sixteen residues mod 4 are non-zero digits
+    LC.check_glv_and_booth(D.HOST)
 
 
 def test_eisenstein_digit_table():
     """the 64-entry table behind eisd_entry (plume_ec.h), regenerated from its definition: for t = (ta, tb), |t| <= 4, the digit is the representative of t mod 4 among
-    0, the units, the associates of theta = 1 - w and of 2 that leaves a carry (t - d) / 4 in {-1, 0, 1}^2; and the header carries exactly this table"""
-    import re
-    digits = {c: D.eis_digit(c) for c in range(1, 19)}
-    assert len(set(digits.values())) == 18 and all(max(abs(a), abs(b)) <= 2 for a, b in digits.values())
-    assert {(a % 4, b % 4) for a, b in digits.values()} | {(0, 0)} == {(a, b) for a in range(4) for b in range(4)}      # a complete residue system of Z[w] / 4
-    tab = []
-    for idx in range(64):
-        ca, cb, na, nb = (idx >> 2) & 3, idx & 3, (idx >> 4) & 1, (idx >> 5) & 1
-        ta_s = [t for t in range(-4, 5) if t % 4 == ca and (t < 0) == bool(na)]
-        tb_s = [t for t in range(-4, 5) if t % 4 == cb and (t < 0) == bool(nb)]
-        if not ta_s or not tb_s:
-            tab.append(0)
-            continue
-        if (ca, cb) == (0, 0):
-            tab.append(0 | (2 << 5) | (2 << 8))
-            continue
-        best = None
-        for code, d in digits.items():
-            if (d[0] % 4, d[1] % 4) != (ca, cb):
-                continue
-            worst = max([abs((t - d[0]) // 4) for t in ta_s] + [abs((t - d[1]) // 4) for t in tb_s])
-            if best is None or worst < best[0]:
-                best = (worst, code, d)
-        assert best and best[0] <= 1, idx
-        tab.append(best[1] | ((best[2][0] + 2) << 5) | ((best[2][1] + 2) << 8))
-    src = (Path(__file__).parent.parent / "zk-nullifier-sig_amd" / "csrc" / "plume_ec.h").read_text()
-    body = src[src.index("static const uint16_t T[64] = {"):]
-    body = body[:body.index("};")]
-    assert [int(x, 16) for x in re.findall(r"0x[0-9A-Fa-f]{3}", body)] == tab
-    # ... and the register-resident packing the kernels run (eisd_entry) is this table for every t the recoding can meet
-    import ctypes as C
-    out = np.zeros(162, dtype=np.uint32)
-    D.lib().ds_eisd_entries(out.ctypes.data_as(C.POINTER(C.c_uint32)))
-    k = 0
-    for ta in range(-4, 5):
-        for tb in range(-4, 5):
-            idx = ((ta & 3) << 2) | (tb & 3) | (16 if ta < 0 else 0) | (32 if tb < 0 else 0)
-            assert int(out[k]) == tab[idx] and int(out[k + 1]) == tab[idx], (ta, tb)
-            k += 2
+    0, the units, the associates of theta = 1 - w and of 2 that leaves a carry (t - d) / 4 in {-1, 0, 1}^2; and the header carries exactly this table
+    ... and the register-resident packing the kernels run (eisd_entry) is this table for every t the recoding can meet"""
+    LC.check_eisd_entries(D.HOST, LC.eisenstein_digit_table())
 
 
 def test_sha256_generic():
-    for n in (0, 1, 3, 55, 56, 57, 63, 64, 65, 119, 120, 121, 198, 99, 500):
-        d = bytes((i * 13 + n) & 0xFF for i in range(n))
-        assert D.sha256(d) == hashlib.sha256(d).digest(), n
+    LC.check_sha256_generic(D.HOST)
+
+
+def test_lane_placement_checks_on_the_host_build():
+    """the checks that tests/test_gpu_devlanes.py adds for the GPU (batch sizes around a wavefront, one wavefront of edge pairs, batches in a shuffled order) hold on the
+    host build too: they test the checks, and the bodies they drive, before a GPU sees either"""
+    LC.check_counts(D.HOST, counts=(1, 63, 64, 65, 193))
+    LC.check_one_wave_of_edge_pairs(D.HOST)
+    LC.check_sc_arith(LC.Placed(D.HOST, 5))
+
+
+def test_gpu_binding_is_poisoned_by_a_failure(monkeypatch):
+    """tests/_devgpu.py: a non-zero return raises with the library's error text, and every later call raises before it reaches the library"""
+    from tests import _devgpu as G
+
+    class Fn:
+        def __init__(self, rc):
+            self.rc, self.calls = rc, 0
+
+        def __call__(self, *args):
+            self.calls += 1
+            return self.rc
+
+    class Stub:
+        dg_sc_op, dg_fe_op = Fn(0), Fn(7)
+        dg_last_error = staticmethod(lambda: b"dg_fe_op: hipMalloc: out of memory")
+
+    monkeypatch.setattr(G, "_lib", Stub)
+    monkeypatch.setattr(G, "_poisoned", None)
+    G.sc_op(0, [1], [2])
+    with pytest.raises(G.DevGpuError, match="returned 7: dg_fe_op: hipMalloc: out of memory"):
+        G.fe_op(0, [1], [2])
+    assert G.poisoned()
+    for call in (lambda: G.sc_op(0, [1], [2]), lambda: G.fe_op(0, [1], [2]), lambda: G.sha256(b"")):
+        with pytest.raises(G.DevGpuError, match="poisoned"):
+            call()
+    assert (Stub.dg_sc_op.calls, Stub.dg_fe_op.calls) == (1, 1)
 
 
 def test_point_mul_matches_oracle():
@@ -626,14 +483,7 @@ def test_crafted_collisions_take_the_checked_fallback():
 
 def test_inversion_by_divsteps_matches_fermat_and_python():
     """fe_inv (Bernstein-Yang divsteps, 20 x 30 steps) against pow(x, -1, p), and against the Fermat chain it replaced; 0 and p give 0"""
-    rng = random.Random(2024)
-    vals = [1, 2, 3, P - 1, P - 2, P + 1, 2**255, 2**256 - 1, 977, 2**32 + 977, 2**128, 2**30, 2**30 - 1, 2**60, (P + 1) // 2]
-    vals += [rng.getrandbits(256) for _ in range(3000)] + [rng.getrandbits(k) | 1 for k in (1, 8, 29, 30, 31, 58, 60, 61, 200, 255) for _ in range(20)]
-    vals = [v for v in vals if v % P]
-    got = D.fe_op(15, vals)
-    assert got == [pow(v % P, -1, P) for v in vals]
-    assert [g % P for g in D.fe_op(5, vals)] == got
-    assert D.fe_op(15, [0, P]) == [0, 0]
+    LC.check_inversion_by_divsteps(D.HOST)
 
 
 def _check_h2c_intermediates(get, regs_from_be, kats):
@@ -812,50 +662,20 @@ def test_twenty_bit_generator_window_build_of_the_device_headers(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ round 5: the short form of equation 1 (csrc/plume_eis.h)
-_LAM = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
-
-
-def _eis_cases(rng, nrand):
-    n = O.N
-    a1, b1 = 0x3086D221A7D46BCDE86C90E49284EB15, 0xE4437ED6010E88286F547FA90ABFE4C3
-    cs = [0, 1, 2, 3, n - 1, n - 2, _LAM, _LAM + 1, _LAM * _LAM % n, 2**128, 2**64, 2**64 + 1, 2**65, 2**96, 2**127, 2**192, (n - 1) // 2, (n + 1) // 2, a1, b1, n - a1, n - b1]
-    cs += [(x + y * _LAM) % n for x in (1, 2**63, 2**64, 2**65, 2**66, -2**64, 3 * 2**62) for y in (0, 1, -1, 2**63, 2**64, -2**65)]      # short on the gamma side already
-    cs += [pow(rng.randrange(2, 2**70), -1, n) for _ in range(100)]                                                                       # tau short, upsilon = 1
-    cs += [rng.randrange(1, 2**66) * pow(rng.randrange(1, 2**66), -1, n) % n for _ in range(100)]                                      # both short: the answer is (nearly) unique
-    cs += [rng.getrandbits(k) % n for k in (8, 16, 32, 64, 96, 127, 129, 160, 200) for _ in range(10)]
-    cs += [rng.randrange(1, n) for _ in range(nrand)]
-    return [c % n for c in cs]
+_eis_cases = LC.eis_cases
 
 
 def test_eis_half_gcd_relation_and_bounds():
     """tau gamma = upsilon (mod pi) for every c -- i.e. (t0 + t1 lambda) c = u0 + u1 lambda (mod n) --, tau != 0, every coefficient below 2^67 (in fact <= 65 bits: the chain
     has seventeen 4-bit windows), no fallback; random and crafted challenges, c = 0 included (verify_non_zk admits it).  The quotients are double-precision estimates: the
     RELATION holds whatever they are, the BOUND is what this test measures."""
-    rng = random.Random(20261002)
-    cs = _eis_cases(rng, 20000)
-    worst = 0
-    for c, (tm1, t1, u0, u1, tau, ok) in zip(cs, D.eis_half_gcd(cs)):
-        t0 = tm1 + 1
-        assert tau == (t0 + t1 * _LAM) % O.N and tau != 0
-        assert (tau * c - (u0 + u1 * _LAM)) % O.N == 0, hex(c)
-        assert ok, hex(c)
-        worst = max(worst, abs(tm1), abs(t1), abs(u0), abs(u1))
-    assert worst.bit_length() <= 66, worst.bit_length()
+    LC.check_eis_half_gcd(D.HOST)
 
 
 def test_eis_pair_is_checked_before_it_is_used():
     """the scalar stage re-derives tau c == upsilon (mod n) from the pair it is about to use (eis_consistent) and falls back to the long form when it does not hold: true for
     every honest pair, crafted challenges included; false after any single tamper -- a coefficient's bit, a sign, tau itself, the pair of a neighbouring challenge"""
-    rng = random.Random(99)
-    cs = _eis_cases(rng, 4000)
-    assert D.eis_consistent(cs).all()
-    pairs = D.eis_half_gcd(cs)
-    for which in (1, 2, 3, 4):
-        got = D.eis_consistent(cs, which)
-        for c, g, (_, _, _, u1, _, _) in zip(cs, got, pairs):
-            if g:       # a tamper that changes nothing: the sign of a ZERO coefficient (upsilon = u0 for small c and for c near n); tau + 1 for c = 0 (both sides stay 0)
-                assert (which == 2 and u1 == 0) or (which == 3 and c == 0), (which, hex(c))
-        assert got.sum() < len(cs) // 20, (which, int(got.sum()))
+    LC.check_eis_pair_is_checked(D.HOST)
 
 
 def test_equation1_short_form_value_and_fallback():
