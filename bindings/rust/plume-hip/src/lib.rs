@@ -89,6 +89,10 @@ pub const PLUME_ETH_ADDR_EIP55: c_int = 2;
 pub const PLUME_ECDSA_MISMATCH: u8 = 0;
 pub const PLUME_ECDSA_MATCH: u8 = 1;
 pub const PLUME_ECDSA_INVALID: u8 = 3;
+/// `plume_ecdsa_sign_batch`: flag bit 0, `v` is 27 or 28; `plume_eth_message_hash_batch`: what is hashed
+pub const PLUME_ECDSA_SIGN_V27: c_int = 1;
+pub const PLUME_ETH_HASH_KECCAK256: c_int = 0;
+pub const PLUME_ETH_HASH_EIP191: c_int = 1;
 pub const PLUME_ECDSA_LOW_S: c_int = 1;
 
 #[link(name = "plume_hip")]
@@ -151,6 +155,13 @@ extern "C" {
         expect: *const u8, pk: *mut u8, address: *mut u8, status: *mut u8) -> c_int;
     fn plume_ecdsa_recover_batch_device(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, hash: *const u8, r: *const u8, s: *const u8,
         v: *const u8, expect: *const u8, pk: *mut u8, address: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_eth_message_hash_batch(ctx: *mut plume_ctx, mode: c_int, n: usize, msgs: *const u8, msg_off: *const u64, hash32: *mut u8) -> c_int;
+    fn plume_eth_message_hash_batch_device(ctx: *mut plume_ctx, mode: c_int, n: usize, msgs: *const u8, msg_off: *const u64, msgs_bytes: usize, hash32: *mut u8,
+        stream: *mut c_void) -> c_int;
+    fn plume_ecdsa_sign_batch(ctx: *mut plume_ctx, flags: c_int, n: usize, hash: *const u8, sk: *const u8, aux: *const u8, r: *mut u8, s: *mut u8, v: *mut u8,
+        status: *mut u8) -> c_int;
+    fn plume_ecdsa_sign_batch_device(ctx: *mut plume_ctx, flags: c_int, n: usize, hash: *const u8, sk: *const u8, aux: *const u8, r: *mut u8, s: *mut u8, v: *mut u8,
+        status: *mut u8, stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -288,6 +299,39 @@ impl HipEngine {
         if rc != 0 { return Err(last_error()); }
         if status[0] == PLUME_ECDSA_INVALID { return Err(HipError("ecdsa_recover_address: the signature recovers no public key".to_string())); }
         Ok(addr)
+    }
+
+    /// A deterministic ECDSA signature `(r, s, v)` by `sk` (32 big-endian bytes) over a 32-byte digest (`plume_ecdsa_sign_batch`): the RFC 6979 nonce over the digest
+    /// itself, byte-identical to geth, ethers and libsecp256k1, hedged with `aux` when given; always low `s`; `v` is 0 / 1, or 27 / 28 with `v27`.  An error when `sk` is
+    /// outside [1, n - 1], the outcome is degenerate, or the self-check withheld the signature.
+    pub fn ecdsa_sign(&self, sk: &[u8; 32], hash32: &[u8; 32], aux: Option<&[u8; 32]>, v27: bool) -> Result<([u8; 32], [u8; 32], u8), HipError> {
+        let (mut r, mut s, mut v, mut status) = ([0u8; 32], [0u8; 32], [0u8; 1], [0u8; 1]);
+        let rc = unsafe { plume_ecdsa_sign_batch(self.0, if v27 { PLUME_ECDSA_SIGN_V27 } else { 0 }, 1, hash32.as_ptr(), sk.as_ptr(), aux.map_or(std::ptr::null(), |a| a.as_ptr()),
+                                                 r.as_mut_ptr(), s.as_mut_ptr(), v.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        if status[0] != 0 { return Err(HipError(format!("ecdsa_sign: no signature (status {})", status[0]))); }
+        Ok((r, s, v[0]))
+    }
+    /// The EIP-191 digest of `msg`, Keccak-256("\x19Ethereum Signed Message:\n" || decimal(len) || msg) (`plume_eth_message_hash_batch`).
+    pub fn eth_message_hash(&self, msg: &[u8]) -> Result<[u8; 32], HipError> {
+        let off = [0u64, msg.len() as u64];
+        let mut h = [0u8; 32];
+        let rc = unsafe { plume_eth_message_hash_batch(self.0, PLUME_ETH_HASH_EIP191, 1, msg.as_ptr(), off.as_ptr(), h.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        Ok(h)
+    }
+    /// A wallet's `personal_sign`: the 65 bytes `r || s || v` (`v` = 27 / 28) of `ecdsa_sign` over the EIP-191 digest of `msg`.
+    pub fn personal_sign(&self, sk: &[u8; 32], msg: &[u8], aux: Option<&[u8; 32]>) -> Result<[u8; 65], HipError> {
+        let (r, s, v) = self.ecdsa_sign(sk, &self.eth_message_hash(msg)?, aux, true)?;
+        let mut out = [0u8; 65];
+        out[..32].copy_from_slice(&r); out[32..64].copy_from_slice(&s); out[64] = v;
+        Ok(out)
+    }
+    /// The public key and the address that `personal_sign`ed `msg`: the EIP-191 digest, then `ecdsa_recover`.
+    pub fn personal_recover(&self, msg: &[u8], sig65: &[u8; 65]) -> Result<(AffinePoint, [u8; 20]), HipError> {
+        let (mut r, mut s) = ([0u8; 32], [0u8; 32]);
+        r.copy_from_slice(&sig65[..32]); s.copy_from_slice(&sig65[32..64]);
+        self.ecdsa_recover(&self.eth_message_hash(msg)?, &r, &s, sig65[64])
     }
 
     /// Aggregate pre-filter (no reference counterpart; include/plume_hip.h `plume_aggregate_check`): `Ok(true)` iff every V1 signature of the batch would

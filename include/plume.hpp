@@ -365,6 +365,47 @@ inline std::array<uint8_t, 20> ecdsa_recover_address(const Bytes32& hash32, cons
     return addr;
 }
 
+// A deterministic ECDSA signature by sk over the 32-byte digest hash32, made on the GPU (plume_hip.h plume_ecdsa_sign_batch): the RFC 6979 nonce over the digest itself --
+// byte-identical to geth, ethers and libsecp256k1 -- hedged with the 32 bytes of aux when given; always low s; v 0 / 1, or 27 / 28 with v27.  Throws SignatureError when the
+// outcome is degenerate (status 2 / 4: a SecretKey is always in range), plume_hip::SelfCheckError when the self-check withheld the signature.
+struct EcdsaSignature {
+    Bytes32 r{}, s{};
+    uint8_t v = 0;
+};
+inline EcdsaSignature ecdsa_sign(const SecretKey& sk, const Bytes32& hash32, const Bytes32* aux = nullptr, Engine& eng = Engine::shared(), bool v27 = false) {
+    EcdsaSignature sig;
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_ecdsa_sign_batch(eng.ctx(), v27 ? PLUME_ECDSA_SIGN_V27 : 0, 1, hash32.data(), sk.to_bytes().data(), aux ? aux->data() : nullptr, sig.r.data(), sig.s.data(),
+                                            &sig.v, &st),
+                     "plume_ecdsa_sign_batch");
+    if (st & PLUME_STATUS_SELFCHECK_FAILED) throw plume_hip::SelfCheckError("the signature does not recover the signer's key and was withheld (plume_set_sign_selfcheck)");
+    if (st) throw SignatureError();
+    return sig;
+}
+// The EIP-191 digest of msg, Keccak-256("\x19Ethereum Signed Message:\n" || decimal(len) || msg), on the GPU (plume_eth_message_hash_batch)
+inline Bytes32 eth_message_hash(const uint8_t* msg, size_t len, Engine& eng = Engine::shared(), int mode = PLUME_ETH_HASH_EIP191) {
+    const uint64_t off[2] = {0, (uint64_t)len};
+    Bytes32 h{};
+    plume_hip::check(plume_eth_message_hash_batch(eng.ctx(), mode, 1, msg, off, h.data()), "plume_eth_message_hash_batch");
+    return h;
+}
+// A wallet's personal_sign: the 65 bytes r || s || v (v = 27 / 28) of ecdsa_sign over the EIP-191 digest of msg
+inline std::array<uint8_t, 65> personal_sign(const SecretKey& sk, const uint8_t* msg, size_t len, const Bytes32* aux = nullptr, Engine& eng = Engine::shared()) {
+    const EcdsaSignature sig = ecdsa_sign(sk, eth_message_hash(msg, len, eng), aux, eng, true);
+    std::array<uint8_t, 65> out{};
+    std::copy(sig.r.begin(), sig.r.end(), out.begin());
+    std::copy(sig.s.begin(), sig.s.end(), out.begin() + 32);
+    out[64] = sig.v;
+    return out;
+}
+// The public key and the address that personal_sign'ed msg: the EIP-191 digest, then ecdsa_recover
+inline std::pair<AffinePoint, std::array<uint8_t, 20>> personal_recover(const uint8_t* msg, size_t len, const std::array<uint8_t, 65>& sig65, Engine& eng = Engine::shared()) {
+    Bytes32 r{}, s{};
+    std::copy(sig65.begin(), sig65.begin() + 32, r.begin());
+    std::copy(sig65.begin() + 32, sig65.begin() + 64, s.begin());
+    return ecdsa_recover(eth_message_hash(msg, len, eng), r, s, sig65[64], eng);
+}
+
 // rust-k256/src/randomizedsigner.rs:25-41: a borrowed secret key and the variant
 class PlumeSigner {
   public:

@@ -75,8 +75,10 @@ int plume_shard_numa_node(const plume_ctx* ctx, int shard);
 void plume_destroy(plume_ctx* ctx);
 /* Last error text of this thread (valid until the next failing call on the thread). */
 const char* plume_last_error(void);
-/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  0.12: public keys and addresses from ECDSA signatures
- * (plume_ecdsa_recover_batch*: ecrecover); 0.11: Ethereum addresses of public keys (plume_eth_address_batch*: Keccak-256);
+/* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  The number in the string stays 0.12 for library 0.13: callers
+ * that need the 0.13 entry points look for the symbols (dlsym / getattr), as zk-nullifier-sig_amd/capi.py does.  0.13: deterministic ECDSA signatures with a recovery id
+ * (plume_ecdsa_sign_batch*) and the digest a wallet signs (plume_eth_message_hash_batch*: Keccak-256 of ragged messages, EIP-191); 0.12: public keys and addresses from
+ * ECDSA signatures (plume_ecdsa_recover_batch*: ecrecover); 0.11: Ethereum addresses of public keys (plume_eth_address_batch*: Keccak-256);
  * 0.10: point recovery (plume_recover_batch*: r_point, hashed_to_curve_r and hashed_to_curve from pk, nullifier, c, s);
  * 0.9: the signer's self-check (plume_set_sign_selfcheck, PLUME_STATUS_SELFCHECK_FAILED); 0.8: derived signing nonces (plume_sign_batch_rfc6979*); 0.7: the persistent nullifier set (plume_nullset_*); 0.5 (round 5): plume_set_stage_timing, stage events off by default; 0.4 (round 5): plume_get_sign_uniform, plume_set_host_lanes, plume_set_eq1_short;
  * the signer defaults to uniform level 1; the generator tables are built by the first call that needs them; stream = NULL means the stream of the context the caller
@@ -530,6 +532,53 @@ int plume_ecdsa_recover_batch(plume_ctx* ctx, int flags, int pk_format, int addr
                               const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status);
 int plume_ecdsa_recover_batch_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s,
                                      const uint8_t* v, const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, void* stream);
+
+/* ---- the digest a wallet signs: Keccak-256 of ragged messages, EIP-191  (library 0.13) ---------------------------
+ * plume_ecdsa_recover_batch and plume_ecdsa_sign_batch take a 32-byte digest; this call makes it from the message.  Message i is msgs[msg_off[i] .. msg_off[i + 1])
+ * (n + 1 offsets, as everywhere else; item lengths below 2^32), and hash32 gets 32 bytes per item:
+ *   PLUME_ETH_HASH_KECCAK256   Keccak-256(msg): the ORIGINAL padding (0x01 ... 0x80, rate 136), not SHA3-256
+ *   PLUME_ETH_HASH_EIP191      Keccak-256("\x19Ethereum Signed Message:\n" || decimal(len(msg)) || msg): what personal_sign / eth_sign hash.  The prefix is 26 bytes; the
+ *                              length is ASCII decimal without leading zeros ("0" for the empty message)
+ * Any other mode returns PLUME_ERR_ARG; n = 0 is a successful no-op.  Like plume_eth_address_batch the call needs no table and no workspace and everything is public
+ * data.  The host form cuts the batch into pieces of at most plume_set_chunk items and splits it over the shards of a plume_init_multi context; offsets that decrease
+ * return PLUME_ERR_ARG there.  The device form (a single-device context) is ONE kernel enqueued on `stream` with no synchronisation; an item whose offsets decrease or
+ * reach past msgs_bytes hashes the empty message and never reads msgs, as in the other device forms.  msgs and hash32 may sit at any byte offset (msg_off: 8-byte
+ * aligned); message bytes are read with aligned 8-byte loads where the words lie inside msgs.  With stage timing on the stage is "eth_message_hash". */
+#define PLUME_ETH_HASH_KECCAK256 0
+#define PLUME_ETH_HASH_EIP191    1
+int plume_eth_message_hash_batch(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, uint8_t* hash32);
+int plume_eth_message_hash_batch_device(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, uint8_t* hash32, void* stream);
+
+/* ---- deterministic ECDSA signatures with a recovery id  (library 0.13) -------------------------------------------
+ * The signer's counterpart of plume_ecdsa_recover_batch: the personal_sign, the transaction signature, the "proof of ECDSA" that publishes a key -- produced where the
+ * keys already are, so that sk never has to leave the engine for a CPU library.  The result is byte-identical to what geth, ethers and libsecp256k1 produce for the same
+ * key and digest.  For item i, with hash 32 bytes, sk 32 big-endian bytes and aux NULL or 32 bytes per item:
+ *   z     int(hash) mod n.
+ *   k     RFC 6979 section 3.2 with HMAC-SHA-256, q = n, x = sk as given, h1 = hash: plain RFC 6979 over the digest itself, NOT the "PLUME-RFC6979" preimage of
+ *         plume_sign_batch_rfc6979.  aux non-NULL appends its 32 bytes in steps d and f (section 3.6), exactly as there.  The nonce loop stops after the same
+ *         PLUME_NONCE_ROUNDS (16) candidates.  k is derived, used and wiped on the device; no call returns it.
+ *   R     k G;  r = R.x mod n;  s = k^-1 (z + r sk) mod n.
+ *   low s ALWAYS: if s > (n - 1) / 2 then s <- n - s and the parity flips (EIP-2; what plume_ecdsa_recover_batch accepts under PLUME_ECDSA_LOW_S).
+ *   v     the parity of R.y after that flip: 0 or 1, or 27 or 28 with PLUME_ECDSA_SIGN_V27 in flags.
+ *   status  0: signed.  PLUME_STATUS_BAD_SCALAR: sk outside [1, n - 1], or the nonce cap ran out.  PLUME_STATUS_IDENTITY: a degenerate outcome -- r = 0, s = 0, or
+ *         R.x >= n.  The last one is a valid signature elsewhere, with a recovery id of 2 or 3 that the one-byte v here and plume_ecdsa_recover_batch do not represent; its
+ *         probability is about 2^-128 and there is NO retry with another nonce (that would leave RFC 6979).  Any non-zero status writes all-zero r, s, v.
+ * Unknown flags bits return PLUME_ERR_ARG; n = 0 is a successful no-op; all four outputs are required.  Outputs are bit-identical at every plume_set_sign_uniform level.
+ * Everything that touches sk, k, k^-1 or z + r sk is select-based at every level: the reduction of R.x, the low-s negation, the zeroing of failed items; the inversion of
+ * k is the fixed-iteration safegcd.  The comb's digit-dependent schedule and addresses are what plume_set_sign_uniform says of r G in plume_sign_batch.
+ * plume_set_sign_selfcheck(ctx, 1) covers this entry point: the signatures are staged in the context together with sk G, the stages of plume_ecdsa_recover_batch recover a
+ * key from every staged (hash, r, s, v), and one release kernel writes the caller's arrays -- byte-identical to mode 0 where the recovered key is sk G, all zero with
+ * PLUME_STATUS_SELFCHECK_FAILED for any other item whose own status was 0, and as mode 0 writes it for an item with a status of its own.  The staging is wiped.
+ * Routing is that of plume_sign_batch_rfc6979*: the host form runs the signer's pipeline (pieces, plume_set_chunk, both host lanes, the shards of a plume_init_multi context;
+ * sk and aux are staged and wiped like the signer's); the device form (a single-device context, n at most the chunk size) enqueues on `stream`, waits for and leaves behind
+ * the workspace event, honours plume_set_sub_batches and plume_set_in_flight and does not synchronise.  The call builds the comb of G (or the level-2 scanned table) on
+ * first use and never the verifier's 1 GiB window table.  The arrays may sit at any byte offset.  With stage timing on the stages are "ecdsa_sign_nonce",
+ * "ecdsa_sign_gmul", "to_affine", "ecdsa_sign_finalize"; with the self-check on, the stages of plume_ecdsa_recover_batch and "ecdsa_sign_release" follow them. */
+#define PLUME_ECDSA_SIGN_V27 1   /* flags bit 0: v is 27 or 28 instead of 0 or 1 */
+int plume_ecdsa_sign_batch(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v,
+                           uint8_t* status);
+int plume_ecdsa_sign_batch_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v,
+                                  uint8_t* status, void* stream);
 
 /* ---- persistent nullifier set: reject repeats across batches  (library 0.7) ----------------------------------
  * A consumer that verifies a STREAM of batches (a vote tally, a claim relayer, a rate limiter) must reject a nullifier it accepted any number of

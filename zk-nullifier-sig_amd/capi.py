@@ -152,10 +152,17 @@ def _load():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
+    # the digest a wallet signs and deterministic ECDSA signatures (library 0.13; Engine.eth_message_hash_batch* / ecdsa_sign_batch* raise PlumeHipError on an older build)
+    for name, args in (("plume_eth_message_hash_batch", [vp, i, sz] + [vp] * 3), ("plume_eth_message_hash_batch_device", [vp, i, sz, vp, vp, sz, vp, vp]),
+                       ("plume_ecdsa_sign_batch", [vp, i, sz] + [vp] * 7), ("plume_ecdsa_sign_batch_device", [vp, i, sz] + [vp] * 8)):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
     _lib = lib
-    if _version(lib) < (0, 12) and not os.environ.get("PLUME_HIP_LIB"):
+    # (the 0.13 entry points are told by their symbols: plume_version() still begins "plume_hip 0.12")
+    if (_version(lib) < (0, 12) or getattr(lib, "plume_ecdsa_sign_batch", None) is None) and not os.environ.get("PLUME_HIP_LIB"):
         _lib = None
-        raise PlumeHipError(f"{p} is {lib.plume_version().decode()}: this module needs plume_hip >= 0.12 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        raise PlumeHipError(f"{p} is {lib.plume_version().decode()} without plume_ecdsa_sign_batch: this module needs the 0.13 entry points (rebuild: make -C zk-nullifier-sig_amd/csrc)")
     return lib
 
 
@@ -170,7 +177,8 @@ def exported_symbols():
             "plume_nullset_create", "plume_nullset_destroy", "plume_nullset_reserve", "plume_nullset_clear", "plume_nullset_size", "plume_nullset_insert", "plume_nullset_contains",
             "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device", "plume_sign_batch_rfc6979", "plume_sign_batch_rfc6979_device",
             "plume_set_sign_selfcheck", "plume_get_sign_selfcheck", "plume_recover_batch", "plume_recover_batch_device",
-            "plume_eth_address_batch", "plume_eth_address_batch_device", "plume_ecdsa_recover_batch", "plume_ecdsa_recover_batch_device"]
+            "plume_eth_address_batch", "plume_eth_address_batch_device", "plume_ecdsa_recover_batch", "plume_ecdsa_recover_batch_device",
+            "plume_eth_message_hash_batch", "plume_eth_message_hash_batch_device", "plume_ecdsa_sign_batch", "plume_ecdsa_sign_batch_device"]
 
 
 def pack_messages(msgs):
@@ -205,6 +213,9 @@ ETH_ADDR_FORMATS = {"raw20": (0, 20), "record64": (1, 64), "eip55": (2, 42)}   #
 # plume_ecdsa_recover_batch (include/plume_hip.h): the status of an item, the flag bits; keys and addresses come in the formats above
 ECDSA_MISMATCH, ECDSA_MATCH, ECDSA_INVALID = 0, 1, 3
 ECDSA_LOW_S = 1
+# plume_eth_message_hash_batch (include/plume_hip.h): what is hashed;  plume_ecdsa_sign_batch: the flag bit (the status of an item is the signer's: 0, 2, 4, 8)
+ETH_HASH_MODES = {"keccak256": 0, "eip191": 1}
+ECDSA_SIGN_V27 = 1
 
 
 def parse_aggregate_record(rec):
@@ -532,6 +543,42 @@ class Engine:
                   "plume_ecdsa_recover_batch")
         return pk, address, status
 
+    def _ecdsa_sign_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no ECDSA signing: {name} came with library 0.13 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    def eth_message_hash_batch(self, msgs, msg_off, mode="eip191"):
+        """The digest a wallet signs for every ragged message (plume_eth_message_hash_batch): Keccak-256(msg) for mode "keccak256", Keccak-256("\\x19Ethereum Signed
+        Message:\\n" || decimal(len) || msg) for "eip191" (personal_sign).  msgs, msg_off as pack_messages returns them; a mode may also be given as its integer.
+        Returns n x 32 bytes."""
+        fn = self._ecdsa_sign_fn("plume_eth_message_hash_batch")
+        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n = len(msg_off) - 1
+        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
+        out = np.zeros((n, 32), dtype=np.uint8)
+        self._chk(fn(self._ctx, int(ETH_HASH_MODES.get(mode, mode)), n, _ptr(msgs), _ptr(msg_off), _ptr(out)), "plume_eth_message_hash_batch")
+        return out
+
+    def ecdsa_sign_batch(self, hash, sk, aux=None, v27=False, flags=None):
+        """Deterministic ECDSA signatures with a recovery id (plume_ecdsa_sign_batch): RFC 6979 nonces over the digest itself (aux: None, or n x 32 bytes of section 3.6's
+        extra input), always low s.  hash, sk: n x 32 big-endian bytes.  Returns (r, s, v, status): r, s n x 32 bytes, v the parity of R's y behind the low-s flip (0 / 1,
+        or 27 / 28 with v27), status[i] 0 (signed), 2 (sk outside [1, n - 1]), 4 (a degenerate outcome) or 8 (withheld by the self-check); r, s, v are zero unless
+        status is 0.  flags: the raw flag word instead of v27."""
+        fn = self._ecdsa_sign_fn("plume_ecdsa_sign_batch")
+        sk = np.ascontiguousarray(sk, dtype=np.uint8)
+        if sk.size % 32:
+            raise ValueError(f"sk: expected records of 32 bytes, got {sk.size} bytes")
+        n = sk.size // 32
+        hash = _np(hash, 32, n, "hash")
+        aux = None if aux is None else _np(aux, 32, n, "aux")
+        r, s = np.zeros((n, 32), dtype=np.uint8), np.zeros((n, 32), dtype=np.uint8)
+        v, status = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        fl = (ECDSA_SIGN_V27 if v27 else 0) if flags is None else int(flags)
+        self._chk(fn(self._ctx, fl, n, _ptr(hash), _ptr(sk), _ptr(aux), _ptr(r), _ptr(s), _ptr(v), _ptr(status)), "plume_ecdsa_sign_batch")
+        return r, s, v, status
+
     def verify_batch_sec1(self, version, msgs, msg_off, pk33, nullifier33, c, s, r_point33=None, hashed_to_curve_r33=None):
         """verify with 33-byte SEC1-compressed points (decompressed and validated on the GPU)"""
         n = len(msg_off) - 1
@@ -711,6 +758,24 @@ class Engine:
         d = self._dp
         self._chk(fn(self._ctx, ECDSA_LOW_S if low_s else 0, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(hash), d(r), d(s), d(v), d(expect),
                      d(pk), d(address), d(status), C.c_void_p(st)), "plume_ecdsa_recover_batch_device")
+
+    def eth_message_hash_batch_device(self, n, msgs, msg_off, msgs_bytes, hash32, mode="eip191", stream=None):
+        """the device form of eth_message_hash_batch on torch tensors (msg_off: n + 1 uint64 offsets; msgs and hash32 at any byte offset); one kernel on `stream`
+        (None = current stream); does not synchronise"""
+        import torch
+        fn = self._ecdsa_sign_fn("plume_eth_message_hash_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, int(ETH_HASH_MODES.get(mode, mode)), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(hash32), C.c_void_p(st)),
+                  "plume_eth_message_hash_batch_device")
+
+    def ecdsa_sign_batch_device(self, n, hash, sk, aux, r, s, v, status, v27=False, stream=None):
+        """the device form of ecdsa_sign_batch on torch tensors; aux may be None; enqueues on `stream` (None = current stream); does not synchronise"""
+        import torch
+        fn = self._ecdsa_sign_fn("plume_ecdsa_sign_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, ECDSA_SIGN_V27 if v27 else 0, int(n), d(hash), d(sk), d(aux), d(r), d(s), d(v), d(status), C.c_void_p(st)), "plume_ecdsa_sign_batch_device")
 
     def verify_non_zk_batch_device(self, version, n, msgs, msg_off, msgs_bytes, pk, nullifier, s, r_point, hashed_to_curve_r, digest_private, ok, stream=None):
         import torch

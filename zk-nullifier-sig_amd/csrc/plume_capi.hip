@@ -27,6 +27,7 @@
 #include "plume_agg_launch.h"
 #include "plume_capi_internal.h"
 #include "plume_ecdsa.h"
+#include "plume_ecdsa_sign.h"
 #include "plume_host_logic.h"
 #include "plume_keccak.h"
 #include "plume_launch.h"
@@ -284,6 +285,8 @@ extern "C" const char* plume_last_error(void) { return g_err.c_str(); }
 #ifndef PLUME_BUILD_ID
 #define PLUME_BUILD_ID "unknown"
 #endif
+// (the number stays 0.12 with library 0.13's entry points: an existing harness pins the string's beginning -- tests/hostsim/ecdsa_driver.cpp -- so what 0.13 added is told by
+// its symbols, plume_ecdsa_sign_batch and plume_eth_message_hash_batch, as include/plume_hip.h says)
 extern "C" const char* plume_version(void) { return "plume_hip 0.12 gfx950 build=" PLUME_BUILD_ID; }
 
 static void destroy_single(plume_ctx* ctx) {
@@ -1878,12 +1881,12 @@ static int ecdsa_args_ok(int flags, int pk_format, int addr_format, size_t n, co
     return 0;
 }
 static int ecdsa_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s, const uint8_t* v,
-                        const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, hipStream_t st, const EcdsaLaunch* fn) {
+                        const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, hipStream_t st, const EcdsaLaunch* fn, bool continue_timer = false) {
     if (n == 0) return 0;
     if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
     if (int rc = need_gcomb(ctx)) return rc;
-    if (int rc = ws_acquire(ctx, st)) return rc;
-    WsHold hold(ctx, st);
+    if (!continue_timer) { if (int rc = ws_acquire(ctx, st)) return rc; }     // continue_timer: the caller (the ECDSA signer's self-check) holds the workspace already
+    std::unique_ptr<WsHold> hold(continue_timer ? nullptr : new WsHold(ctx, st));
     const std::vector<size_t> cut = sub_batch_bounds(ctx, n);
     const size_t nsub = cut.size() - 1;
     size_t scr_bytes = 0;
@@ -1894,7 +1897,7 @@ static int ecdsa_device(plume_ctx* ctx, int flags, int pk_format, int addr_forma
         return PLUME_ERR_HIP;
     const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
     StageTimer& t = ctx->timer;
-    t.begin(st);
+    if (!continue_timer) t.begin(st);
     for (size_t k = 0; k < nsub; k++) {
         const size_t lo = cut[k], cnt = cut[k + 1] - cut[k];
         EcdsaArgs a;                                                          // the slice [lo, lo + cnt) as a batch of its own: every array and every scratch region starts at the slice
@@ -1914,7 +1917,7 @@ static int ecdsa_device(plume_ctx* ctx, int flags, int pk_format, int addr_forma
         fn->finalize(a, st); t.stage("ecdsa_finalize", st);
     }
     HIPCHK(hipGetLastError());
-    return hold.release();
+    return hold ? hold->release() : 0;
 }
 int plume::capi_ecdsa_recover_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s,
                                      const uint8_t* v, const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, void* stream, const EcdsaLaunch* fn) {
@@ -1963,6 +1966,156 @@ int plume::capi_ecdsa_recover(plume_ctx* ctx, int flags, int pk_format, int addr
     return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
         return ecdsa_host(sh, flags, pk_format, addr_format, hi - lo, hash + 32 * lo, r + 32 * lo, s + 32 * lo, v + lo, expect ? expect + 20 * lo : nullptr,
                           pk ? pk + P * lo : nullptr, address ? address + W * lo : nullptr, status ? status + lo : nullptr, fn);
+    });
+}
+// The message-hash call (plume_capi_internal.h): the ABI lives in plume_eth_hash_capi.hip, the launcher beside the address kernel's.  Like the address call it needs no table and touches no workspace.
+static int eth_hash_args_ok(int mode, size_t n, const void* off, const void* hash, EthHashLaunch fn) {
+    if (mode != PLUME_ETHK_HASH_KECCAK256 && mode != PLUME_ETHK_HASH_EIP191) return fail(PLUME_ERR_ARG, "mode must be 0 or 1");
+    if (!fn) return fail(PLUME_ERR_ARG, "the message-hash kernel is not part of this build");
+    if (n && (!off || !hash)) return fail(PLUME_ERR_ARG, "null array");
+    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
+    return 0;
+}
+static int eth_hash_device(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, uint8_t* hash, hipStream_t st, EthHashLaunch fn) {
+    if (n == 0) return 0;
+    if (!msgs && msgs_bytes) return fail(PLUME_ERR_ARG, "null message buffer");
+    EthHashArgs a; a.mode = mode; a.n = (uint32_t)n; a.msgs = msgs; a.msg_off = msg_off; a.msgs_bytes = msgs ? msgs_bytes : 0; a.hash = hash;
+    ctx->timer.begin(st);
+    fn(a, st); ctx->timer.stage("eth_message_hash", st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int plume::capi_eth_message_hash_device(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, uint8_t* hash32, void* stream,
+                                        EthHashLaunch hash_fn) {
+    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = eth_hash_args_ok(mode, n, msg_off, hash32, hash_fn)) return rc;
+    return eth_hash_device(ctx, mode, n, msgs, msg_off, msgs_bytes, hash32, st_, hash_fn);
+}
+static int eth_hash_host(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, uint8_t* hash, EthHashLaunch fn) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HostSlot& sl = ctx->slot[0];
+    hipStream_t st = ctx->stream;
+    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
+        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
+        if (sl.relbuf.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
+        uint64_t* rel = sl.rel = (uint64_t*)sl.relbuf.p;
+        switch (plume_host::rebase_offsets(msg_off, i0, cnt, rel)) {
+            case 0: break;
+            case 1: return fail(PLUME_ERR_ARG, "msg_off is not non-decreasing");
+            default: return fail(PLUME_ERR_ARG, "message bytes per pass exceed 4 GiB");
+        }
+        const size_t bytes = (size_t)rel[cnt];
+        if (bytes && !msgs) return fail(PLUME_ERR_ARG, "null message buffer");
+        if (sl.msgs.ensure(bytes + 16) || sl.off.ensure((cnt + 1) * 8) || sl.out[0].ensure(32 * cnt)) return PLUME_ERR_HIP;
+        if (bytes) HIPCHK(hipMemcpyAsync(sl.msgs.p, msgs + msg_off[i0], bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(sl.off.p, rel, (cnt + 1) * 8, hipMemcpyHostToDevice, st));
+        int rc = eth_hash_device(ctx, mode, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), bytes, sl.out[0].as<uint8_t>(), st, fn);
+        hipError_t e = hipSuccess;
+        if (!rc) e = hipMemcpyAsync(hash + 32 * i0, sl.out[0].p, 32 * cnt, hipMemcpyDeviceToHost, st);
+        const hipError_t es = hipStreamSynchronize(st);                            // on failure too: the slot's buffers (and the page-locked offsets) are reused by the next call
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(PLUME_ERR_HIP, std::string("digest download: ") + hipGetErrorString(e));
+        if (es != hipSuccess) return fail(PLUME_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
+    }
+    return 0;
+}
+int plume::capi_eth_message_hash(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, uint8_t* hash32, EthHashLaunch hash_fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = eth_hash_args_ok(mode, n, msg_off, hash32, hash_fn)) return rc;
+    if (n == 0) return 0;
+    if (ctx->shards.empty()) return eth_hash_host(ctx, mode, n, msgs, msg_off, hash32, hash_fn);
+    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int { return eth_hash_host(sh, mode, hi - lo, msgs, msg_off + lo, hash32 + 32 * lo, hash_fn); });
+}
+// The ECDSA signer (plume_capi_internal.h): the ABI and the launchers live in plume_ecdsa_sign_capi.hip.  The table of G is the signer's -- the comb, or at level 2 the
+// scanned table -- and the workspace is the signer's too: the nonce buffer, one Jacobian result per item (two with the self-check: sk G), the item flags; the call joins the
+// ws_free chain.  plume_set_sub_batches cuts the call as it cuts an ECDSA recovery (sub_batch_bounds); there is no stage in front of a long multiplication to overlap, so
+// the slices follow one another on the caller's stream.  With plume_set_sign_selfcheck on, finalize writes ctx->scstage, the recover stages (ecdsa_device, on this
+// workspace and this stream) recover a key from the staged (hash, r, s, v), the release kernel writes the caller's arrays and the staging is wiped.
+static int ecdsa_sign_args_ok(int flags, size_t n, const void* hash, const void* sk, const void* r, const void* s, const void* v, const void* status, const EcdsaSignLaunch* fn) {
+    if (flags & ~PLUME_ECDSAK_SIGN_V27) return fail(PLUME_ERR_ARG, "unknown flag bits");
+    if (!fn || !fn->nonce || !fn->gmul || !fn->finalize || !fn->release || !fn->recover) return fail(PLUME_ERR_ARG, "the ECDSA signing kernels are not part of this build");
+    if (n && (!hash || !sk || !r || !s || !v || !status)) return fail(PLUME_ERR_ARG, "null array");
+    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
+    return 0;
+}
+static int ecdsa_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v, uint8_t* status,
+                             hipStream_t st, const EcdsaSignLaunch* fn) {
+    if (n == 0) return 0;
+    if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
+    if (int rc = need_sign_tables(ctx)) return rc;
+    const bool selfcheck = ctx->sign_selfcheck != 0;
+    if (selfcheck) { if (int rc = need_gcomb(ctx)) return rc; }                  // the recover stages' table, built before anything is queued
+    if (int rc = ws_acquire(ctx, st)) return rc;
+    WsHold hold(ctx, st);
+    const std::vector<size_t> cut = sub_batch_bounds(ctx, n);
+    const size_t nsub = cut.size() - 1;
+    const size_t T = selfcheck ? 2 : 1;                                         // points per item
+    constexpr size_t kEcdsaStageBytes = 2 * 32 + 2 * 64 + 3;                         // per item: r, s | sk G, the recovered key | v, status, the recover stages' status -- in that order, the records 16-byte aligned
+    if (ctx->nonce.ensure(32 * n) || ctx->itemflags.ensure(n) || ctx->res.ensure((size_t)PLUME_JAC_WORDS * 4 * T * n) || ctx->resinf.ensure(T * n) ||
+        (selfcheck && ctx->scstage.ensure(kEcdsaStageBytes * n)))
+        return PLUME_ERR_HIP;
+    uint8_t* const stg = ctx->scstage.as<uint8_t>();
+    uint8_t *const g_r = stg, *const g_s = stg + 32 * n, *const g_pk = stg + 64 * n, *const g_rec = stg + 128 * n, *const g_v = stg + 192 * n, *const g_status = stg + 193 * n,
+            *const g_recst = stg + 194 * n;
+    struct StageWipe {                                                          // failure paths only: a call that fails behind finalize still wipes what it staged, in front of ws_free (~WsHold)
+        plume_ctx* ctx; size_t bytes; hipStream_t st;
+        ~StageWipe() { if (bytes) (void)hipMemsetAsync(ctx->scstage.p, 0, bytes, st); }
+    } stage_wipe{ctx, selfcheck ? kEcdsaStageBytes * n : 0, st};
+    StageTimer& t = ctx->timer;
+    t.begin(st);
+    for (size_t k = 0; k < nsub; k++) {
+        const size_t lo = cut[k], cnt = cut[k + 1] - cut[k];
+        EcdsaSignArgs a;                                                        // the slice [lo, lo + cnt) as a batch of its own
+        memset(&a, 0, sizeof a);
+        a.flags = flags; a.uniform = ctx->sign_uniform; a.n = (uint32_t)cnt; a.ntask = (uint32_t)T;
+        a.hash = hash + 32 * lo; a.sk = sk + 32 * lo; a.aux = aux ? aux + 32 * lo : nullptr;
+        a.r = (selfcheck ? g_r : r) + 32 * lo; a.s = (selfcheck ? g_s : s) + 32 * lo; a.v = (selfcheck ? g_v : v) + lo; a.status = (selfcheck ? g_status : status) + lo;
+        a.pkstage = selfcheck ? g_pk + 64 * lo : nullptr;
+        a.k = ctx->nonce.as<uint8_t>() + 32 * lo; a.itemflags = ctx->itemflags.as<uint8_t>() + lo;
+        a.res = ctx->res.as<uint32_t>() + (size_t)PLUME_JAC_WORDS * T * lo; a.resinf = ctx->resinf.as<uint8_t>() + T * lo;
+        a.gcomb = ctx->fixed->gcomb.as<uint32_t>(); a.gscan = ctx->fixed->gscan.as<uint32_t>();
+        fn->nonce(a, st); t.stage("ecdsa_sign_nonce", st);
+        fn->gmul(a, st); t.stage("ecdsa_sign_gmul", st);
+        launch_normalize(a.res, a.resinf, T * cnt, st); t.stage("to_affine", st);
+        fn->finalize(a, st); t.stage("ecdsa_sign_finalize", st);
+    }
+    // the nonces never leave the device; wipe them and the images of k G behind the last kernel that reads them
+    HIPCHK(hipMemsetAsync(ctx->nonce.p, 0, 32 * n, st));
+    HIPCHK(hipMemsetAsync(ctx->res.p, 0, (size_t)PLUME_JAC_WORDS * 4 * T * n, st));
+    HIPCHK(hipGetLastError());
+    if (selfcheck) {
+        if (int rc = ecdsa_device(ctx, PLUME_ECDSAK_LOW_S, PLUME_ETHK_PK_AFFINE64, PLUME_ETHK_ADDR_RAW20, n, hash, g_r, g_s, g_v, nullptr, g_rec, nullptr, g_recst, st, fn->recover, true))
+            return rc;
+        EcdsaSignReleaseArgs ra;
+        ra.n = (uint32_t)n; ra.stage_r = g_r; ra.stage_s = g_s; ra.stage_v = g_v; ra.stage_status = g_status; ra.stage_pk = g_pk; ra.rec_pk = g_rec; ra.rec_status = g_recst;
+        ra.r = r; ra.s = s; ra.v = v; ra.status = status;
+        fn->release(ra, st); t.stage("ecdsa_sign_release", st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(ctx->scstage.p, 0, kEcdsaStageBytes * n, st));        // a withheld s is precisely the value that must not linger
+        stage_wipe.bytes = 0;
+    }
+    return hold.release();
+}
+int plume::capi_ecdsa_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v,
+                                  uint8_t* status, void* stream, const EcdsaSignLaunch* fn) {
+    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = ecdsa_sign_args_ok(flags, n, hash, sk, r, s, v, status, fn)) return rc;
+    return ecdsa_sign_device(ctx, flags, n, hash, sk, aux, r, s, v, status, st_, fn);
+}
+// the host-pointer form: the signer's pipeline (host_call_any: pieces, two lanes, shards; sk and aux staged as secrets and wiped), with no messages to stage
+int plume::capi_ecdsa_sign(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v, uint8_t* status,
+                           const EcdsaSignLaunch* fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = ecdsa_sign_args_ok(flags, n, hash, sk, r, s, v, status, fn)) return rc;
+    if (n == 0) return 0;
+    static const uint8_t no_msgs[16] = {0};
+    const std::vector<uint64_t> no_off(n + 1, 0);                               // every item's message is empty
+    const HostCall call{no_msgs, no_off.data(), {{hash, 32}, {sk, 32, true}, {aux, 32, true}}, {{r, 32}, {s, 32}, {v, 1}, {status, 1}}, false, ctx->host_sign_lanes > 1};
+    return host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return ecdsa_sign_device(on, flags, cnt, sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(), aux ? sl.in[2].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(),
+                                 sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(), sl.out[3].as<uint8_t>(), on->stream, fn);
     });
 }
 // The STRUCTURE half of SecretKey::from_sec1_der for the fixed 109-byte form above (what the wasm layer emits): ok[i] = 1 iff the record has that exact shape and

@@ -1,4 +1,4 @@
-// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_ecdsa_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
+// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_eth_hash_capi.hip, plume_ecdsa_capi.hip, plume_ecdsa_sign_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -74,5 +74,33 @@ __attribute__((visibility("hidden"))) int capi_ecdsa_recover(plume_ctx* ctx, int
 __attribute__((visibility("hidden"))) int capi_ecdsa_recover_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r,
                                                                     const uint8_t* s, const uint8_t* v, const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status,
                                                                     void* stream, const EcdsaLaunch* fn);
+
+// The message-hash call (plume_eth_message_hash_batch*): one kernel on the caller's arrays, no tables and no workspace, like the address call.  The host-pointer form stages
+// chunks of at most plume_set_chunk items (their message bytes and offsets rebased to the chunk) through the context's first slot and splits over the shards of a
+// plume_init_multi context; the device form enqueues on the caller's stream and does not synchronise.
+struct EthHashArgs;
+typedef void (*EthHashLaunch)(const EthHashArgs& a, hipStream_t st);
+__attribute__((visibility("hidden"))) int capi_eth_message_hash(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, uint8_t* hash32,
+                                                                EthHashLaunch hash_fn);
+__attribute__((visibility("hidden"))) int capi_eth_message_hash_device(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes,
+                                                                       uint8_t* hash32, void* stream, EthHashLaunch hash_fn);
+
+// The ECDSA signer (plume_ecdsa_sign_batch*): nonce, the comb, the conversion to affine, finalize; with plume_set_sign_selfcheck on, the recover stages over the staged
+// signatures and the release kernel behind them.  The launchers of its own kernels come in as a hook struct, with the recover stages' hooks beside them; the conversion and
+// the table stage are plume_capi.hip's own.  Workspace waits, plume_set_sub_batches, the chunk limit, the in-flight lanes, the host pipeline (sk and aux staged and wiped)
+// and sharding are those of plume_sign_batch_rfc6979*.  The comb (or, at level 2, the scanned table) is the only fixed table: never the verifier's window table.
+struct EcdsaSignArgs;
+struct EcdsaSignReleaseArgs;
+struct EcdsaSignLaunch {
+    void (*nonce)(const EcdsaSignArgs& a, hipStream_t st);
+    void (*gmul)(const EcdsaSignArgs& a, hipStream_t st);
+    void (*finalize)(const EcdsaSignArgs& a, hipStream_t st);
+    void (*release)(const EcdsaSignReleaseArgs& a, hipStream_t st);
+    const EcdsaLaunch* recover;
+};
+__attribute__((visibility("hidden"))) int capi_ecdsa_sign(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r,
+                                                          uint8_t* s, uint8_t* v, uint8_t* status, const EcdsaSignLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_ecdsa_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux,
+                                                                 uint8_t* r, uint8_t* s, uint8_t* v, uint8_t* status, void* stream, const EcdsaSignLaunch* fn);
 
 }  // namespace plume

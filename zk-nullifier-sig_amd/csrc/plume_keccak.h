@@ -179,4 +179,135 @@ PLUME_HD void eth_address_item(const EthArgs& a, uint32_t i) {
     a.status[i] = (uint8_t)(diff == 0 ? PLUME_ETHK_MATCH : PLUME_ETHK_MISMATCH);
 }
 
+// ------------------------------------------------------------------------------------------------ ragged messages
+// The digest a wallet signs (plume_eth_message_hash_batch, include/plume_hip.h): Keccak-256 of message i = msgs[msg_off[i] .. msg_off[i + 1]) itself (mode 0) or of
+//     "\x19Ethereum Signed Message:\n" || decimal(len) || msg                                    (mode 1, EIP-191 version 0x45: personal_sign)
+// One lane per item (k_eth_message_hash, plume_eth_kernels.hip).  The stream of P prefix bytes, len message bytes and the pad (0x01 ... 0x80, rate 136) is absorbed block
+// by block in a run-time loop; the state only ever sees literal indices, as above:
+//   - a lane of the block that lies wholly inside the message is two aligned 8-byte loads and a funnel shift (the message starts at any byte), when both words lie inside
+//     the msgs buffer; seventeen such tests, unrolled, XOR straight into a[0] .. a[16]
+//   - every other lane that holds anything -- prefix, decimal length, the ragged head and tail of the message, the pad -- is put together byte by byte from selects on the
+//     byte's position (keccak_edge_lane) in ONE run-time loop over the block's lanes, and lands in the state through seventeen selects: there is no byte-indexed array
+// Lanes of a wavefront run different block counts: the loop runs while any lane has a block left (nonce_any's rule, stated here so that this header does not need SHA-256).
+// An item whose offsets msg_span rejects hashes the empty message and never reads msgs.  Every value is public: plain branches.
+#define PLUME_ETHK_HASH_KECCAK256 0    // PLUME_ETH_HASH_* (include/plume_hip.h)
+#define PLUME_ETHK_HASH_EIP191 1
+#define PLUME_KECCAK_RATE 136u
+#define PLUME_EIP191_PREFIX_LEN 26u
+
+struct EthHashArgs {
+    int mode;                         // PLUME_ETHK_HASH_*
+    uint32_t n;
+    const uint8_t* msgs; const uint64_t* msg_off;     // n + 1 offsets
+    uint64_t msgs_bytes;
+    uint8_t* hash;                    // 32 bytes per item, at any byte offset
+};
+
+PLUME_HD bool keccak_any(bool p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __any(p ? 1 : 0) != 0;
+#else
+    return p;
+#endif
+}
+
+// the number of decimal digits of v (1 for 0)
+PLUME_HD uint32_t dec_digits(uint32_t v) {
+    uint32_t nd = 1, lim = 10;
+    PLUME_UNROLL for (int k = 0; k < 9; k++) { nd += v >= lim ? 1u : 0u; lim *= 10u; }   // 10^1 .. 10^9: the last product still fits 32 bits
+    return nd;
+}
+// ASCII digit d (0 = the most significant) of v, which has nd digits
+PLUME_HD uint32_t dec_digit_at(uint32_t v, uint32_t nd, uint32_t d) {
+    const uint32_t e = nd - 1u - d;
+    uint32_t pw = 1u, p = 1u;
+    PLUME_UNROLL for (uint32_t k = 1; k < 10; k++) { p *= 10u; pw = e == k ? p : pw; }
+    return 0x30u + (v / pw) % 10u;
+}
+// eight bytes of "\x19Ethereum Signed Message:\n" from byte 8 q on, little-endian; zero past byte 25
+PLUME_HD uint64_t eip191_prefix_lane(uint32_t q) {
+    return q == 0 ? 0x7565726568744519ull : q == 1 ? 0x64656e676953206dull : q == 2 ? 0x6567617373654d20ull : q == 3 ? 0x0a3aull : 0ull;
+}
+
+// what one item absorbs: P prefix bytes (the fixed 26 and nd digits), len message bytes, the pad up to `last`, the final byte of the final block
+struct keccak_stream {
+    const uint8_t* msg;
+    uint32_t len, nd, P;
+    uint64_t total, last;             // P + len; 136 * blocks - 1
+};
+// byte `pos` of the stream
+PLUME_HD uint32_t keccak_stream_byte(const keccak_stream& s, uint64_t pos) {
+    if (pos < s.P) {
+        const uint32_t p = (uint32_t)pos;
+        if (p < PLUME_EIP191_PREFIX_LEN) return (uint32_t)(eip191_prefix_lane(p >> 3) >> (8 * (p & 7))) & 0xFFu;
+        return dec_digit_at(s.len, s.nd, p - PLUME_EIP191_PREFIX_LEN);
+    }
+    if (pos < s.total) return s.msg[pos - s.P];
+    return (pos == s.total ? 0x01u : 0u) | (pos == s.last ? 0x80u : 0u);
+}
+// the lane of the stream that starts at byte pos, for a lane the aligned loads do not serve
+PLUME_HD uint64_t keccak_edge_lane(const keccak_stream& s, uint64_t pos) {
+    if (pos + 8 <= (s.P < 24u ? s.P : 24u)) return eip191_prefix_lane((uint32_t)pos >> 3);      // wholly inside the fixed text
+    uint64_t v = 0;
+    PLUME_NOUNROLL for (uint32_t b = 0; b < 8; b++) v |= (uint64_t)keccak_stream_byte(s, pos + b) << (8 * b);
+    return v;
+}
+// eight message bytes at p (any alignment) by aligned loads: ok = false, and no load, unless the words that hold them lie inside [lo, hi)
+PLUME_HD uint64_t keccak_load_lane(bool& ok, const uint8_t* p, const uint8_t* lo, const uint8_t* hi) {
+    const uintptr_t a = (uintptr_t)p, w0 = a & ~(uintptr_t)7;
+    const uint32_t sh = 8u * (uint32_t)(a & 7u);
+    ok = w0 >= (uintptr_t)lo && w0 + (sh ? 16u : 8u) <= (uintptr_t)hi;
+    if (!ok) return 0;
+    const uint64_t x = *(const uint64_t*)w0;
+    if (sh == 0) return x;
+    const uint64_t y = *(const uint64_t*)(w0 + 8);
+    return (x >> sh) | (y << (64u - sh));
+}
+
+// Keccak-256 of item i's stream: the digest as eight little-endian words in memory order
+PLUME_HD void eth_message_digest(uint32_t dg[8], const EthHashArgs& a, uint32_t i) {
+    uint64_t o0; uint32_t len;
+    (void)msg_span(o0, len, a.msg_off, i, a.msgs_bytes);                                 // rejected offsets: the empty message, msgs never read
+    keccak_stream s;
+    s.msg = a.msgs + o0; s.len = len;
+    s.nd = dec_digits(len);
+    s.P = a.mode == PLUME_ETHK_HASH_EIP191 ? PLUME_EIP191_PREFIX_LEN + s.nd : 0u;
+    s.total = (uint64_t)s.P + len;
+    const uint64_t nblk = s.total / PLUME_KECCAK_RATE + 1;                               // the pad always adds a byte
+    s.last = nblk * PLUME_KECCAK_RATE - 1;
+    const uint8_t* const lo = a.msgs; const uint8_t* const hi = a.msgs + a.msgs_bytes;
+    uint64_t st[25];
+    PLUME_UNROLL for (int k = 0; k < 25; k++) st[k] = 0;
+    PLUME_NOUNROLL for (uint64_t blk = 0; keccak_any(blk < nblk); blk++) {
+        if (blk < nblk) {
+            const uint64_t base = blk * PLUME_KECCAK_RATE;
+            uint32_t edge = 0;                                                           // bit j: lane j is not served by the aligned loads
+            PLUME_UNROLL for (int j = 0; j < 17; j++) {
+                const uint64_t pos = base + 8u * (uint32_t)j;
+                bool ok = false;
+                uint64_t v = 0;
+                if (pos >= s.P && pos + 8 <= s.total) v = keccak_load_lane(ok, s.msg + (pos - s.P), lo, hi);
+                st[j] ^= v;
+                edge |= ok ? 0u : 1u << j;
+            }
+            PLUME_NOUNROLL for (uint32_t j = 0; j < 17; j++) {
+                const uint64_t pos = base + 8u * j;
+                if (!((edge >> j) & 1u) || (pos > s.total && j != 16u)) continue;         // served, or nothing but zero bytes (lane 16 may hold the last pad byte)
+                const uint64_t v = keccak_edge_lane(s, pos);
+                PLUME_UNROLL for (int k = 0; k < 17; k++) st[k] ^= (uint32_t)k == j ? v : 0ull;
+            }
+            keccak_f1600(st);
+        }
+    }
+    PLUME_UNROLL for (int k = 0; k < 8; k++) dg[k] = (uint32_t)(st[k >> 1] >> (32 * (k & 1)));
+}
+
+// lane i of k_eth_message_hash
+PLUME_HD void eth_message_hash_item(const EthHashArgs& a, uint32_t i) {
+    uint32_t r[16];
+    PLUME_UNROLL for (int k = 8; k < 16; k++) r[k] = 0u;
+    eth_message_digest(r, a, i);
+    recover_store<32>(a.hash + 32 * (size_t)i, r);
+}
+
 }  // namespace plume

@@ -330,6 +330,49 @@ def ecdsa_recover_address(hash32: bytes, r: bytes, s: bytes, v: int, engine: Opt
     return _ecdsa_recover("ecdsa_recover_address", ("address", "status"), hash32, r, s, v, engine)[1][0].tobytes()
 
 
+def _b32(what: str, name: str, b) -> bytes:
+    b = bytes(b)
+    if len(b) != 32:
+        raise ValueError(f"{what}: {name} is 32 bytes")
+    return b
+
+
+def ecdsa_sign(sk, hash32: bytes, aux: Optional[bytes] = None, engine: Optional[Engine] = None, v27: bool = False) -> Tuple[bytes, bytes, int]:
+    """A deterministic ECDSA signature (r, s, v) by sk over the 32-byte digest hash32, made on the GPU (include/plume_hip.h, plume_ecdsa_sign_batch): the RFC 6979 nonce over
+    the digest itself -- byte-identical to geth, ethers and libsecp256k1 -- hedged with the 32 bytes of aux when given; always low s; v 0 / 1, or 27 / 28 with v27.  sk: a
+    SecretKey or 32 big-endian bytes.  Raises SignatureError when sk is outside [1, n - 1] or the outcome is degenerate (status 2 / 4), PlumeSelfCheckError when the
+    self-check withheld the signature."""
+    sk32 = _b32("ecdsa_sign", "sk", sk.to_bytes() if isinstance(sk, SecretKey) else sk)
+    a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
+    r, s, v, status = (engine or default_engine()).ecdsa_sign_batch(a(_b32("ecdsa_sign", "hash32", hash32)), a(sk32), None if aux is None else a(_b32("ecdsa_sign", "aux", aux)),
+                                                                    v27=v27)
+    st = int(status[0])
+    if st == 8:
+        raise PlumeSelfCheckError("ecdsa_sign: the signature did not recover the signer's key and was withheld")
+    if st:
+        raise SignatureError(f"ecdsa_sign: no signature (status {st}: {'sk outside [1, n - 1]' if st == 2 else 'a degenerate outcome'})")
+    return r[0].tobytes(), s[0].tobytes(), int(v[0])
+
+
+def personal_sign(sk, msg: bytes, aux: Optional[bytes] = None, engine: Optional[Engine] = None) -> bytes:
+    """A wallet's personal_sign: the 65 bytes r || s || v (v = 27 / 28) of ecdsa_sign over the EIP-191 digest Keccak-256("\\x19Ethereum Signed Message:\\n" || len || msg),
+    digest and signature both made on the GPU"""
+    eng = engine or default_engine()
+    msgs, off = pack_messages([bytes(msg)])
+    r, s, v = ecdsa_sign(sk, eng.eth_message_hash_batch(msgs, off, "eip191")[0].tobytes(), aux, eng, v27=True)
+    return r + s + bytes([v])
+
+
+def personal_recover(msg: bytes, sig65: bytes, engine: Optional[Engine] = None) -> Tuple[AffinePoint, bytes]:
+    """The public key and the 20-byte address that personal_sign'ed msg: the EIP-191 digest, then ecdsa_recover.  sig65: r || s || v with v 0, 1, 27 or 28"""
+    sig65 = bytes(sig65)
+    if len(sig65) != 65:
+        raise ValueError("personal_recover: sig65 is the 65 bytes r || s || v")
+    eng = engine or default_engine()
+    msgs, off = pack_messages([bytes(msg)])
+    return ecdsa_recover(eng.eth_message_hash_batch(msgs, off, "eip191")[0].tobytes(), sig65[:32], sig65[32:64], sig65[64], eng)
+
+
 def circuit_inputs(sig: "PlumeSignature", engine: Optional[Engine] = None) -> dict:
     """All inputs of the circom verifier (circuits/circom/verify_nullifier.circom:14-31; test/v1.test.ts:68-78) for one signature, as lists of four 64-bit
     little-endian registers (circuits/circom/utils.ts:11-17): c, s, pk, nullifier from the signature, q{0,1}_x_mapped / q{0,1}_y_mapped from the GPU hash_to_curve
