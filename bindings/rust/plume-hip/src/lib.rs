@@ -94,6 +94,9 @@ pub const PLUME_ECDSA_SIGN_V27: c_int = 1;
 pub const PLUME_ETH_HASH_KECCAK256: c_int = 0;
 pub const PLUME_ETH_HASH_EIP191: c_int = 1;
 pub const PLUME_ECDSA_LOW_S: c_int = 1;
+/// `plume_eth_tx_parse_batch`: the status of an item
+pub const PLUME_ETH_TX_OK: u8 = 1;
+pub const PLUME_ETH_TX_INVALID: u8 = 3;
 
 #[link(name = "plume_hip")]
 extern "C" {
@@ -162,6 +165,14 @@ extern "C" {
         status: *mut u8) -> c_int;
     fn plume_ecdsa_sign_batch_device(ctx: *mut plume_ctx, flags: c_int, n: usize, hash: *const u8, sk: *const u8, aux: *const u8, r: *mut u8, s: *mut u8, v: *mut u8,
         status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_eth_tx_parse_batch(ctx: *mut plume_ctx, n: usize, txs: *const u8, tx_off: *const u64, hash32: *mut u8, r: *mut u8, s: *mut u8, v: *mut u8, chain_id: *mut u64,
+        tx_type: *mut u8, status: *mut u8) -> c_int;
+    fn plume_eth_tx_parse_batch_device(ctx: *mut plume_ctx, n: usize, txs: *const u8, tx_off: *const u64, txs_bytes: usize, hash32: *mut u8, r: *mut u8, s: *mut u8, v: *mut u8,
+        chain_id: *mut u64, tx_type: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_eth_tx_sender_batch(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, txs: *const u8, tx_off: *const u64, expect: *const u8,
+        pk: *mut u8, address: *mut u8, chain_id: *mut u64, tx_type: *mut u8, status: *mut u8) -> c_int;
+    fn plume_eth_tx_sender_batch_device(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, txs: *const u8, tx_off: *const u64, txs_bytes: usize,
+        expect: *const u8, pk: *mut u8, address: *mut u8, chain_id: *mut u64, tx_type: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -332,6 +343,39 @@ impl HipEngine {
         let (mut r, mut s) = ([0u8; 32], [0u8; 32]);
         r.copy_from_slice(&sig65[..32]); s.copy_from_slice(&sig65[32..64]);
         self.ecdsa_recover(&self.eth_message_hash(msg)?, &r, &s, sig65[64])
+    }
+
+    /// The 32 bytes the sender of one raw signed transaction signed (`plume_eth_tx_parse_batch`): legacy (unprotected or EIP-155) and the typed envelopes 01 - 04.  An
+    /// error for an item that is no such transaction.  A sender recovery, not a consensus decoder: inner fields are not validated.
+    pub fn tx_signing_hash(&self, raw: &[u8]) -> Result<[u8; 32], HipError> {
+        let off = [0u64, raw.len() as u64];
+        let (mut h, mut r, mut s, mut v, mut status) = ([0u8; 32], [0u8; 32], [0u8; 32], [0u8; 1], [0u8; 1]);
+        let rc = unsafe { plume_eth_tx_parse_batch(self.0, 1, raw.as_ptr(), off.as_ptr(), h.as_mut_ptr(), r.as_mut_ptr(), s.as_mut_ptr(), v.as_mut_ptr(), std::ptr::null_mut(),
+                                                   std::ptr::null_mut(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        if status[0] != PLUME_ETH_TX_OK { return Err(HipError("tx_signing_hash: not a signed transaction of a known kind".to_string())); }
+        Ok(h)
+    }
+    /// The public key and the address of the sender of one raw signed transaction (`plume_eth_tx_sender_batch`), with the EIP-2 low-`s` rule.  An error when there is no
+    /// sender: the framing is broken or the signature recovers no key.
+    pub fn tx_sender(&self, raw: &[u8]) -> Result<(AffinePoint, [u8; 20]), HipError> {
+        let off = [0u64, raw.len() as u64];
+        let (mut pk, mut addr, mut status) = ([0u8; 64], [0u8; 20], [0u8; 1]);
+        let rc = unsafe { plume_eth_tx_sender_batch(self.0, PLUME_ECDSA_LOW_S, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, raw.as_ptr(), off.as_ptr(), std::ptr::null(),
+                                                    pk.as_mut_ptr(), addr.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        if status[0] == PLUME_ECDSA_INVALID { return Err(HipError("tx_sender: no sender".to_string())); }
+        Ok((get_point(&pk), addr))
+    }
+    /// `tx_sender` for callers that want the 20 address bytes only.
+    pub fn tx_sender_address(&self, raw: &[u8]) -> Result<[u8; 20], HipError> {
+        let off = [0u64, raw.len() as u64];
+        let (mut addr, mut status) = ([0u8; 20], [0u8; 1]);
+        let rc = unsafe { plume_eth_tx_sender_batch(self.0, PLUME_ECDSA_LOW_S, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, raw.as_ptr(), off.as_ptr(), std::ptr::null(),
+                                                    std::ptr::null_mut(), addr.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        if status[0] == PLUME_ECDSA_INVALID { return Err(HipError("tx_sender_address: no sender".to_string())); }
+        Ok(addr)
     }
 
     /// Aggregate pre-filter (no reference counterpart; include/plume_hip.h `plume_aggregate_check`): `Ok(true)` iff every V1 signature of the batch would

@@ -406,6 +406,40 @@ inline std::pair<AffinePoint, std::array<uint8_t, 20>> personal_recover(const ui
     return ecdsa_recover(eth_message_hash(msg, len, eng), r, s, sig65[64], eng);
 }
 
+// The senders of raw signed transactions (plume_hip.h plume_eth_tx_parse_batch / plume_eth_tx_sender_batch): legacy (unprotected or EIP-155) and the typed envelopes 01 - 04,
+// framed, hashed and recovered on the GPU.  A sender recovery, not a consensus decoder: inner fields are not validated.  tx_signing_hash gives the 32 bytes the sender signed
+// and throws SignatureError for an item that is no such transaction; tx_sender gives the public key and the 20-byte address (low_s: the EIP-2 rule, right for everything
+// after Homestead) and throws SignatureError when there is no sender -- the framing is broken or the signature recovers no key; tx_sender_address is for callers that want
+// the 20 bytes only.
+inline Bytes32 tx_signing_hash(const uint8_t* raw, size_t len, Engine& eng = Engine::shared()) {
+    const uint64_t off[2] = {0, (uint64_t)len};
+    Bytes32 h{}, r{}, s{};
+    uint8_t v = 0, st = 0xFF;
+    plume_hip::check(plume_eth_tx_parse_batch(eng.ctx(), 1, raw, off, h.data(), r.data(), s.data(), &v, nullptr, nullptr, &st), "plume_eth_tx_parse_batch");
+    if (st != PLUME_ETH_TX_OK) throw SignatureError();
+    return h;
+}
+inline std::pair<AffinePoint, std::array<uint8_t, 20>> tx_sender(const uint8_t* raw, size_t len, Engine& eng = Engine::shared(), bool low_s = true) {
+    const uint64_t off[2] = {0, (uint64_t)len};
+    uint8_t pk[64], st = 0xFF;
+    std::array<uint8_t, 20> addr{};
+    plume_hip::check(plume_eth_tx_sender_batch(eng.ctx(), low_s ? PLUME_ECDSA_LOW_S : 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, raw, off, nullptr, pk, addr.data(), nullptr,
+                                               nullptr, &st),
+                     "plume_eth_tx_sender_batch");
+    if (st == PLUME_ECDSA_INVALID) throw SignatureError();
+    return {AffinePoint::from_bytes64(pk), addr};
+}
+inline std::array<uint8_t, 20> tx_sender_address(const uint8_t* raw, size_t len, Engine& eng = Engine::shared(), bool low_s = true) {
+    const uint64_t off[2] = {0, (uint64_t)len};
+    uint8_t st = 0xFF;
+    std::array<uint8_t, 20> addr{};
+    plume_hip::check(plume_eth_tx_sender_batch(eng.ctx(), low_s ? PLUME_ECDSA_LOW_S : 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, raw, off, nullptr, nullptr, addr.data(),
+                                               nullptr, nullptr, &st),
+                     "plume_eth_tx_sender_batch");
+    if (st == PLUME_ECDSA_INVALID) throw SignatureError();
+    return addr;
+}
+
 // rust-k256/src/randomizedsigner.rs:25-41: a borrowed secret key and the variant
 class PlumeSigner {
   public:

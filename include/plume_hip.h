@@ -76,7 +76,8 @@ void plume_destroy(plume_ctx* ctx);
 /* Last error text of this thread (valid until the next failing call on the thread). */
 const char* plume_last_error(void);
 /* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  The number in the string stays 0.12 for library 0.13: callers
- * that need the 0.13 entry points look for the symbols (dlsym / getattr), as zk-nullifier-sig_amd/capi.py does.  0.13: deterministic ECDSA signatures with a recovery id
+ * that need the 0.13 or 0.14 entry points look for the symbols (dlsym / getattr), as zk-nullifier-sig_amd/capi.py does.  0.14: the senders of raw Ethereum transactions
+ * (plume_eth_tx_parse_batch*, plume_eth_tx_sender_batch*); 0.13: deterministic ECDSA signatures with a recovery id
  * (plume_ecdsa_sign_batch*) and the digest a wallet signs (plume_eth_message_hash_batch*: Keccak-256 of ragged messages, EIP-191); 0.12: public keys and addresses from
  * ECDSA signatures (plume_ecdsa_recover_batch*: ecrecover); 0.11: Ethereum addresses of public keys (plume_eth_address_batch*: Keccak-256);
  * 0.10: point recovery (plume_recover_batch*: r_point, hashed_to_curve_r and hashed_to_curve from pk, nullifier, c, s);
@@ -579,6 +580,53 @@ int plume_ecdsa_sign_batch(plume_ctx* ctx, int flags, size_t n, const uint8_t* h
                            uint8_t* status);
 int plume_ecdsa_sign_batch_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v,
                                   uint8_t* status, void* stream);
+
+/* ---- the senders of raw Ethereum transactions  (library 0.14) ----------------------------------------------------
+ * An account publishes its key in the signatures it makes, and by far the most of those are transactions.  These calls take signed transactions as they travel on the
+ * wire -- item i is txs[tx_off[i] .. tx_off[i + 1]), n + 1 offsets as everywhere else, item lengths below 2^32 -- and give what plume_ecdsa_recover_batch takes (parse)
+ * or the sender itself (sender).  THIS IS A SENDER RECOVERY, NOT A CONSENSUS DECODER: the envelope, the top-level framing and the signature fields are checked; the
+ * contents of every other field, the nested access, blob-hash and authorization lists included, are skipped by their header and copied verbatim into the hash.  A
+ * transaction a node accepts gets the same sender here; one a node rejects for an inner field may still get one.
+ *   RLP       first byte 00-7f: a one-byte string, the byte itself; 80-b7: a string of b - 0x80 bytes; b8-bf: b - 0xb7 big-endian length bytes, then the string; c0-f7: a
+ *             list with a payload of b - 0xc0 bytes; f8-ff: a list with b - 0xf7 length bytes.  Canonical: a one-byte string below 0x80 uses the single-byte form, the long
+ *             form only serves lengths above 55, length bytes have no leading zero.  A canonical integer is a string without a leading zero byte; zero is the empty string.
+ *   envelope  first byte >= 0xc0: legacy, tx_type 0, one list that covers the item exactly, 9 items (nonce, gasPrice, gasLimit, to, value, data, v, r, s).  First byte 01,
+ *             02, 03, 04 (EIP-2930, EIP-1559, EIP-4844 in its canonical form, EIP-7702): tx_type is that byte, the rest is one list that covers it exactly, with 11, 12, 14,
+ *             13 items, the first chainId, the last three yParity, r, s.  Anything else (the empty item, 00, 05-7f, 80-bf) is invalid, and so is the EIP-4844 network
+ *             wrapper, by its item count.
+ *   framing   the outer header and every top-level header canonical; every item inside the payload; the items tile the payload exactly, with the exact count; v / yParity,
+ *             r, s and a typed chainId canonical integers; r and s at most 32 bytes; legacy v and typed chainId at most 8 bytes; yParity 0 or 1.
+ *   v         legacy: 27 or 28 -> parity v - 27, chain_id 0 (unprotected); v >= 37 -> parity (v - 35) & 1, chain_id (v - 35) >> 1 (1 .. 2^63 - 18); any other value, 35
+ *             and 36 included, is invalid.  Typed: the parity is yParity, chain_id the first field (below 2^64).
+ *   hash32    with body = the input from the first top-level item to the start of v / yParity and list(x) = the canonical list header of len(x), then x:
+ *             Keccak-256(list(body)) for an unprotected legacy item, Keccak-256(list(body || rlp_int(chain_id) || 80 80)) under EIP-155, Keccak-256(type || list(body))
+ *             for a typed one.
+ *   r, s      32 big-endian bytes, left-padded;  v: one byte, 0 or 1;  chain_id: uint64_t;  tx_type: one byte.
+ *   status    PLUME_ETH_TX_OK, or PLUME_ETH_TX_INVALID: the item breaks a rule above and EVERY record of it is zero.  In the device forms an item whose offsets decrease or
+ *             reach past txs_bytes is invalid and never reads txs.
+ * 1 <= r, s < n, the low-s rule and "no point with x = r" are NOT checked by the parse: they belong to the recover stages.  The transaction id is Keccak-256 of the raw
+ * item: plume_eth_message_hash_batch with PLUME_ETH_HASH_KECCAK256 over the same txs / tx_off gives it, so there is no output for it here.
+ * plume_eth_tx_parse_batch: hash32, r, s and v are required, chain_id, tx_type and status optional.  No table, no workspace.  The host form routes exactly like
+ * plume_eth_message_hash_batch (pieces of at most plume_set_chunk items, the shards of a plume_init_multi context, decreasing offsets return PLUME_ERR_ARG); the device form
+ * is ONE kernel (k_eth_tx_parse) on `stream` with no synchronisation.  With stage timing on the stage is "eth_tx_parse".
+ * plume_eth_tx_sender_batch: k_eth_tx_parse into staging the context owns, then the unchanged stages of plume_ecdsa_recover_batch on the staged (hash, r, s, v).  flags,
+ * pk_format, addr_format, expect, pk, address and status (PLUME_ECDSA_MATCH / MISMATCH / INVALID) mean what they mean there; PLUME_ECDSA_LOW_S is the right setting for
+ * anything after Homestead.  An item invalid in the framing stages r = 0, so it leaves the recover stages invalid with zero records.  chain_id and tx_type (optional) report
+ * the FRAMING: they are zero only for framing-invalid items, and are written as parsed for an item whose signature then fails to recover.  Routing, the workspace event,
+ * plume_set_sub_batches and the chunk limit of the device form are those of plume_ecdsa_recover_batch*.  With stage timing on the stages are "eth_tx_parse" followed by the
+ * five recover stages.  The call builds the comb of G on first use and never the 1 GiB window table.
+ * Both: n = 0 is a successful no-op; unknown flags or formats return PLUME_ERR_ARG; the arrays may sit at any byte offset (tx_off and chain_id: 8-byte aligned);
+ * everything is public data. */
+#define PLUME_ETH_TX_OK      1
+#define PLUME_ETH_TX_INVALID 3
+int plume_eth_tx_parse_batch(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
+                             uint8_t* tx_type, uint8_t* status);
+int plume_eth_tx_parse_batch_device(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, uint8_t* hash32, uint8_t* r, uint8_t* s,
+                                    uint8_t* v, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream);
+int plume_eth_tx_sender_batch(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, const uint8_t* expect,
+                              uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status);
+int plume_eth_tx_sender_batch_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes,
+                                     const uint8_t* expect, uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream);
 
 /* ---- persistent nullifier set: reject repeats across batches  (library 0.7) ----------------------------------
  * A consumer that verifies a STREAM of batches (a vote tally, a claim relayer, a rate limiter) must reject a nullifier it accepted any number of

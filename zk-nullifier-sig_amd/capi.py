@@ -158,6 +158,12 @@ def _load():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
+    # the senders of raw transactions (library 0.14; Engine.eth_tx_parse_batch* / eth_tx_sender_batch* raise PlumeHipError on an older build)
+    for name, args in (("plume_eth_tx_parse_batch", [vp, sz] + [vp] * 9), ("plume_eth_tx_parse_batch_device", [vp, sz, vp, vp, sz] + [vp] * 8),
+                       ("plume_eth_tx_sender_batch", [vp, i, i, i, sz] + [vp] * 8), ("plume_eth_tx_sender_batch_device", [vp, i, i, i, sz, vp, vp, sz] + [vp] * 7)):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
     _lib = lib
     # (the 0.13 entry points are told by their symbols: plume_version() still begins "plume_hip 0.12")
     if (_version(lib) < (0, 12) or getattr(lib, "plume_ecdsa_sign_batch", None) is None) and not os.environ.get("PLUME_HIP_LIB"):
@@ -178,7 +184,8 @@ def exported_symbols():
             "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device", "plume_sign_batch_rfc6979", "plume_sign_batch_rfc6979_device",
             "plume_set_sign_selfcheck", "plume_get_sign_selfcheck", "plume_recover_batch", "plume_recover_batch_device",
             "plume_eth_address_batch", "plume_eth_address_batch_device", "plume_ecdsa_recover_batch", "plume_ecdsa_recover_batch_device",
-            "plume_eth_message_hash_batch", "plume_eth_message_hash_batch_device", "plume_ecdsa_sign_batch", "plume_ecdsa_sign_batch_device"]
+            "plume_eth_message_hash_batch", "plume_eth_message_hash_batch_device", "plume_ecdsa_sign_batch", "plume_ecdsa_sign_batch_device",
+            "plume_eth_tx_parse_batch", "plume_eth_tx_parse_batch_device", "plume_eth_tx_sender_batch", "plume_eth_tx_sender_batch_device"]
 
 
 def pack_messages(msgs):
@@ -216,6 +223,8 @@ ECDSA_LOW_S = 1
 # plume_eth_message_hash_batch (include/plume_hip.h): what is hashed;  plume_ecdsa_sign_batch: the flag bit (the status of an item is the signer's: 0, 2, 4, 8)
 ETH_HASH_MODES = {"keccak256": 0, "eip191": 1}
 ECDSA_SIGN_V27 = 1
+# plume_eth_tx_parse_batch (include/plume_hip.h): the status of an item (plume_eth_tx_sender_batch reports the recovery's: ECDSA_*)
+ETH_TX_OK, ETH_TX_INVALID = 1, 3
 
 
 def parse_aggregate_record(rec):
@@ -579,6 +588,47 @@ class Engine:
         self._chk(fn(self._ctx, fl, n, _ptr(hash), _ptr(sk), _ptr(aux), _ptr(r), _ptr(s), _ptr(v), _ptr(status)), "plume_ecdsa_sign_batch")
         return r, s, v, status
 
+    def _eth_tx_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no transaction parsing: {name} came with library 0.14 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    def eth_tx_parse_batch(self, txs, tx_off):
+        """What plume_ecdsa_recover_batch takes, from raw signed transactions (plume_eth_tx_parse_batch): legacy (unprotected or EIP-155) and the typed envelopes 01 - 04.
+        txs, tx_off as pack_messages returns them.  Returns a dict: hash (n x 32: what the sender signed), r, s (n x 32 big-endian), v (n: the parity, 0 or 1), chain_id
+        (n uint64; 0 for an unprotected legacy item), tx_type (n) and status (n: ETH_TX_OK or ETH_TX_INVALID, every record of an invalid item being zero).  A sender
+        recovery, not a consensus decoder: fields other than the envelope and the signature are not inspected.  The transaction id is
+        eth_message_hash_batch(txs, tx_off, "keccak256")."""
+        fn = self._eth_tx_fn("plume_eth_tx_parse_batch")
+        tx_off = np.ascontiguousarray(tx_off, dtype=np.uint64)
+        n = len(tx_off) - 1
+        txs = np.ascontiguousarray(txs, dtype=np.uint8)
+        out = {"hash": np.zeros((n, 32), np.uint8), "r": np.zeros((n, 32), np.uint8), "s": np.zeros((n, 32), np.uint8), "v": np.zeros(n, np.uint8),
+               "chain_id": np.zeros(n, np.uint64), "tx_type": np.zeros(n, np.uint8), "status": np.zeros(n, np.uint8)}
+        self._chk(fn(self._ctx, n, _ptr(txs), _ptr(tx_off), *(_ptr(out[k]) for k in ("hash", "r", "s", "v", "chain_id", "tx_type", "status"))), "plume_eth_tx_parse_batch")
+        return out
+
+    def eth_tx_sender_batch(self, txs, tx_off, expect=None, pk_format="affine64", addr_format="raw20", low_s=True, want=("pk", "address", "status")):
+        """The sender of every raw signed transaction (plume_eth_tx_sender_batch): eth_tx_parse_batch into staging the context owns, then the stages of
+        ecdsa_recover_batch.  expect, the formats, low_s (on by default: the rule for everything after Homestead) and `want` are that call's.  Returns (pk, address,
+        status, chain_id, tx_type): status[i] is ECDSA_MATCH, ECDSA_MISMATCH or ECDSA_INVALID (the framing or the signature: zero records); chain_id and tx_type report
+        the framing and are zero only for an item invalid there."""
+        fn = self._eth_tx_fn("plume_eth_tx_sender_batch")
+        pf, P = ETH_PK_FORMATS[pk_format]
+        af, W = ETH_ADDR_FORMATS[addr_format]
+        tx_off = np.ascontiguousarray(tx_off, dtype=np.uint64)
+        n = len(tx_off) - 1
+        txs = np.ascontiguousarray(txs, dtype=np.uint8)
+        expect = None if expect is None else _np(expect, 20, n, "expect")
+        pk = np.zeros((n, P), dtype=np.uint8) if "pk" in want else None
+        address = np.zeros((n, W), dtype=np.uint8) if "address" in want else None
+        status = np.zeros(n, dtype=np.uint8) if "status" in want else None
+        chain_id, tx_type = np.zeros(n, np.uint64), np.zeros(n, np.uint8)
+        self._chk(fn(self._ctx, ECDSA_LOW_S if low_s else 0, pf, af, n, _ptr(txs), _ptr(tx_off), _ptr(expect), _ptr(pk), _ptr(address), _ptr(chain_id), _ptr(tx_type),
+                     _ptr(status)), "plume_eth_tx_sender_batch")
+        return pk, address, status, chain_id, tx_type
+
     def verify_batch_sec1(self, version, msgs, msg_off, pk33, nullifier33, c, s, r_point33=None, hashed_to_curve_r33=None):
         """verify with 33-byte SEC1-compressed points (decompressed and validated on the GPU)"""
         n = len(msg_off) - 1
@@ -768,6 +818,27 @@ class Engine:
         d = self._dp
         self._chk(fn(self._ctx, int(ETH_HASH_MODES.get(mode, mode)), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(hash32), C.c_void_p(st)),
                   "plume_eth_message_hash_batch_device")
+
+    def eth_tx_parse_batch_device(self, n, txs, tx_off, txs_bytes, hash32, r, s, v, chain_id=None, tx_type=None, status=None, stream=None):
+        """the device form of eth_tx_parse_batch on torch tensors (tx_off: n + 1 uint64 offsets; chain_id: n 8-byte words; the byte arrays at any byte offset; chain_id,
+        tx_type and status may be None); one kernel on `stream` (None = current stream); does not synchronise"""
+        import torch
+        fn = self._eth_tx_fn("plume_eth_tx_parse_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, int(n), d(txs), d(tx_off), int(txs_bytes), d(hash32), d(r), d(s), d(v), d(chain_id), d(tx_type), d(status), C.c_void_p(st)),
+                  "plume_eth_tx_parse_batch_device")
+
+    def eth_tx_sender_batch_device(self, n, txs, tx_off, txs_bytes, expect, pk, address, chain_id, tx_type, status, pk_format="affine64", addr_format="raw20", low_s=True,
+                                   stream=None):
+        """the device form of eth_tx_sender_batch on torch tensors; expect, chain_id and tx_type may be None, and any two of pk, address and status; enqueues on `stream`
+        (None = current stream); does not synchronise"""
+        import torch
+        fn = self._eth_tx_fn("plume_eth_tx_sender_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, ECDSA_LOW_S if low_s else 0, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(txs), d(tx_off), int(txs_bytes),
+                     d(expect), d(pk), d(address), d(chain_id), d(tx_type), d(status), C.c_void_p(st)), "plume_eth_tx_sender_batch_device")
 
     def ecdsa_sign_batch_device(self, n, hash, sk, aux, r, s, v, status, v27=False, stream=None):
         """the device form of ecdsa_sign_batch on torch tensors; aux may be None; enqueues on `stream` (None = current stream); does not synchronise"""

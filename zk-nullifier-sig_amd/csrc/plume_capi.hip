@@ -18,6 +18,8 @@
 #include <sys/random.h>
 #include <string>
 #include <thread>
+#include <tuple>
+#include <initializer_list>
 #include <algorithm>
 #include <atomic>
 #include <memory>
@@ -28,6 +30,7 @@
 #include "plume_capi_internal.h"
 #include "plume_ecdsa.h"
 #include "plume_ecdsa_sign.h"
+#include "plume_eth_tx.h"
 #include "plume_host_logic.h"
 #include "plume_keccak.h"
 #include "plume_launch.h"
@@ -179,6 +182,7 @@ struct plume_ctx {
     DevBuf bases, jobflags, itemflags, tab, tabscr, res, resinf, res2, res2inf, pkaff, sink, redo, digs, eq1fall, eq1k, clk;
     int sign_selfcheck = 0;                                        // plume_set_sign_selfcheck: 1 = every sign call stages its outputs here, verifies them and releases what verifies (sign_device)
     DevBuf scstage;                                                // ... the staging: six records in the 64-byte form, the signer's status and the check's verdict, 322 B / item; wiped after the release
+    DevBuf txstage;                                                // plume_eth_tx_sender_batch: what k_eth_tx_parse hands the recover stages -- hash, r, s, v, 97 B / item (public data: not wiped)
     DevBuf nonce;                                                  // the derived-nonce signer: r of the call in flight, 32 B / item, wiped on the call's stream after sign_final
     int eq1_short = 1;                                             // verify calls that give R: equation 1 in its short form (plume_eis.h).  0 = long form always (A/B), 2 = test: every item takes the fallback
     size_t eq1_short_min = (size_t)1 << 16;                        // ... for calls of at least this many items.  Round 6 sweep on one box, interleaved (profiles/r06_eq1_threshold.txt), now that the
@@ -300,7 +304,7 @@ static void destroy_single(plume_ctx* ctx) {
     if (ctx->ws_used && ctx->ws_free) (void)hipEventSynchronize(ctx->ws_free);
     for (hipStream_t q : {ctx->stream, ctx->up, ctx->down, ctx->side, ctx->pre}) if (q) (void)hipStreamSynchronize(q);
     for (DevBuf* b : {&ctx->bases, &ctx->jobflags, &ctx->itemflags, &ctx->tab, &ctx->tabscr, &ctx->res, &ctx->resinf, &ctx->res2, &ctx->res2inf, &ctx->pkaff,
-                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->scstage, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
+                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->scstage, &ctx->txstage, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
         b->release();
     for (DevBuf& b : ctx->agg) b.release();
     if (ctx->fixed) {
@@ -2026,6 +2030,172 @@ int plume::capi_eth_message_hash(plume_ctx* ctx, int mode, size_t n, const uint8
     if (n == 0) return 0;
     if (ctx->shards.empty()) return eth_hash_host(ctx, mode, n, msgs, msg_off, hash32, hash_fn);
     return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int { return eth_hash_host(sh, mode, hi - lo, msgs, msg_off + lo, hash32 + 32 * lo, hash_fn); });
+}
+// The transaction calls (plume_capi_internal.h): the ABI and the launcher live in plume_eth_tx_capi.hip.  parse is the message-hash call with more outputs: no table, no
+// workspace.  sender runs the same kernel into ctx->txstage and the recover stages (ecdsa_device, on this workspace and this stream) on what it staged, so it holds the
+// workspace from in front of the parse to behind finalize.
+static int eth_tx_parse_args_ok(size_t n, const void* off, const void* hash, const void* r, const void* s, const void* v, EthTxLaunch fn) {
+    if (!fn) return fail(PLUME_ERR_ARG, "the transaction kernel is not part of this build");
+    if (n && (!off || !hash || !r || !s || !v)) return fail(PLUME_ERR_ARG, "null array");
+    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
+    return 0;
+}
+static EthTxArgs eth_tx_args(size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, uint8_t* hash, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
+                             uint8_t* tx_type, uint8_t* status) {
+    EthTxArgs a; a.n = (uint32_t)n; a.txs = txs; a.tx_off = tx_off; a.txs_bytes = txs ? txs_bytes : 0; a.hash = hash; a.r = r; a.s = s; a.v = v; a.chain_id = chain_id;
+    a.tx_type = tx_type; a.status = status;
+    return a;
+}
+static int eth_tx_parse_device(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, uint8_t* hash, uint8_t* r, uint8_t* s, uint8_t* v,
+                               uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, hipStream_t st, EthTxLaunch fn) {
+    if (n == 0) return 0;
+    if (!txs && txs_bytes) return fail(PLUME_ERR_ARG, "null transaction buffer");
+    ctx->timer.begin(st);
+    fn(eth_tx_args(n, txs, tx_off, txs_bytes, hash, r, s, v, chain_id, tx_type, status), st); ctx->timer.stage("eth_tx_parse", st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int plume::capi_eth_tx_parse_device(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v,
+                                    uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream, EthTxLaunch tx_fn) {
+    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = eth_tx_parse_args_ok(n, tx_off, hash32, r, s, v, tx_fn)) return rc;
+    return eth_tx_parse_device(ctx, n, txs, tx_off, txs_bytes, hash32, r, s, v, chain_id, tx_type, status, st_, tx_fn);
+}
+// one piece of a host-pointer transaction call: the offsets rebased to the piece and the piece's bytes, uploaded through the slot.  bytes: what the piece holds
+static int eth_tx_stage_piece(plume_ctx* ctx, HostSlot& sl, const uint8_t* txs, const uint64_t* tx_off, size_t i0, size_t cnt, size_t& bytes, hipStream_t st) {
+    if (sl.relbuf.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
+    uint64_t* rel = sl.rel = (uint64_t*)sl.relbuf.p;
+    switch (plume_host::rebase_offsets(tx_off, i0, cnt, rel)) {
+        case 0: break;
+        case 1: return fail(PLUME_ERR_ARG, "tx_off is not non-decreasing");
+        default: return fail(PLUME_ERR_ARG, "transaction bytes per pass exceed 4 GiB");
+    }
+    bytes = (size_t)rel[cnt];
+    if (bytes && !txs) return fail(PLUME_ERR_ARG, "null transaction buffer");
+    if (sl.msgs.ensure(bytes + 16) || sl.off.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
+    if (bytes) HIPCHK(hipMemcpyAsync(sl.msgs.p, txs + tx_off[i0], bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sl.off.p, rel, (cnt + 1) * 8, hipMemcpyHostToDevice, st));
+    return 0;
+}
+// downloads behind a piece's kernels, then the wait -- on failure too: the slot's buffers (and the page-locked offsets) are reused by the next call
+static int eth_tx_drain_piece(int rc, hipStream_t st, std::initializer_list<std::tuple<void*, const void*, size_t>> copies) {
+    hipError_t e = hipSuccess;
+    for (const auto& c : copies)
+        if (!rc && e == hipSuccess && std::get<0>(c)) e = hipMemcpyAsync(std::get<0>(c), std::get<1>(c), std::get<2>(c), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(PLUME_ERR_HIP, std::string("transaction download: ") + hipGetErrorString(e));
+    if (es != hipSuccess) return fail(PLUME_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
+    return 0;
+}
+static int eth_tx_parse_host(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, uint8_t* hash, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
+                             uint8_t* tx_type, uint8_t* status, EthTxLaunch fn) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HostSlot& sl = ctx->slot[0];
+    hipStream_t st = ctx->stream;
+    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
+        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
+        size_t bytes = 0;
+        if (int rc = eth_tx_stage_piece(ctx, sl, txs, tx_off, i0, cnt, bytes, st)) { (void)hipStreamSynchronize(st); return rc; }
+        if (sl.out[0].ensure(32 * cnt) || sl.out[1].ensure(32 * cnt) || sl.out[2].ensure(32 * cnt) || sl.out[3].ensure(cnt) || (chain_id && sl.out[4].ensure(8 * cnt)) ||
+            (tx_type && sl.out[5].ensure(cnt)) || (status && sl.out[6].ensure(cnt))) {
+            (void)hipStreamSynchronize(st);
+            return PLUME_ERR_HIP;
+        }
+        const int rc = eth_tx_parse_device(ctx, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), bytes, sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(),
+                                           sl.out[3].as<uint8_t>(), chain_id ? sl.out[4].as<uint64_t>() : nullptr, tx_type ? sl.out[5].as<uint8_t>() : nullptr,
+                                           status ? sl.out[6].as<uint8_t>() : nullptr, st, fn);
+        if (int rc2 = eth_tx_drain_piece(rc, st, {{hash + 32 * i0, sl.out[0].p, 32 * cnt}, {r + 32 * i0, sl.out[1].p, 32 * cnt}, {s + 32 * i0, sl.out[2].p, 32 * cnt},
+                                                  {v + i0, sl.out[3].p, cnt}, {chain_id ? chain_id + i0 : nullptr, sl.out[4].p, 8 * cnt},
+                                                  {tx_type ? tx_type + i0 : nullptr, sl.out[5].p, cnt}, {status ? status + i0 : nullptr, sl.out[6].p, cnt}}))
+            return rc2;
+    }
+    return 0;
+}
+int plume::capi_eth_tx_parse(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
+                             uint8_t* tx_type, uint8_t* status, EthTxLaunch tx_fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = eth_tx_parse_args_ok(n, tx_off, hash32, r, s, v, tx_fn)) return rc;
+    if (n == 0) return 0;
+    if (ctx->shards.empty()) return eth_tx_parse_host(ctx, n, txs, tx_off, hash32, r, s, v, chain_id, tx_type, status, tx_fn);
+    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
+        return eth_tx_parse_host(sh, hi - lo, txs, tx_off + lo, hash32 + 32 * lo, r + 32 * lo, s + 32 * lo, v + lo, chain_id ? chain_id + lo : nullptr,
+                                 tx_type ? tx_type + lo : nullptr, status ? status + lo : nullptr, tx_fn);
+    });
+}
+static int eth_tx_sender_args_ok(int flags, int pk_format, int addr_format, size_t n, const void* off, const void* pk, const void* address, const void* status,
+                                 EthTxLaunch tx_fn, const EcdsaLaunch* fn) {
+    if (!tx_fn) return fail(PLUME_ERR_ARG, "the transaction kernel is not part of this build");
+    if (n && !off) return fail(PLUME_ERR_ARG, "null array");
+    const uint8_t one = 0;                                                      // (hash, r, s, v are the staging's: any non-null pointer passes the recovery's own check)
+    return ecdsa_args_ok(flags, pk_format, addr_format, n, &one, &one, &one, &one, pk, address, status, fn);
+}
+static int eth_tx_sender_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes,
+                                const uint8_t* expect, uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, hipStream_t st, EthTxLaunch tx_fn,
+                                const EcdsaLaunch* fn) {
+    if (n == 0) return 0;
+    if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
+    if (!txs && txs_bytes) return fail(PLUME_ERR_ARG, "null transaction buffer");
+    if (int rc = need_gcomb(ctx)) return rc;                                    // the recover stages' table, built before anything is queued
+    if (int rc = ws_acquire(ctx, st)) return rc;
+    WsHold hold(ctx, st);
+    if (ctx->txstage.ensure(97 * n)) return PLUME_ERR_HIP;
+    uint8_t* const stg = ctx->txstage.as<uint8_t>();
+    uint8_t *const g_hash = stg, *const g_r = stg + 32 * n, *const g_s = stg + 64 * n, *const g_v = stg + 96 * n;
+    ctx->timer.begin(st);
+    tx_fn(eth_tx_args(n, txs, tx_off, txs_bytes, g_hash, g_r, g_s, g_v, chain_id, tx_type, nullptr), st); ctx->timer.stage("eth_tx_parse", st);
+    HIPCHK(hipGetLastError());
+    if (int rc = ecdsa_device(ctx, flags, pk_format, addr_format, n, g_hash, g_r, g_s, g_v, expect, pk, address, status, st, fn, true)) return rc;
+    return hold.release();
+}
+int plume::capi_eth_tx_sender_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes,
+                                     const uint8_t* expect, uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream,
+                                     EthTxLaunch tx_fn, const EcdsaLaunch* fn) {
+    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = eth_tx_sender_args_ok(flags, pk_format, addr_format, n, tx_off, pk, address, status, tx_fn, fn)) return rc;
+    return eth_tx_sender_device(ctx, flags, pk_format, addr_format, n, txs, tx_off, txs_bytes, expect, pk, address, chain_id, tx_type, status, st_, tx_fn, fn);
+}
+static int eth_tx_sender_host(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, const uint8_t* expect,
+                              uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, EthTxLaunch tx_fn, const EcdsaLaunch* fn) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HostSlot& sl = ctx->slot[0];
+    hipStream_t st = ctx->stream;
+    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
+    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
+        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
+        size_t bytes = 0;
+        if (int rc = eth_tx_stage_piece(ctx, sl, txs, tx_off, i0, cnt, bytes, st)) { (void)hipStreamSynchronize(st); return rc; }
+        hipError_t eu = hipSuccess;
+        if ((expect && sl.in[0].ensure(20 * cnt)) || (pk && sl.out[0].ensure(P * cnt)) || (address && sl.out[1].ensure(W * cnt)) || (status && sl.out[2].ensure(cnt)) ||
+            (chain_id && sl.out[3].ensure(8 * cnt)) || (tx_type && sl.out[4].ensure(cnt)) ||
+            (expect && (eu = hipMemcpyAsync(sl.in[0].p, expect + 20 * i0, 20 * cnt, hipMemcpyHostToDevice, st)) != hipSuccess)) {
+            (void)hipStreamSynchronize(st);
+            return eu != hipSuccess ? fail(PLUME_ERR_HIP, std::string("expect upload: ") + hipGetErrorString(eu)) : PLUME_ERR_HIP;
+        }
+        const int rc = eth_tx_sender_device(ctx, flags, pk_format, addr_format, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), bytes, expect ? sl.in[0].as<uint8_t>() : nullptr,
+                                            pk ? sl.out[0].as<uint8_t>() : nullptr, address ? sl.out[1].as<uint8_t>() : nullptr, chain_id ? sl.out[3].as<uint64_t>() : nullptr,
+                                            tx_type ? sl.out[4].as<uint8_t>() : nullptr, status ? sl.out[2].as<uint8_t>() : nullptr, st, tx_fn, fn);
+        if (int rc2 = eth_tx_drain_piece(rc, st, {{pk ? pk + P * i0 : nullptr, sl.out[0].p, P * cnt}, {address ? address + W * i0 : nullptr, sl.out[1].p, W * cnt},
+                                                  {status ? status + i0 : nullptr, sl.out[2].p, cnt}, {chain_id ? chain_id + i0 : nullptr, sl.out[3].p, 8 * cnt},
+                                                  {tx_type ? tx_type + i0 : nullptr, sl.out[4].p, cnt}}))
+            return rc2;
+    }
+    return 0;
+}
+int plume::capi_eth_tx_sender(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, const uint8_t* expect,
+                              uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, EthTxLaunch tx_fn, const EcdsaLaunch* fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = eth_tx_sender_args_ok(flags, pk_format, addr_format, n, tx_off, pk, address, status, tx_fn, fn)) return rc;
+    if (n == 0) return 0;
+    if (ctx->shards.empty()) return eth_tx_sender_host(ctx, flags, pk_format, addr_format, n, txs, tx_off, expect, pk, address, chain_id, tx_type, status, tx_fn, fn);
+    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
+    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
+        return eth_tx_sender_host(sh, flags, pk_format, addr_format, hi - lo, txs, tx_off + lo, expect ? expect + 20 * lo : nullptr, pk ? pk + P * lo : nullptr,
+                                  address ? address + W * lo : nullptr, chain_id ? chain_id + lo : nullptr, tx_type ? tx_type + lo : nullptr, status ? status + lo : nullptr,
+                                  tx_fn, fn);
+    });
 }
 // The ECDSA signer (plume_capi_internal.h): the ABI and the launchers live in plume_ecdsa_sign_capi.hip.  The table of G is the signer's -- the comb, or at level 2 the
 // scanned table -- and the workspace is the signer's too: the nonce buffer, one Jacobian result per item (two with the self-check: sk G), the item flags; the call joins the

@@ -1,4 +1,4 @@
-// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_eth_hash_capi.hip, plume_ecdsa_capi.hip, plume_ecdsa_sign_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
+// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_eth_hash_capi.hip, plume_ecdsa_capi.hip, plume_ecdsa_sign_capi.hip, plume_eth_tx_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -84,6 +84,24 @@ __attribute__((visibility("hidden"))) int capi_eth_message_hash(plume_ctx* ctx, 
                                                                 EthHashLaunch hash_fn);
 __attribute__((visibility("hidden"))) int capi_eth_message_hash_device(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes,
                                                                        uint8_t* hash32, void* stream, EthHashLaunch hash_fn);
+
+// The transaction calls (plume_eth_tx_parse_batch*, plume_eth_tx_sender_batch*).  parse: one kernel on the caller's arrays, routed like the message-hash call.  sender: the
+// same kernel into the context's staging (hash, r, s, v: 97 B / item), then the recover stages on it -- workspace, sub-batches, chunk limit and routing are those of
+// capi_ecdsa_recover*.  The kernel's launcher comes in as a hook, the recover stages' as theirs.
+struct EthTxArgs;
+typedef void (*EthTxLaunch)(const EthTxArgs& a, hipStream_t st);
+__attribute__((visibility("hidden"))) int capi_eth_tx_parse(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, uint8_t* hash32, uint8_t* r, uint8_t* s,
+                                                            uint8_t* v, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, EthTxLaunch tx_fn);
+__attribute__((visibility("hidden"))) int capi_eth_tx_parse_device(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, uint8_t* hash32,
+                                                                   uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream,
+                                                                   EthTxLaunch tx_fn);
+__attribute__((visibility("hidden"))) int capi_eth_tx_sender(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off,
+                                                             const uint8_t* expect, uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status,
+                                                             EthTxLaunch tx_fn, const EcdsaLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_eth_tx_sender_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs,
+                                                                    const uint64_t* tx_off, size_t txs_bytes, const uint8_t* expect, uint8_t* pk, uint8_t* address,
+                                                                    uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream, EthTxLaunch tx_fn,
+                                                                    const EcdsaLaunch* fn);
 
 // The ECDSA signer (plume_ecdsa_sign_batch*): nonce, the comb, the conversion to affine, finalize; with plume_set_sign_selfcheck on, the recover stages over the staged
 // signatures and the release kernel behind them.  The launchers of its own kernels come in as a hook struct, with the recover stages' hooks beside them; the conversion and

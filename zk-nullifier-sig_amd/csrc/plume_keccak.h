@@ -182,11 +182,11 @@ PLUME_HD void eth_address_item(const EthArgs& a, uint32_t i) {
 // ------------------------------------------------------------------------------------------------ ragged messages
 // The digest a wallet signs (plume_eth_message_hash_batch, include/plume_hip.h): Keccak-256 of message i = msgs[msg_off[i] .. msg_off[i + 1]) itself (mode 0) or of
 //     "\x19Ethereum Signed Message:\n" || decimal(len) || msg                                    (mode 1, EIP-191 version 0x45: personal_sign)
-// One lane per item (k_eth_message_hash, plume_eth_kernels.hip).  The stream of P prefix bytes, len message bytes and the pad (0x01 ... 0x80, rate 136) is absorbed block
-// by block in a run-time loop; the state only ever sees literal indices, as above:
+// One lane per item (k_eth_message_hash, plume_eth_kernels.hip).  The stream of P prefix bytes, len message bytes, S suffix bytes (none here: k_eth_tx_parse, plume_eth_tx.h,
+// has some) and the pad (0x01 ... 0x80, rate 136) is absorbed block by block in a run-time loop; the state only ever sees literal indices, as above:
 //   - a lane of the block that lies wholly inside the message is two aligned 8-byte loads and a funnel shift (the message starts at any byte), when both words lie inside
 //     the msgs buffer; seventeen such tests, unrolled, XOR straight into a[0] .. a[16]
-//   - every other lane that holds anything -- prefix, decimal length, the ragged head and tail of the message, the pad -- is put together byte by byte from selects on the
+//   - every other lane that holds anything -- prefix, decimal length, the ragged head and tail of the message, the suffix, the pad -- is put together byte by byte from selects on the
 //     byte's position (keccak_edge_lane) in ONE run-time loop over the block's lanes, and lands in the state through seventeen selects: there is no byte-indexed array
 // Lanes of a wavefront run different block counts: the loop runs while any lane has a block left (nonce_any's rule, stated here so that this header does not need SHA-256).
 // An item whose offsets msg_span rejects hashes the empty message and never reads msgs.  Every value is public: plain branches.
@@ -229,25 +229,41 @@ PLUME_HD uint64_t eip191_prefix_lane(uint32_t q) {
     return q == 0 ? 0x7565726568744519ull : q == 1 ? 0x64656e676953206dull : q == 2 ? 0x6567617373654d20ull : q == 3 ? 0x0a3aull : 0ull;
 }
 
-// what one item absorbs: P prefix bytes (the fixed 26 and nd digits), len message bytes, the pad up to `last`, the final byte of the final block
+// what one item absorbs: P prefix bytes, len bytes of the input at msg, S suffix bytes, the pad up to `last`, the final byte of the final block.  The prefix (at most 40
+// bytes) and the suffix (at most 16) are little-endian lanes in named members, picked by selects: the message-hash kernel's stream is "26 + nd prefix bytes, no suffix",
+// the transaction kernel's (plume_eth_tx.h) a type byte and a list header in front, the EIP-155 fields behind.
 struct keccak_stream {
     const uint8_t* msg;
-    uint32_t len, nd, P;
-    uint64_t total, last;             // P + len; 136 * blocks - 1
+    uint32_t len, P, S;
+    uint64_t p0, p1, p2, p3, p4, s0, s1;
+    uint64_t total, last;             // P + len + S; 136 * blocks - 1
+    uint64_t nblk;                    // blocks to absorb; 0: the lane only keeps its wavefront company
 };
+PLUME_HD void keccak_stream_init(keccak_stream& s, const uint8_t* msg, uint32_t len) {
+    s.msg = msg; s.len = len; s.P = 0; s.S = 0;
+    s.p0 = s.p1 = s.p2 = s.p3 = s.p4 = s.s0 = s.s1 = 0;
+}
+// after msg, len, P, S are set: the block count and the place of the last pad byte
+PLUME_HD void keccak_stream_close(keccak_stream& s) {
+    s.total = (uint64_t)s.P + s.len + s.S;
+    s.nblk = s.total / PLUME_KECCAK_RATE + 1;                                            // the pad always adds a byte
+    s.last = s.nblk * PLUME_KECCAK_RATE - 1;
+}
+PLUME_HD uint64_t keccak_prefix_lane(const keccak_stream& s, uint32_t q) { return q == 0 ? s.p0 : q == 1 ? s.p1 : q == 2 ? s.p2 : q == 3 ? s.p3 : s.p4; }
 // byte `pos` of the stream
 PLUME_HD uint32_t keccak_stream_byte(const keccak_stream& s, uint64_t pos) {
-    if (pos < s.P) {
-        const uint32_t p = (uint32_t)pos;
-        if (p < PLUME_EIP191_PREFIX_LEN) return (uint32_t)(eip191_prefix_lane(p >> 3) >> (8 * (p & 7))) & 0xFFu;
-        return dec_digit_at(s.len, s.nd, p - PLUME_EIP191_PREFIX_LEN);
+    if (pos < s.P) return (uint32_t)(keccak_prefix_lane(s, (uint32_t)pos >> 3) >> (8 * ((uint32_t)pos & 7))) & 0xFFu;
+    const uint64_t body_end = (uint64_t)s.P + s.len;
+    if (pos < body_end) return s.msg[pos - s.P];
+    if (pos < s.total) {
+        const uint32_t q = (uint32_t)(pos - body_end);
+        return (uint32_t)((q < 8 ? s.s0 : s.s1) >> (8 * (q & 7))) & 0xFFu;
     }
-    if (pos < s.total) return s.msg[pos - s.P];
     return (pos == s.total ? 0x01u : 0u) | (pos == s.last ? 0x80u : 0u);
 }
-// the lane of the stream that starts at byte pos, for a lane the aligned loads do not serve
+// the lane of the stream that starts at byte pos (a multiple of 8), for a lane the aligned loads do not serve
 PLUME_HD uint64_t keccak_edge_lane(const keccak_stream& s, uint64_t pos) {
-    if (pos + 8 <= (s.P < 24u ? s.P : 24u)) return eip191_prefix_lane((uint32_t)pos >> 3);      // wholly inside the fixed text
+    if (pos + 8 <= s.P) return keccak_prefix_lane(s, (uint32_t)pos >> 3);                   // wholly inside the prefix
     uint64_t v = 0;
     PLUME_NOUNROLL for (uint32_t b = 0; b < 8; b++) v |= (uint64_t)keccak_stream_byte(s, pos + b) << (8 * b);
     return v;
@@ -264,29 +280,21 @@ PLUME_HD uint64_t keccak_load_lane(bool& ok, const uint8_t* p, const uint8_t* lo
     return (x >> sh) | (y << (64u - sh));
 }
 
-// Keccak-256 of item i's stream: the digest as eight little-endian words in memory order
-PLUME_HD void eth_message_digest(uint32_t dg[8], const EthHashArgs& a, uint32_t i) {
-    uint64_t o0; uint32_t len;
-    (void)msg_span(o0, len, a.msg_off, i, a.msgs_bytes);                                 // rejected offsets: the empty message, msgs never read
-    keccak_stream s;
-    s.msg = a.msgs + o0; s.len = len;
-    s.nd = dec_digits(len);
-    s.P = a.mode == PLUME_ETHK_HASH_EIP191 ? PLUME_EIP191_PREFIX_LEN + s.nd : 0u;
-    s.total = (uint64_t)s.P + len;
-    const uint64_t nblk = s.total / PLUME_KECCAK_RATE + 1;                               // the pad always adds a byte
-    s.last = nblk * PLUME_KECCAK_RATE - 1;
-    const uint8_t* const lo = a.msgs; const uint8_t* const hi = a.msgs + a.msgs_bytes;
+// Keccak-256 of a stream: the digest as eight little-endian words in memory order.  [lo, hi) is the buffer the aligned loads may touch.  Every lane of a wavefront that
+// is active at the call must make it (nblk = 0 for a lane with nothing to hash): the loop's condition is a vote.
+PLUME_HD void keccak_stream_digest(uint32_t dg[8], const keccak_stream& s, const uint8_t* lo, const uint8_t* hi) {
+    const uint64_t body_end = (uint64_t)s.P + s.len;
     uint64_t st[25];
     PLUME_UNROLL for (int k = 0; k < 25; k++) st[k] = 0;
-    PLUME_NOUNROLL for (uint64_t blk = 0; keccak_any(blk < nblk); blk++) {
-        if (blk < nblk) {
+    PLUME_NOUNROLL for (uint64_t blk = 0; keccak_any(blk < s.nblk); blk++) {
+        if (blk < s.nblk) {
             const uint64_t base = blk * PLUME_KECCAK_RATE;
             uint32_t edge = 0;                                                           // bit j: lane j is not served by the aligned loads
             PLUME_UNROLL for (int j = 0; j < 17; j++) {
                 const uint64_t pos = base + 8u * (uint32_t)j;
                 bool ok = false;
                 uint64_t v = 0;
-                if (pos >= s.P && pos + 8 <= s.total) v = keccak_load_lane(ok, s.msg + (pos - s.P), lo, hi);
+                if (pos >= s.P && pos + 8 <= body_end) v = keccak_load_lane(ok, s.msg + (pos - s.P), lo, hi);
                 st[j] ^= v;
                 edge |= ok ? 0u : 1u << j;
             }
@@ -300,6 +308,25 @@ PLUME_HD void eth_message_digest(uint32_t dg[8], const EthHashArgs& a, uint32_t 
         }
     }
     PLUME_UNROLL for (int k = 0; k < 8; k++) dg[k] = (uint32_t)(st[k >> 1] >> (32 * (k & 1)));
+}
+
+// Keccak-256 of item i's stream: the digest as eight little-endian words in memory order
+PLUME_HD void eth_message_digest(uint32_t dg[8], const EthHashArgs& a, uint32_t i) {
+    uint64_t o0; uint32_t len;
+    (void)msg_span(o0, len, a.msg_off, i, a.msgs_bytes);                                 // rejected offsets: the empty message, msgs never read
+    keccak_stream s;
+    keccak_stream_init(s, a.msgs + o0, len);
+    if (a.mode == PLUME_ETHK_HASH_EIP191) {                                              // the fixed text, then the decimal length: bytes 26 .. 26 + nd
+        const uint32_t nd = dec_digits(len);
+        s.P = PLUME_EIP191_PREFIX_LEN + nd;
+        s.p0 = eip191_prefix_lane(0); s.p1 = eip191_prefix_lane(1); s.p2 = eip191_prefix_lane(2); s.p3 = eip191_prefix_lane(3);
+        PLUME_NOUNROLL for (uint32_t d = 0; d < nd; d++) {
+            const uint64_t c = dec_digit_at(len, nd, d);
+            if (d < 6) s.p3 |= c << (8 * (d + 2)); else s.p4 |= c << (8 * (d - 6));
+        }
+    }
+    keccak_stream_close(s);
+    keccak_stream_digest(dg, s, a.msgs, a.msgs + a.msgs_bytes);
 }
 
 // lane i of k_eth_message_hash

@@ -21,7 +21,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .capi import ECDSA_INVALID, ETH_INVALID, ETH_MATCH, RECOVER_INVALID, RECOVER_MATCH, Engine, default_engine, pack_messages
+from .capi import ECDSA_INVALID, ETH_INVALID, ETH_MATCH, ETH_TX_OK, RECOVER_INVALID, RECOVER_MATCH, Engine, default_engine, pack_messages
 
 DST = b"QUUX-V01-CS02-with-secp256k1_XMD:SHA-256_SSWU_RO_"  # rust-k256/src/lib.rs:61
 _P = 2**256 - 2**32 - 977
@@ -371,6 +371,37 @@ def personal_recover(msg: bytes, sig65: bytes, engine: Optional[Engine] = None) 
     eng = engine or default_engine()
     msgs, off = pack_messages([bytes(msg)])
     return ecdsa_recover(eng.eth_message_hash_batch(msgs, off, "eip191")[0].tobytes(), sig65[:32], sig65[32:64], sig65[64], eng)
+
+
+def tx_signing_hash(raw: bytes, engine: Optional[Engine] = None) -> bytes:
+    """The 32 bytes the sender of one raw signed transaction signed, made on the GPU (include/plume_hip.h, plume_eth_tx_parse_batch): legacy (unprotected or EIP-155) and the
+    typed envelopes 01 - 04.  Raises SignatureError for an item that is no such transaction (the envelope, the top-level framing or a signature field breaks the rule)."""
+    msgs, off = pack_messages([bytes(raw)])
+    out = (engine or default_engine()).eth_tx_parse_batch(msgs, off)
+    if int(out["status"][0]) != ETH_TX_OK:
+        raise SignatureError("tx_signing_hash: not a signed transaction of a known kind")
+    return out["hash"][0].tobytes()
+
+
+def _tx_sender(what: str, want, raw: bytes, engine: Optional[Engine], low_s: bool):
+    msgs, off = pack_messages([bytes(raw)])
+    pk, address, status, _, _ = (engine or default_engine()).eth_tx_sender_batch(msgs, off, low_s=low_s, want=want)
+    if int(status[0]) == ECDSA_INVALID:
+        raise SignatureError(f"{what}: no sender (not a signed transaction of a known kind, or its signature recovers no public key)")
+    return pk, address
+
+
+def tx_sender(raw: bytes, engine: Optional[Engine] = None, low_s: bool = True) -> Tuple[AffinePoint, bytes]:
+    """The public key and the 20-byte address of the sender of one raw signed transaction, framed, hashed and recovered on the GPU (plume_eth_tx_sender_batch).  low_s: the
+    EIP-2 rule, right for everything after Homestead.  A sender recovery, not a consensus decoder: inner fields are not validated.  Raises SignatureError when there is no
+    sender."""
+    pk, address = _tx_sender("tx_sender", ("pk", "address", "status"), raw, engine, low_s)
+    return AffinePoint.from_bytes64(pk[0].tobytes()), address[0].tobytes()
+
+
+def tx_sender_address(raw: bytes, engine: Optional[Engine] = None, low_s: bool = True) -> bytes:
+    """tx_sender for callers that want the 20 address bytes only"""
+    return _tx_sender("tx_sender_address", ("address", "status"), raw, engine, low_s)[1][0].tobytes()
 
 
 def circuit_inputs(sig: "PlumeSignature", engine: Optional[Engine] = None) -> dict:

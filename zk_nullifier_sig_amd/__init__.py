@@ -4,7 +4,7 @@ from pathlib import Path as _Path
 
 __path__.append(str(_Path(__file__).resolve().parent.parent / "zk-nullifier-sig_amd"))
 
-from .capi import ECDSA_INVALID, ECDSA_LOW_S, ECDSA_MATCH, ECDSA_MISMATCH, ECDSA_SIGN_V27, ETH_HASH_MODES, ETH_INVALID, ETH_MATCH, ETH_MISMATCH, Engine, NullifierSet, PlumeHipError, default_engine, library_path  # noqa: E402,F401
+from .capi import ECDSA_INVALID, ECDSA_LOW_S, ECDSA_MATCH, ECDSA_MISMATCH, ECDSA_SIGN_V27, ETH_HASH_MODES, ETH_INVALID, ETH_MATCH, ETH_MISMATCH, ETH_TX_INVALID, ETH_TX_OK, Engine, NullifierSet, PlumeHipError, default_engine, library_path  # noqa: E402,F401
 from .plume import (  # noqa: E402,F401
     DST,
     AffinePoint,
@@ -28,6 +28,9 @@ from .plume import (  # noqa: E402,F401
     personal_sign,
     sign,
     sign_with_r,
+    tx_sender,
+    tx_sender_address,
+    tx_signing_hash,
     verify_non_zk,
 )
 from . import nullifier_set  # noqa: E402,F401
