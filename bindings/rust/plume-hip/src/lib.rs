@@ -97,6 +97,15 @@ pub const PLUME_ECDSA_LOW_S: c_int = 1;
 /// `plume_eth_tx_parse_batch`: the status of an item
 pub const PLUME_ETH_TX_OK: u8 = 1;
 pub const PLUME_ETH_TX_INVALID: u8 = 3;
+/// `plume_merkle_*`: leaf formats, the sort flag, the status of an item, the proof length of a refused index
+pub const PLUME_MERKLE_LEAF_HASH32: c_int = 0;
+pub const PLUME_MERKLE_LEAF_ADDRESS: c_int = 1;
+pub const PLUME_MERKLE_LEAF_ADDRESS_UINT256: c_int = 2;
+pub const PLUME_MERKLE_SORT_LEAVES: c_int = 1;
+pub const PLUME_MERKLE_MISMATCH: u8 = 0;
+pub const PLUME_MERKLE_MATCH: u8 = 1;
+pub const PLUME_MERKLE_INVALID: u8 = 3;
+pub const PLUME_MERKLE_BAD_PROOF: u8 = 255;
 
 #[link(name = "plume_hip")]
 extern "C" {
@@ -173,6 +182,20 @@ extern "C" {
         pk: *mut u8, address: *mut u8, chain_id: *mut u64, tx_type: *mut u8, status: *mut u8) -> c_int;
     fn plume_eth_tx_sender_batch_device(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, txs: *const u8, tx_off: *const u64, txs_bytes: usize,
         expect: *const u8, pk: *mut u8, address: *mut u8, chain_id: *mut u64, tx_type: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_merkle_max_proof_len(n: usize) -> usize;
+    fn plume_merkle_leaf_batch(ctx: *mut plume_ctx, leaf_format: c_int, addr_format: c_int, n: usize, address: *const u8, amount: *const u8, leaf32: *mut u8,
+        status: *mut u8) -> c_int;
+    fn plume_merkle_leaf_batch_device(ctx: *mut plume_ctx, leaf_format: c_int, addr_format: c_int, n: usize, address: *const u8, amount: *const u8, leaf32: *mut u8,
+        status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_merkle_tree_build(ctx: *mut plume_ctx, flags: c_int, n: usize, leaf32: *const u8, tree: *mut u8, leaf_pos: *mut u32) -> c_int;
+    fn plume_merkle_tree_build_device(ctx: *mut plume_ctx, flags: c_int, n: usize, leaf32: *const u8, tree: *mut u8, leaf_pos: *mut u32, stream: *mut c_void) -> c_int;
+    fn plume_merkle_proof_batch(ctx: *mut plume_ctx, n: usize, tree: *const u8, m: usize, pos: *const u32, depth: usize, proof: *mut u8, proof_len: *mut u8) -> c_int;
+    fn plume_merkle_proof_batch_device(ctx: *mut plume_ctx, n: usize, tree: *const u8, m: usize, pos: *const u32, depth: usize, proof: *mut u8, proof_len: *mut u8,
+        stream: *mut c_void) -> c_int;
+    fn plume_merkle_verify_batch(ctx: *mut plume_ctx, leaf_format: c_int, addr_format: c_int, m: usize, address_or_leaf: *const u8, amount: *const u8, depth: usize,
+        proof: *const u8, proof_len: *const u8, root32: *const u8, status: *mut u8) -> c_int;
+    fn plume_merkle_verify_batch_device(ctx: *mut plume_ctx, leaf_format: c_int, addr_format: c_int, m: usize, address_or_leaf: *const u8, amount: *const u8, depth: usize,
+        proof: *const u8, proof_len: *const u8, root32: *const u8, status: *mut u8, stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -376,6 +399,63 @@ impl HipEngine {
         if rc != 0 { return Err(last_error()); }
         if status[0] == PLUME_ECDSA_INVALID { return Err(HipError("tx_sender_address: no sender".to_string())); }
         Ok(addr)
+    }
+
+    /// The leaf of one account in OpenZeppelin's `StandardMerkleTree` (`plume_merkle_leaf_batch`): `Keccak(Keccak(abi.encode(address)))`, or with an `amount` (32
+    /// big-endian bytes) `Keccak(Keccak(abi.encode(address, amount)))`, the tree of `["address", "uint256"]`.
+    pub fn merkle_leaf(&self, addr20: &[u8; 20], amount: Option<&[u8; 32]>) -> Result<[u8; 32], HipError> {
+        let mut leaf = [0u8; 32];
+        let fmt = if amount.is_some() { PLUME_MERKLE_LEAF_ADDRESS_UINT256 } else { PLUME_MERKLE_LEAF_ADDRESS };
+        let rc = unsafe { plume_merkle_leaf_batch(self.0, fmt, PLUME_ETH_ADDR_RAW20, 1, addr20.as_ptr(), amount.map_or(std::ptr::null(), |a| a.as_ptr()), leaf.as_mut_ptr(),
+                                                  std::ptr::null_mut()) };
+        if rc != 0 { return Err(last_error()); }
+        Ok(leaf)
+    }
+    /// The whole tree over 32-byte leaves (`plume_merkle_tree_build`): `(2n - 1) * 32` bytes, the root first, and the tree index of every input leaf.  `sort`: order
+    /// the leaves by (hash, input index) first, as `StandardMerkleTree` does.
+    pub fn merkle_tree(&self, leaves: &[[u8; 32]], sort: bool) -> Result<(Vec<u8>, Vec<u32>), HipError> {
+        let n = leaves.len();
+        let flat: Vec<u8> = leaves.iter().flatten().copied().collect();
+        let (mut tree, mut pos) = (vec![0u8; if n == 0 { 0 } else { 32 * (2 * n - 1) }], vec![0u32; n]);
+        let rc = unsafe { plume_merkle_tree_build(self.0, if sort { PLUME_MERKLE_SORT_LEAVES } else { 0 }, n, flat.as_ptr(), tree.as_mut_ptr(), pos.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        Ok((tree, pos))
+    }
+    /// The root of `merkle_tree`.
+    pub fn merkle_root(&self, leaves: &[[u8; 32]], sort: bool) -> Result<[u8; 32], HipError> {
+        let (tree, _) = self.merkle_tree(leaves, sort)?;
+        let mut root = [0u8; 32];
+        root.copy_from_slice(&tree[..32]);
+        Ok(root)
+    }
+    /// The proof of input leaf `index`: the siblings on the way to the root, leaf side first (`plume_merkle_proof_batch`).
+    pub fn merkle_proof(&self, leaves: &[[u8; 32]], index: usize, sort: bool) -> Result<Vec<[u8; 32]>, HipError> {
+        if index >= leaves.len() { return Err(HipError("merkle_proof: index out of range".to_string())); }
+        let (tree, pos) = self.merkle_tree(leaves, sort)?;
+        let depth = unsafe { plume_merkle_max_proof_len(leaves.len()) };
+        let (mut slots, mut len) = (vec![0u8; 32 * depth + 1], [0u8; 1]);
+        let rc = unsafe { plume_merkle_proof_batch(self.0, leaves.len(), tree.as_ptr(), 1, pos[index..].as_ptr(), depth, slots.as_mut_ptr(), len.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        if len[0] == PLUME_MERKLE_BAD_PROOF { return Err(HipError("merkle_proof: no proof".to_string())); }
+        Ok((0..len[0] as usize).map(|k| { let mut e = [0u8; 32]; e.copy_from_slice(&slots[32 * k..32 * k + 32]); e }).collect())
+    }
+    fn merkle_verify_item(&self, fmt: c_int, item: &[u8], amount: Option<&[u8; 32]>, proof: &[[u8; 32]], root32: &[u8; 32]) -> Result<bool, HipError> {
+        if proof.len() > 64 { return Ok(false); }
+        let mut slots: Vec<u8> = proof.iter().flatten().copied().collect();
+        slots.push(0);                                   // keeps the pointer non-null for an empty proof
+        let (len, mut status) = ([proof.len() as u8], [0u8; 1]);
+        let rc = unsafe { plume_merkle_verify_batch(self.0, fmt, PLUME_ETH_ADDR_RAW20, 1, item.as_ptr(), amount.map_or(std::ptr::null(), |a| a.as_ptr()), proof.len(),
+                                                    slots.as_ptr(), len.as_ptr(), root32.as_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        Ok(status[0] == PLUME_MERKLE_MATCH)
+    }
+    /// `MerkleProof.verify` of a 32-byte leaf (`plume_merkle_verify_batch`).
+    pub fn merkle_verify(&self, leaf: &[u8; 32], proof: &[[u8; 32]], root32: &[u8; 32]) -> Result<bool, HipError> {
+        self.merkle_verify_item(PLUME_MERKLE_LEAF_HASH32, leaf, None, proof, root32)
+    }
+    /// `merkle_verify` of an address: its leaf (with `amount`, the leaf of `["address", "uint256"]`) is computed in the same kernel.
+    pub fn merkle_verify_address(&self, addr20: &[u8; 20], amount: Option<&[u8; 32]>, proof: &[[u8; 32]], root32: &[u8; 32]) -> Result<bool, HipError> {
+        self.merkle_verify_item(if amount.is_some() { PLUME_MERKLE_LEAF_ADDRESS_UINT256 } else { PLUME_MERKLE_LEAF_ADDRESS }, addr20, amount, proof, root32)
     }
 
     /// Aggregate pre-filter (no reference counterpart; include/plume_hip.h `plume_aggregate_check`): `Ok(true)` iff every V1 signature of the batch would
@@ -646,6 +726,12 @@ impl PlumeSignature {
     pub fn verify_for_address(&self, engine: &HipEngine, addr20: &[u8; 20]) -> bool {
         let matches = engine.eth_address_batch(std::slice::from_ref(&self.pk), Some(std::slice::from_ref(addr20))).ok().and_then(|mut v| v.pop().flatten()).map(|(_, m)| m).unwrap_or(false);
         matches && self.verify(engine)
+    }
+    /// `verify()` AND "`pk`'s address is on the allow-list whose Merkle root is `root32`": pk -> address -> leaf -> proof, for a consumer that holds one 32-byte root
+    /// of a `StandardMerkleTree` of `["address"]` (or of `["address", "uint256"]` with `amount`).  `false` for a `pk` that has no address.
+    pub fn verify_for_root(&self, engine: &HipEngine, root32: &[u8; 32], proof: &[[u8; 32]], amount: Option<&[u8; 32]>) -> bool {
+        let on_list = self.eth_address(engine).ok().map_or(false, |a| engine.merkle_verify_address(&a, amount, proof, root32).unwrap_or(false));
+        on_list && self.verify(engine)
     }
     /// The V1-specific fields this signature's `pk, nullifier, c, s` imply (`HipEngine::recover_batch`), for a `c` that is the V1 hash of them: upgrades a compact
     /// four-field record to a V1 record.  An error when the library rejects the inputs or `c` is not that hash -- never a silent pair of points that do not verify.

@@ -280,6 +280,10 @@ struct PlumeSignature {
     std::array<uint8_t, 20> eth_address(Engine& eng = Engine::shared()) const;
     std::string eth_address_eip55(Engine& eng = Engine::shared()) const;
     bool verify_for_address(const std::array<uint8_t, 20>& addr20, Engine& eng = Engine::shared()) const;
+    // verify() AND "pk's address is on the allow-list whose Merkle root is root32" (plume_hip.h plume_merkle_verify_batch): pk -> address -> leaf -> proof, for a consumer
+    // that holds one 32-byte root of OpenZeppelin's StandardMerkleTree of ["address"] -- or of ["address", "uint256"] when amount (32 big-endian bytes) is given -- and
+    // takes a proof from every claimant.  proof: the siblings, leaf side first.  false for a pk that has no address.
+    bool verify_for_root(const Bytes32& root32, const std::vector<Bytes32>& proof, const Bytes32* amount = nullptr, Engine& eng = Engine::shared()) const;
     // rust-k256/src/lib.rs:149-156
     template <class Rng> static PlumeSignature sign_v1(const SecretKey& secret_key, const Bytes& msg, Rng& rng, Engine& eng = Engine::shared());
     template <class Rng> static PlumeSignature sign_v2(const SecretKey& secret_key, const Bytes& msg, Rng& rng, Engine& eng = Engine::shared());
@@ -438,6 +442,71 @@ inline std::array<uint8_t, 20> tx_sender_address(const uint8_t* raw, size_t len,
                      "plume_eth_tx_sender_batch");
     if (st == PLUME_ECDSA_INVALID) throw SignatureError();
     return addr;
+}
+
+// Keccak Merkle allow-lists (plume_hip.h plume_merkle_*): the tree OpenZeppelin's StandardMerkleTree builds and MerkleProof.verify checks, made on the GPU.  merkle_leaf:
+// the leaf of an account, Keccak(Keccak(abi.encode(address))) or, with an amount (32 big-endian bytes), Keccak(Keccak(abi.encode(address, amount))).  merkle_root /
+// merkle_proof: the root of the tree over 32-byte leaves and the siblings of leaf `index`, leaf side first (sort: order the leaves by hash first, as StandardMerkleTree
+// does).  merkle_verify: MerkleProof.verify of a 32-byte leaf; merkle_verify_address computes the leaf of an address first, in the same kernel.
+inline Bytes32 merkle_leaf(const std::array<uint8_t, 20>& addr20, const Bytes32* amount = nullptr, Engine& eng = Engine::shared()) {
+    Bytes32 leaf{};
+    plume_hip::check(plume_merkle_leaf_batch(eng.ctx(), amount ? PLUME_MERKLE_LEAF_ADDRESS_UINT256 : PLUME_MERKLE_LEAF_ADDRESS, PLUME_ETH_ADDR_RAW20, 1, addr20.data(),
+                                             amount ? amount->data() : nullptr, leaf.data(), nullptr),
+                     "plume_merkle_leaf_batch");
+    return leaf;
+}
+namespace merkle_detail {
+inline std::vector<uint8_t> merkle_tree(const std::vector<Bytes32>& leaves, bool sort, std::vector<uint32_t>& leaf_pos, Engine& eng) {
+    std::vector<uint8_t> flat(32 * leaves.size()), tree(leaves.empty() ? 0 : 32 * (2 * leaves.size() - 1));
+    for (size_t i = 0; i < leaves.size(); i++) std::copy(leaves[i].begin(), leaves[i].end(), flat.begin() + 32 * i);
+    leaf_pos.assign(leaves.size(), 0);
+    plume_hip::check(plume_merkle_tree_build(eng.ctx(), sort ? PLUME_MERKLE_SORT_LEAVES : 0, leaves.size(), flat.data(), tree.data(), leaf_pos.data()), "plume_merkle_tree_build");
+    return tree;
+}
+}  // namespace merkle_detail
+inline Bytes32 merkle_root(const std::vector<Bytes32>& leaves, bool sort = true, Engine& eng = Engine::shared()) {
+    std::vector<uint32_t> pos;
+    const std::vector<uint8_t> tree = merkle_detail::merkle_tree(leaves, sort, pos, eng);
+    Bytes32 root{};
+    std::copy(tree.begin(), tree.begin() + 32, root.begin());
+    return root;
+}
+inline std::vector<Bytes32> merkle_proof(const std::vector<Bytes32>& leaves, size_t index, bool sort = true, Engine& eng = Engine::shared()) {
+    std::vector<uint32_t> pos;
+    const std::vector<uint8_t> tree = merkle_detail::merkle_tree(leaves, sort, pos, eng);
+    if (index >= leaves.size()) throw std::out_of_range("merkle_proof: index");
+    const size_t depth = plume_merkle_max_proof_len(leaves.size());
+    std::vector<uint8_t> slots(32 * depth + 1);
+    uint8_t len = 0;
+    plume_hip::check(plume_merkle_proof_batch(eng.ctx(), leaves.size(), tree.data(), 1, &pos[index], depth, slots.data(), &len), "plume_merkle_proof_batch");
+    std::vector<Bytes32> proof(len == PLUME_MERKLE_BAD_PROOF ? 0 : len);
+    for (size_t k = 0; k < proof.size(); k++) std::copy(slots.begin() + 32 * k, slots.begin() + 32 * k + 32, proof[k].begin());
+    return proof;
+}
+namespace merkle_detail {
+inline bool merkle_verify_item(int leaf_format, const uint8_t* item, const Bytes32* amount, const std::vector<Bytes32>& proof, const Bytes32& root32, Engine& eng) {
+    if (proof.size() > 64) return false;
+    std::vector<uint8_t> slots(32 * proof.size() + 1);
+    for (size_t k = 0; k < proof.size(); k++) std::copy(proof[k].begin(), proof[k].end(), slots.begin() + 32 * k);
+    const uint8_t len = (uint8_t)proof.size();
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_merkle_verify_batch(eng.ctx(), leaf_format, PLUME_ETH_ADDR_RAW20, 1, item, amount ? amount->data() : nullptr, proof.size(), slots.data(), &len, root32.data(), &st),
+          "plume_merkle_verify_batch");
+    return st == PLUME_MERKLE_MATCH;
+}
+}  // namespace merkle_detail
+inline bool merkle_verify(const Bytes32& leaf, const std::vector<Bytes32>& proof, const Bytes32& root32, Engine& eng = Engine::shared()) {
+    return merkle_detail::merkle_verify_item(PLUME_MERKLE_LEAF_HASH32, leaf.data(), nullptr, proof, root32, eng);
+}
+inline bool merkle_verify_address(const std::array<uint8_t, 20>& addr20, const std::vector<Bytes32>& proof, const Bytes32& root32, const Bytes32* amount = nullptr,
+                                  Engine& eng = Engine::shared()) {
+    return merkle_detail::merkle_verify_item(amount ? PLUME_MERKLE_LEAF_ADDRESS_UINT256 : PLUME_MERKLE_LEAF_ADDRESS, addr20.data(), amount, proof, root32, eng);
+}
+inline bool PlumeSignature::verify_for_root(const Bytes32& root32, const std::vector<Bytes32>& proof, const Bytes32* amount, Engine& eng) const {
+    uint8_t st = 0xFF;
+    std::array<uint8_t, 20> addr{};
+    plume_hip::check(plume_eth_address_batch(eng.ctx(), PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, pk.xy.data(), nullptr, addr.data(), &st), "plume_eth_address_batch");
+    return st != PLUME_ETH_INVALID && merkle_verify_address(addr, proof, root32, amount, eng) && verify(eng);
 }
 
 // rust-k256/src/randomizedsigner.rs:25-41: a borrowed secret key and the variant

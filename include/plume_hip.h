@@ -76,7 +76,8 @@ void plume_destroy(plume_ctx* ctx);
 /* Last error text of this thread (valid until the next failing call on the thread). */
 const char* plume_last_error(void);
 /* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  The number in the string stays 0.12 for library 0.13: callers
- * that need the 0.13 or 0.14 entry points look for the symbols (dlsym / getattr), as zk-nullifier-sig_amd/capi.py does.  0.14: the senders of raw Ethereum transactions
+ * that need the 0.13, 0.14 or 0.15 entry points look for the symbols (dlsym / getattr), as zk-nullifier-sig_amd/capi.py does.  0.15: Keccak Merkle allow-lists
+ * (plume_merkle_*); 0.14: the senders of raw Ethereum transactions
  * (plume_eth_tx_parse_batch*, plume_eth_tx_sender_batch*); 0.13: deterministic ECDSA signatures with a recovery id
  * (plume_ecdsa_sign_batch*) and the digest a wallet signs (plume_eth_message_hash_batch*: Keccak-256 of ragged messages, EIP-191); 0.12: public keys and addresses from
  * ECDSA signatures (plume_ecdsa_recover_batch*: ecrecover); 0.11: Ethereum addresses of public keys (plume_eth_address_batch*: Keccak-256);
@@ -627,6 +628,58 @@ int plume_eth_tx_sender_batch(plume_ctx* ctx, int flags, int pk_format, int addr
                               uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status);
 int plume_eth_tx_sender_batch_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes,
                                      const uint8_t* expect, uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream);
+
+/* ---- Keccak Merkle allow-lists of addresses  (library 0.15) -------------------------------------------------------
+ * An application that gates on a list of accounts usually publishes ONE 32-byte root and lets every claimant bring a proof.  These calls build that tree, hand out proofs
+ * and check proofs against a root, in the form OpenZeppelin's StandardMerkleTree (@openzeppelin/merkle-tree) builds and MerkleProof.verify checks on chain.
+ *   leaf       PLUME_MERKLE_LEAF_HASH32: the caller's 32 bytes as they are.  PLUME_MERKLE_LEAF_ADDRESS: Keccak-256(Keccak-256(0^12 || addr20)), the tree of ["address"].
+ *              PLUME_MERKLE_LEAF_ADDRESS_UINT256: Keccak-256(Keccak-256(0^12 || addr20 || amount32)), amount32 big-endian: the tree of ["address", "uint256"].
+ *              Addresses come as PLUME_ETH_ADDR_RAW20 (20 bytes per item) or PLUME_ETH_ADDR_RECORD64 (64 bytes per item: what plume_eth_address_batch,
+ *              plume_ecdsa_recover_batch and plume_eth_tx_sender_batch write); a RECORD64 whose first 44 bytes are not zero is invalid.  PLUME_ETH_ADDR_EIP55 returns
+ *              PLUME_ERR_ARG.  With HASH32 an item is 32 bytes and addr_format (still 0 or 1) and amount are ignored; amount is also ignored with ADDRESS.
+ *   node       hash_pair(a, b) = Keccak-256(min(a, b) || max(a, b)), the 32-byte values compared as big-endian numbers.
+ *   tree       n >= 1 leaves L[0 .. n) give tree[0 .. 2n - 1) of 32-byte nodes: tree[2n - 2 - i] = L[i], tree[i] = hash_pair(tree[2i + 1], tree[2i + 2]) for
+ *              i = n - 2 .. 0; the root is tree[0].  With PLUME_MERKLE_SORT_LEAVES L is the input sorted ascending by (leaf bytes, input index) -- the index makes
+ *              leaf_pos deterministic for duplicate leaves -- and without it L is the input order.  leaf_pos[j] is the tree index of input leaf j.
+ *   proof      of tree index t: while t > 0 emit tree[t odd ? t + 1 : t - 1], then t = (t - 1) / 2.  Its length is floor(log2(t + 1)), at most
+ *              plume_merkle_max_proof_len(n) = floor(log2(2n - 1)); when n is no power of two the leaves' proofs differ in length by one.
+ *   verify     MerkleProof.processProof: h = leaf, h = hash_pair(h, p) for every proof element p in turn, compare h with the root.
+ * plume_merkle_leaf_batch: leaf32[i] and status[i] (optional): PLUME_MERKLE_MATCH for a valid item, PLUME_MERKLE_INVALID and the all-zero leaf for an invalid one.
+ * plume_merkle_tree_build: tree holds (2n - 1) * 32 bytes; leaf_pos (n words) is optional; n = 0 or n > 2^26 returns PLUME_ERR_ARG; unknown flag bits too.  The sort is a
+ * bitonic network on the whole (leaf, index) key; its workspace, 36 bytes per leaf of n rounded up to a power of two, belongs to the context, so the device form joins the
+ * workspace chain of the other device-resident calls.  The host form stages the whole tree on ONE device: a plume_init_multi context uses its first.
+ * plume_merkle_proof_batch: the proofs of m tree indices pos[k] (any node, not only leaves), each in `depth` slots of 32 bytes (depth <= 64), unused slots zero;
+ * proof_len[k] is one byte.  A pos[k] outside [0, 2n - 1) or a proof longer than depth gives PLUME_MERKLE_BAD_PROOF (255) and zero slots.  The host form uploads the tree
+ * once and takes the indices in pieces of at most plume_set_chunk, on the first device of a plume_init_multi context.
+ * plume_merkle_verify_batch: item k is an address (or, with HASH32, a leaf), its amount where the format has one, `depth` proof slots and proof_len[k]; the leaf is computed
+ * in the same kernel, so the records of plume_eth_tx_sender_batch go in as they are.  status[k] (required): PLUME_MERKLE_MATCH the proof leads to root32,
+ * PLUME_MERKLE_MISMATCH it does not, PLUME_MERKLE_INVALID an invalid item or proof_len[k] > depth.  The host form routes like plume_eth_address_batch (pieces of at most
+ * plume_set_chunk items, the shards of a plume_init_multi context).
+ * All: m = 0 (n = 0 for the leaf call) is a successful no-op; the device forms enqueue on `stream` and do not synchronise; byte arrays may sit at any byte offset (16-byte
+ * aligned arrays take the vector loads), leaf_pos and pos need 4-byte alignment; with stage timing on the stages are "merkle_leaf", "merkle_sort", "merkle_place",
+ * "merkle_levels" (one launch per depth of more than 256 parents), "merkle_top" (the depths above, one launch), "merkle_proof", "merkle_verify"; everything is public
+ * data. */
+#define PLUME_MERKLE_LEAF_HASH32          0
+#define PLUME_MERKLE_LEAF_ADDRESS         1
+#define PLUME_MERKLE_LEAF_ADDRESS_UINT256 2
+#define PLUME_MERKLE_SORT_LEAVES          1
+#define PLUME_MERKLE_MISMATCH  0
+#define PLUME_MERKLE_MATCH     1
+#define PLUME_MERKLE_INVALID   3
+#define PLUME_MERKLE_BAD_PROOF 255
+size_t plume_merkle_max_proof_len(size_t n);
+int plume_merkle_leaf_batch(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* address, const uint8_t* amount, uint8_t* leaf32, uint8_t* status);
+int plume_merkle_leaf_batch_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* address, const uint8_t* amount, uint8_t* leaf32, uint8_t* status,
+                                   void* stream);
+int plume_merkle_tree_build(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf32, uint8_t* tree, uint32_t* leaf_pos);
+int plume_merkle_tree_build_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf32, uint8_t* tree, uint32_t* leaf_pos, void* stream);
+int plume_merkle_proof_batch(plume_ctx* ctx, size_t n, const uint8_t* tree, size_t m, const uint32_t* pos, size_t depth, uint8_t* proof, uint8_t* proof_len);
+int plume_merkle_proof_batch_device(plume_ctx* ctx, size_t n, const uint8_t* tree, size_t m, const uint32_t* pos, size_t depth, uint8_t* proof, uint8_t* proof_len,
+                                    void* stream);
+int plume_merkle_verify_batch(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* address_or_leaf, const uint8_t* amount, size_t depth,
+                              const uint8_t* proof, const uint8_t* proof_len, const uint8_t* root32, uint8_t* status);
+int plume_merkle_verify_batch_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* address_or_leaf, const uint8_t* amount, size_t depth,
+                                     const uint8_t* proof, const uint8_t* proof_len, const uint8_t* root32, uint8_t* status, void* stream);
 
 /* ---- persistent nullifier set: reject repeats across batches  (library 0.7) ----------------------------------
  * A consumer that verifies a STREAM of batches (a vote tally, a claim relayer, a rate limiter) must reject a nullifier it accepted any number of

@@ -164,6 +164,17 @@ def _load():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
+    # Keccak Merkle allow-lists (library 0.15; Engine.merkle_* raise PlumeHipError on an older build)
+    for name, args in (("plume_merkle_leaf_batch", [vp, i, i, sz] + [vp] * 4), ("plume_merkle_leaf_batch_device", [vp, i, i, sz] + [vp] * 5),
+                       ("plume_merkle_tree_build", [vp, i, sz] + [vp] * 3), ("plume_merkle_tree_build_device", [vp, i, sz] + [vp] * 4),
+                       ("plume_merkle_proof_batch", [vp, sz, vp, sz, vp, sz, vp, vp]), ("plume_merkle_proof_batch_device", [vp, sz, vp, sz, vp, sz, vp, vp, vp]),
+                       ("plume_merkle_verify_batch", [vp, i, i, sz, vp, vp, sz] + [vp] * 4), ("plume_merkle_verify_batch_device", [vp, i, i, sz, vp, vp, sz] + [vp] * 5)):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
+    fn = getattr(lib, "plume_merkle_max_proof_len", None)
+    if fn is not None:
+        fn.argtypes, fn.restype = [sz], C.c_void_p                                 # (a size_t: ctypes hands back None for 0)
     _lib = lib
     # (the 0.13 entry points are told by their symbols: plume_version() still begins "plume_hip 0.12")
     if (_version(lib) < (0, 12) or getattr(lib, "plume_ecdsa_sign_batch", None) is None) and not os.environ.get("PLUME_HIP_LIB"):
@@ -185,7 +196,9 @@ def exported_symbols():
             "plume_set_sign_selfcheck", "plume_get_sign_selfcheck", "plume_recover_batch", "plume_recover_batch_device",
             "plume_eth_address_batch", "plume_eth_address_batch_device", "plume_ecdsa_recover_batch", "plume_ecdsa_recover_batch_device",
             "plume_eth_message_hash_batch", "plume_eth_message_hash_batch_device", "plume_ecdsa_sign_batch", "plume_ecdsa_sign_batch_device",
-            "plume_eth_tx_parse_batch", "plume_eth_tx_parse_batch_device", "plume_eth_tx_sender_batch", "plume_eth_tx_sender_batch_device"]
+            "plume_eth_tx_parse_batch", "plume_eth_tx_parse_batch_device", "plume_eth_tx_sender_batch", "plume_eth_tx_sender_batch_device",
+            "plume_merkle_max_proof_len", "plume_merkle_leaf_batch", "plume_merkle_leaf_batch_device", "plume_merkle_tree_build", "plume_merkle_tree_build_device",
+            "plume_merkle_proof_batch", "plume_merkle_proof_batch_device", "plume_merkle_verify_batch", "plume_merkle_verify_batch_device"]
 
 
 def pack_messages(msgs):
@@ -225,6 +238,11 @@ ETH_HASH_MODES = {"keccak256": 0, "eip191": 1}
 ECDSA_SIGN_V27 = 1
 # plume_eth_tx_parse_batch (include/plume_hip.h): the status of an item (plume_eth_tx_sender_batch reports the recovery's: ECDSA_*)
 ETH_TX_OK, ETH_TX_INVALID = 1, 3
+# plume_merkle_* (include/plume_hip.h): leaf formats -> (PLUME_MERKLE_LEAF_*), the sort flag, the status of an item, the proof length of a refused index
+MERKLE_LEAF_FORMATS = {"hash32": 0, "address": 1, "address_uint256": 2}
+MERKLE_SORT_LEAVES = 1
+MERKLE_MISMATCH, MERKLE_MATCH, MERKLE_INVALID = 0, 1, 3
+MERKLE_BAD_PROOF = 255
 
 
 def parse_aggregate_record(rec):
@@ -629,6 +647,108 @@ class Engine:
                      _ptr(status)), "plume_eth_tx_sender_batch")
         return pk, address, status, chain_id, tx_type
 
+    def _merkle_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no Merkle trees: {name} came with library 0.15 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    @staticmethod
+    def _merkle_items(leaf_format, addr_format, items, amounts):
+        lf = MERKLE_LEAF_FORMATS[leaf_format]
+        if addr_format == "eip55":
+            af, W = ETH_ADDR_FORMATS[addr_format][0], 42                         # (the library refuses it: PLUME_ERR_ARG)
+        else:
+            af, W = ETH_ADDR_FORMATS[addr_format]
+        W = 32 if lf == 0 else W
+        items = np.ascontiguousarray(items, dtype=np.uint8)
+        if items.size % W:
+            raise ValueError(f"items: expected records of {W} bytes, got {items.size} bytes")
+        n = items.size // W
+        if lf == 2:
+            if amounts is None:
+                raise ValueError("the address_uint256 leaf needs amounts")
+            if not (isinstance(amounts, np.ndarray) and amounts.dtype == np.uint8):
+                amounts = np.frombuffer(b"".join(int(a).to_bytes(32, "big") for a in amounts), np.uint8)
+            amounts = _np(amounts, 32, n, "amounts")
+        else:
+            amounts = None
+        return lf, af, n, items, amounts
+
+    def merkle_max_proof_len(self, n):
+        """floor(log2(2n - 1)): the longest proof of a tree of n leaves (plume_merkle_max_proof_len)"""
+        return int(self._merkle_fn("plume_merkle_max_proof_len")(int(n)) or 0)
+
+    def merkle_leaf_batch(self, items, amounts=None, leaf_format="address", addr_format="raw20"):
+        """The leaves of an OpenZeppelin StandardMerkleTree (plume_merkle_leaf_batch).  leaf_format "address": Keccak(Keccak(abi.encode(address))), the tree of
+        ["address"]; "address_uint256": with amounts (integers, or n x 32 big-endian bytes), the tree of ["address", "uint256"]; "hash32": the items are the leaves.
+        items: n x 20 ("raw20") or n x 64 ("record64": what eth_address_batch, ecdsa_recover_batch and eth_tx_sender_batch write).  Returns (leaf n x 32, status):
+        MERKLE_MATCH, or MERKLE_INVALID and a zero leaf for a record64 whose first 44 bytes are not zero."""
+        fn = self._merkle_fn("plume_merkle_leaf_batch")
+        lf, af, n, items, amounts = self._merkle_items(leaf_format, addr_format, items, amounts)
+        leaf, status = np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        self._chk(fn(self._ctx, lf, af, n, _ptr(items), _ptr(amounts), _ptr(leaf), _ptr(status)), "plume_merkle_leaf_batch")
+        return leaf, status
+
+    def merkle_tree_build(self, leaves, sort=True):
+        """(tree (2n - 1) x 32, leaf_pos n uint32) of n >= 1 leaves of 32 bytes (plume_merkle_tree_build): tree[0] is the root, the leaves sit at the end in reverse,
+        sorted by (bytes, input index) when sort is set; leaf_pos[j] is the tree index of input leaf j."""
+        fn = self._merkle_fn("plume_merkle_tree_build")
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint8)
+        if leaves.size % 32:
+            raise ValueError(f"leaves: expected records of 32 bytes, got {leaves.size} bytes")
+        n = leaves.size // 32
+        tree, leaf_pos = np.zeros((max(2 * n - 1, 0), 32), np.uint8), np.zeros(n, np.uint32)
+        self._chk(fn(self._ctx, MERKLE_SORT_LEAVES if sort else 0, n, _ptr(leaves), _ptr(tree), _ptr(leaf_pos)), "plume_merkle_tree_build")
+        return tree, leaf_pos
+
+    def merkle_proof_batch(self, tree, pos, depth=None):
+        """The proofs of the tree indices pos (plume_merkle_proof_batch): (proof m x depth x 32, proof_len m).  depth defaults to the longest proof of the tree; unused
+        slots are zero; an index outside the tree, or a proof longer than depth, gives MERKLE_BAD_PROOF and zero slots."""
+        fn = self._merkle_fn("plume_merkle_proof_batch")
+        tree = np.ascontiguousarray(tree, dtype=np.uint8)
+        n = (tree.size // 32 + 1) // 2
+        if tree.size % 32 or tree.size // 32 != 2 * n - 1:
+            raise ValueError(f"tree: expected 2n - 1 nodes of 32 bytes, got {tree.size} bytes")
+        pos = np.ascontiguousarray(pos, dtype=np.uint32)
+        depth = self.merkle_max_proof_len(n) if depth is None else int(depth)
+        proof, proof_len = np.zeros((len(pos), depth, 32), np.uint8), np.zeros(len(pos), np.uint8)
+        self._chk(fn(self._ctx, n, _ptr(tree), len(pos), _ptr(pos), depth, _ptr(proof) if depth else None, _ptr(proof_len)), "plume_merkle_proof_batch")
+        return proof, proof_len
+
+    def merkle_verify_batch(self, items, proof, proof_len, root, amounts=None, leaf_format="address", addr_format="raw20"):
+        """MerkleProof.verify for every item against one root (plume_merkle_verify_batch).  items and amounts as merkle_leaf_batch takes them (the leaf is computed on the
+        GPU); proof: m x depth x 32, proof_len: m bytes.  Returns status: MERKLE_MATCH, MERKLE_MISMATCH, or MERKLE_INVALID (an invalid item, or proof_len above depth)."""
+        fn = self._merkle_fn("plume_merkle_verify_batch")
+        lf, af, m, items, amounts = self._merkle_items(leaf_format, addr_format, items, amounts)
+        proof = np.ascontiguousarray(proof, dtype=np.uint8)
+        if m == 0 or proof.size % (32 * m):
+            if m or proof.size:
+                raise ValueError(f"proof: expected {m} x depth x 32 bytes, got {proof.size} bytes")
+        depth = proof.size // (32 * m) if m else 0
+        proof_len = _np(proof_len, 1, m, "proof_len")
+        root = _np(root, 32, 1, "root")
+        status = np.zeros(m, np.uint8)
+        self._chk(fn(self._ctx, lf, af, m, _ptr(items), _ptr(amounts), depth, _ptr(proof) if depth else None, _ptr(proof_len), _ptr(root), _ptr(status)),
+                  "plume_merkle_verify_batch")
+        return status
+
+    def merkle_tree(self, items, amounts=None, sort=True, leaf_format=None, addr_format="raw20"):
+        """A MerkleTree over leaves (n x 32 bytes: leaf_format None or "hash32") or over addresses (leaf_format "address", or "address_uint256" when amounts are given):
+        the leaves, the tree and its proofs come from the GPU.  Raises ValueError when an address record is invalid."""
+        if leaf_format is None:
+            leaf_format = "address_uint256" if amounts is not None else "hash32" if len(items) and len(items[0]) == 32 else "address"
+        if not isinstance(items, np.ndarray):
+            items = np.frombuffer(b"".join(bytes(x) for x in items), np.uint8)
+        if leaf_format == "hash32":
+            leaves = np.ascontiguousarray(items, dtype=np.uint8).reshape(-1, 32)
+        else:
+            leaves, st = self.merkle_leaf_batch(items, amounts, leaf_format, addr_format)
+            if (st != MERKLE_MATCH).any():
+                raise ValueError(f"item {int(np.flatnonzero(st != MERKLE_MATCH)[0])} is no address record")
+        tree, leaf_pos = self.merkle_tree_build(leaves, sort)
+        return MerkleTree(self, tree, leaf_pos, leaf_format, addr_format)
+
     def verify_batch_sec1(self, version, msgs, msg_off, pk33, nullifier33, c, s, r_point33=None, hashed_to_curve_r33=None):
         """verify with 33-byte SEC1-compressed points (decompressed and validated on the GPU)"""
         n = len(msg_off) - 1
@@ -840,6 +960,43 @@ class Engine:
         self._chk(fn(self._ctx, ECDSA_LOW_S if low_s else 0, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(txs), d(tx_off), int(txs_bytes),
                      d(expect), d(pk), d(address), d(chain_id), d(tx_type), d(status), C.c_void_p(st)), "plume_eth_tx_sender_batch_device")
 
+    def merkle_leaf_batch_device(self, n, items, amounts, leaf32, status, leaf_format="address", addr_format="raw20", stream=None):
+        """the device form of merkle_leaf_batch on torch tensors; amounts (n x 32 big-endian bytes) and status may be None; one kernel on `stream` (None = current
+        stream); does not synchronise"""
+        import torch
+        fn = self._merkle_fn("plume_merkle_leaf_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, MERKLE_LEAF_FORMATS[leaf_format], ETH_ADDR_FORMATS[addr_format][0], int(n), d(items), d(amounts), d(leaf32), d(status), C.c_void_p(st)),
+                  "plume_merkle_leaf_batch_device")
+
+    def merkle_tree_build_device(self, n, leaf32, tree, leaf_pos, sort=True, stream=None):
+        """the device form of merkle_tree_build on torch tensors (tree: (2n - 1) x 32 bytes; leaf_pos: n 4-byte words, or None); enqueues on `stream` (None = current
+        stream); does not synchronise"""
+        import torch
+        fn = self._merkle_fn("plume_merkle_tree_build_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, MERKLE_SORT_LEAVES if sort else 0, int(n), d(leaf32), d(tree), d(leaf_pos), C.c_void_p(st)), "plume_merkle_tree_build_device")
+
+    def merkle_proof_batch_device(self, n, tree, m, pos, depth, proof, proof_len, stream=None):
+        """the device form of merkle_proof_batch on torch tensors (pos: m 4-byte words; proof: m x depth x 32 bytes; proof_len: m bytes); one kernel on `stream` (None =
+        current stream); does not synchronise"""
+        import torch
+        fn = self._merkle_fn("plume_merkle_proof_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, int(n), d(tree), int(m), d(pos), int(depth), d(proof), d(proof_len), C.c_void_p(st)), "plume_merkle_proof_batch_device")
+
+    def merkle_verify_batch_device(self, m, items, amounts, depth, proof, proof_len, root32, status, leaf_format="address", addr_format="raw20", stream=None):
+        """the device form of merkle_verify_batch on torch tensors; amounts may be None; one kernel on `stream` (None = current stream); does not synchronise"""
+        import torch
+        fn = self._merkle_fn("plume_merkle_verify_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, MERKLE_LEAF_FORMATS[leaf_format], ETH_ADDR_FORMATS[addr_format][0], int(m), d(items), d(amounts), int(depth), d(proof), d(proof_len),
+                     d(root32), d(status), C.c_void_p(st)), "plume_merkle_verify_batch_device")
+
     def ecdsa_sign_batch_device(self, n, hash, sk, aux, r, s, v, status, v27=False, stream=None):
         """the device form of ecdsa_sign_batch on torch tensors; aux may be None; enqueues on `stream` (None = current stream); does not synchronise"""
         import torch
@@ -937,6 +1094,26 @@ class Engine:
         ms = C.c_float()
         t = self._lib.plume_microbench_last_ticks(C.byref(ms))
         return float(t), float(ms.value)
+
+
+class MerkleTree:
+    """A tree built by Engine.merkle_tree: .root (32 bytes), .tree ((2n - 1) x 32 uint8), .leaf_pos (n uint32: the tree index of input item j), .n, and
+    .proofs(indices): the proofs of the INPUT items `indices` (all of them by default) as (proof m x depth x 32, proof_len m), from the GPU."""
+
+    def __init__(self, engine, tree, leaf_pos, leaf_format, addr_format):
+        self.engine, self.tree, self.leaf_pos, self.leaf_format, self.addr_format = engine, tree, leaf_pos, leaf_format, addr_format
+        self.n = len(leaf_pos)
+        self.root = tree[0].tobytes()
+        self.depth = engine.merkle_max_proof_len(self.n)
+
+    def proofs(self, indices=None):
+        idx = np.arange(self.n) if indices is None else np.asarray(indices, dtype=np.int64)
+        return self.engine.merkle_proof_batch(self.tree, self.leaf_pos[idx], self.depth)
+
+    def proof(self, index):
+        """the proof of input item `index` as a list of 32-byte strings"""
+        p, ln = self.proofs([index])
+        return [p[0, s].tobytes() for s in range(int(ln[0]))]
 
 
 def _version(lib):

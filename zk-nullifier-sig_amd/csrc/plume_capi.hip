@@ -34,6 +34,7 @@
 #include "plume_host_logic.h"
 #include "plume_keccak.h"
 #include "plume_launch.h"
+#include "plume_merkle.h"
 #include "plume_nonce.h"
 #include "plume_recover.h"
 #include "plume_selfcheck.h"
@@ -183,6 +184,7 @@ struct plume_ctx {
     int sign_selfcheck = 0;                                        // plume_set_sign_selfcheck: 1 = every sign call stages its outputs here, verifies them and releases what verifies (sign_device)
     DevBuf scstage;                                                // ... the staging: six records in the 64-byte form, the signer's status and the check's verdict, 322 B / item; wiped after the release
     DevBuf txstage;                                                // plume_eth_tx_sender_batch: what k_eth_tx_parse hands the recover stages -- hash, r, s, v, 97 B / item (public data: not wiped)
+    DevBuf mrksort;                                                // plume_merkle_tree_build: the sort's records, nine word arrays of npad words, 36 B / padded leaf (public data: not wiped)
     DevBuf nonce;                                                  // the derived-nonce signer: r of the call in flight, 32 B / item, wiped on the call's stream after sign_final
     int eq1_short = 1;                                             // verify calls that give R: equation 1 in its short form (plume_eis.h).  0 = long form always (A/B), 2 = test: every item takes the fallback
     size_t eq1_short_min = (size_t)1 << 16;                        // ... for calls of at least this many items.  Round 6 sweep on one box, interleaved (profiles/r06_eq1_threshold.txt), now that the
@@ -304,7 +306,7 @@ static void destroy_single(plume_ctx* ctx) {
     if (ctx->ws_used && ctx->ws_free) (void)hipEventSynchronize(ctx->ws_free);
     for (hipStream_t q : {ctx->stream, ctx->up, ctx->down, ctx->side, ctx->pre}) if (q) (void)hipStreamSynchronize(q);
     for (DevBuf* b : {&ctx->bases, &ctx->jobflags, &ctx->itemflags, &ctx->tab, &ctx->tabscr, &ctx->res, &ctx->resinf, &ctx->res2, &ctx->res2inf, &ctx->pkaff,
-                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->scstage, &ctx->txstage, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
+                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->scstage, &ctx->txstage, &ctx->mrksort, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
         b->release();
     for (DevBuf& b : ctx->agg) b.release();
     if (ctx->fixed) {
@@ -2195,6 +2197,236 @@ int plume::capi_eth_tx_sender(plume_ctx* ctx, int flags, int pk_format, int addr
         return eth_tx_sender_host(sh, flags, pk_format, addr_format, hi - lo, txs, tx_off + lo, expect ? expect + 20 * lo : nullptr, pk ? pk + P * lo : nullptr,
                                   address ? address + W * lo : nullptr, chain_id ? chain_id + lo : nullptr, tx_type ? tx_type + lo : nullptr, status ? status + lo : nullptr,
                                   tx_fn, fn);
+    });
+}
+// The Merkle calls (plume_capi_internal.h): the ABI and the launchers live in plume_merkle_capi.hip.  leaf and verify are the address call over again: per-item kernels
+// on the caller's arrays, no table, no workspace.  build and proof work on one tree, so their host-pointer forms never split: a plume_init_multi context runs them on its
+// first shard, the whole tree staged in that context's first slot.  build's sort keeps its records in ctx->mrksort, so the device form holds the workspace like the
+// transaction sender does.
+static int merkle_formats_ok(int leaf_format, int addr_format, const MerkleLaunch* fn) {
+    if (!fn || !fn->leaf || !fn->sort || !fn->place || !fn->level || !fn->top || !fn->proof || !fn->verify) return fail(PLUME_ERR_ARG, "the Merkle kernels are not part of this build");
+    if (leaf_format != PLUME_MRK_LEAF_HASH32 && leaf_format != PLUME_MRK_LEAF_ADDRESS && leaf_format != PLUME_MRK_LEAF_ADDRESS_UINT256)
+        return fail(PLUME_ERR_ARG, "leaf_format must be 0, 1 or 2");
+    if (addr_format != PLUME_ETHK_ADDR_RAW20 && addr_format != PLUME_ETHK_ADDR_RECORD64) return fail(PLUME_ERR_ARG, "addr_format must be 0 or 1: a leaf is made of address bytes, not of EIP-55 text");
+    return 0;
+}
+static int merkle_leaf_args_ok(int leaf_format, int addr_format, size_t n, const void* in, const void* amount, const void* leaf, const MerkleLaunch* fn) {
+    if (int rc = merkle_formats_ok(leaf_format, addr_format, fn)) return rc;
+    if (n && (!in || !leaf || (leaf_format == PLUME_MRK_LEAF_ADDRESS_UINT256 && !amount))) return fail(PLUME_ERR_ARG, "null array");
+    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
+    return 0;
+}
+static int merkle_leaf_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* in, const uint8_t* amount, uint8_t* leaf, uint8_t* status,
+                              hipStream_t st, const MerkleLaunch* fn) {
+    if (n == 0) return 0;
+    MerkleLeafArgs a; a.leaf_format = leaf_format; a.addr_format = addr_format; a.n = (uint32_t)n; a.in = in; a.amount = amount; a.leaf = leaf; a.status = status;
+    ctx->timer.begin(st);
+    fn->leaf(a, st); ctx->timer.stage("merkle_leaf", st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int plume::capi_merkle_leaf_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* address, const uint8_t* amount, uint8_t* leaf32, uint8_t* status,
+                                   void* stream, const MerkleLaunch* fn) {
+    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = merkle_leaf_args_ok(leaf_format, addr_format, n, address, amount, leaf32, fn)) return rc;
+    return merkle_leaf_device(ctx, leaf_format, addr_format, n, address, amount, leaf32, status, st_, fn);
+}
+static int merkle_leaf_host(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* in, const uint8_t* amount, uint8_t* leaf, uint8_t* status,
+                            const MerkleLaunch* fn) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HostSlot& sl = ctx->slot[0];
+    hipStream_t st = ctx->stream;
+    const size_t W = mrk_item_width(leaf_format, addr_format);
+    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
+        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
+        if (sl.in[0].ensure(W * cnt) || (amount && sl.in[1].ensure(32 * cnt)) || sl.out[0].ensure(32 * cnt) || (status && sl.out[1].ensure(cnt))) return PLUME_ERR_HIP;
+        HIPCHK(hipMemcpyAsync(sl.in[0].p, in + W * i0, W * cnt, hipMemcpyHostToDevice, st));
+        hipError_t e = hipSuccess;
+        if (amount) e = hipMemcpyAsync(sl.in[1].p, amount + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st);
+        int rc = e != hipSuccess ? fail(PLUME_ERR_HIP, std::string("amount upload: ") + hipGetErrorString(e))
+                                 : merkle_leaf_device(ctx, leaf_format, addr_format, cnt, sl.in[0].as<uint8_t>(), amount ? sl.in[1].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(),
+                                                      status ? sl.out[1].as<uint8_t>() : nullptr, st, fn);
+        if (int rc2 = eth_tx_drain_piece(rc, st, {{leaf + 32 * i0, sl.out[0].p, 32 * cnt}, {status ? status + i0 : nullptr, sl.out[1].p, cnt}})) return rc2;
+    }
+    return 0;
+}
+int plume::capi_merkle_leaf(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* address, const uint8_t* amount, uint8_t* leaf32, uint8_t* status,
+                            const MerkleLaunch* fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = merkle_leaf_args_ok(leaf_format, addr_format, n, address, amount, leaf32, fn)) return rc;
+    if (n == 0) return 0;
+    if (leaf_format != PLUME_MRK_LEAF_ADDRESS_UINT256) amount = nullptr;
+    if (ctx->shards.empty()) return merkle_leaf_host(ctx, leaf_format, addr_format, n, address, amount, leaf32, status, fn);
+    const size_t W = mrk_item_width(leaf_format, addr_format);
+    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
+        return merkle_leaf_host(sh, leaf_format, addr_format, hi - lo, address + W * lo, amount ? amount + 32 * lo : nullptr, leaf32 + 32 * lo, status ? status + lo : nullptr, fn);
+    });
+}
+static int merkle_build_args_ok(int flags, size_t n, const void* leaf, const void* tree, const MerkleLaunch* fn) {
+    if (int rc = merkle_formats_ok(PLUME_MRK_LEAF_HASH32, PLUME_ETHK_ADDR_RAW20, fn)) return rc;
+    if (flags & ~PLUME_MRK_SORT_LEAVES) return fail(PLUME_ERR_ARG, "unknown flag bits");
+    if (n == 0 || n > PLUME_MRK_MAX_N) return fail(PLUME_ERR_ARG, "a tree has between 1 and 2^26 leaves");
+    if (!leaf || !tree) return fail(PLUME_ERR_ARG, "null array");
+    return 0;
+}
+static int merkle_build_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf, uint8_t* tree, uint32_t* leaf_pos, hipStream_t st, const MerkleLaunch* fn) {
+    const bool sorted = (flags & PLUME_MRK_SORT_LEAVES) && n > 1;
+    const uint32_t npad = mrk_next_pow2((uint32_t)n);
+    if (int rc = ws_acquire(ctx, st)) return rc;
+    WsHold hold(ctx, st);
+    if (sorted && ctx->mrksort.ensure((size_t)PLUME_MRK_REC_WORDS * 4 * npad)) return PLUME_ERR_HIP;
+    ctx->timer.begin(st);
+    if (sorted) {
+        MerkleSortArgs sa; sa.n = (uint32_t)n; sa.npad = npad; sa.tile = npad < PLUME_MRK_TILE ? npad : PLUME_MRK_TILE; sa.leaf = leaf; sa.ws = ctx->mrksort.as<uint32_t>();
+        fn->sort(sa, st); ctx->timer.stage("merkle_sort", st);
+    }
+    MerkleTreeArgs ta; ta.n = (uint32_t)n; ta.npad = npad; ta.leaf = leaf; ta.ws = sorted ? ctx->mrksort.as<uint32_t>() : nullptr; ta.tree = tree; ta.leaf_pos = leaf_pos;
+    fn->place(ta, st); ctx->timer.stage("merkle_place", st);
+    if (n >= 2) {
+        const char* e = std::getenv("PLUME_MERKLE_FUSED_TOP");                           // A/B knob (tests/gpu_debug/merkle_timing.py): 0 = one launch per depth all the way up
+        const bool fused = !(e && std::atoi(e) == 0);
+        uint32_t d = mrk_parent_depth((uint32_t)n) + 1u;
+        const uint32_t stop = fused ? PLUME_MRK_TOP_DEPTH + 1u : 0u;
+        if (d > stop) {
+            while (d-- > stop) fn->level(tree, (uint32_t)n, d, st);
+            d = stop;
+            ctx->timer.stage("merkle_levels", st);
+        }
+        if (fused) { fn->top(tree, (uint32_t)n, d - 1u, st); ctx->timer.stage("merkle_top", st); }
+    }
+    HIPCHK(hipGetLastError());
+    return hold.release();
+}
+int plume::capi_merkle_tree_build_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf32, uint8_t* tree, uint32_t* leaf_pos, void* stream, const MerkleLaunch* fn) {
+    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = merkle_build_args_ok(flags, n, leaf32, tree, fn)) return rc;
+    return merkle_build_device(ctx, flags, n, leaf32, tree, leaf_pos, st_, fn);
+}
+int plume::capi_merkle_tree_build(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf32, uint8_t* tree, uint32_t* leaf_pos, const MerkleLaunch* fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = merkle_build_args_ok(flags, n, leaf32, tree, fn)) return rc;
+    if (!ctx->shards.empty()) ctx = ctx->shards[0];                             // one tree: one device holds all of it
+    HIPCHK(hipSetDevice(ctx->device));
+    HostSlot& sl = ctx->slot[0];
+    hipStream_t st = ctx->stream;
+    const size_t tb = 32 * (2 * n - 1);
+    if (sl.in[0].ensure(32 * n) || sl.out[0].ensure(tb) || (leaf_pos && sl.out[1].ensure(4 * n))) return PLUME_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(sl.in[0].p, leaf32, 32 * n, hipMemcpyHostToDevice, st));
+    const int rc = merkle_build_device(ctx, flags, n, sl.in[0].as<uint8_t>(), sl.out[0].as<uint8_t>(), leaf_pos ? sl.out[1].as<uint32_t>() : nullptr, st, fn);
+    return eth_tx_drain_piece(rc, st, {{tree, sl.out[0].p, tb}, {leaf_pos, sl.out[1].p, 4 * n}});
+}
+static int merkle_proof_args_ok(size_t n, const void* tree, size_t m, const void* pos, size_t depth, const void* proof, const void* proof_len, const MerkleLaunch* fn) {
+    if (int rc = merkle_formats_ok(PLUME_MRK_LEAF_HASH32, PLUME_ETHK_ADDR_RAW20, fn)) return rc;
+    if (n == 0 || n > PLUME_MRK_MAX_N) return fail(PLUME_ERR_ARG, "a tree has between 1 and 2^26 leaves");
+    if (depth > PLUME_MRK_MAX_DEPTH) return fail(PLUME_ERR_ARG, "depth above 64");
+    if (m > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "m too large");
+    if (m && (!tree || !pos || !proof_len || (depth && !proof))) return fail(PLUME_ERR_ARG, "null array");
+    return 0;
+}
+static int merkle_proof_device(plume_ctx* ctx, size_t n, const uint8_t* tree, size_t m, const uint32_t* pos, size_t depth, uint8_t* proof, uint8_t* proof_len, hipStream_t st,
+                               const MerkleLaunch* fn) {
+    if (m == 0) return 0;
+    MerkleProofArgs a; a.n = (uint32_t)n; a.m = (uint32_t)m; a.depth = (uint32_t)depth; a.tree = tree; a.pos = pos; a.proof = proof; a.proof_len = proof_len;
+    ctx->timer.begin(st);
+    fn->proof(a, st); ctx->timer.stage("merkle_proof", st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int plume::capi_merkle_proof_device(plume_ctx* ctx, size_t n, const uint8_t* tree, size_t m, const uint32_t* pos, size_t depth, uint8_t* proof, uint8_t* proof_len,
+                                    void* stream, const MerkleLaunch* fn) {
+    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = merkle_proof_args_ok(n, tree, m, pos, depth, proof, proof_len, fn)) return rc;
+    return merkle_proof_device(ctx, n, tree, m, pos, depth, proof, proof_len, st_, fn);
+}
+int plume::capi_merkle_proof(plume_ctx* ctx, size_t n, const uint8_t* tree, size_t m, const uint32_t* pos, size_t depth, uint8_t* proof, uint8_t* proof_len,
+                             const MerkleLaunch* fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = merkle_proof_args_ok(n, tree, m, pos, depth, proof, proof_len, fn)) return rc;
+    if (m == 0) return 0;
+    if (!ctx->shards.empty()) ctx = ctx->shards[0];                             // the tree is staged once: one device answers every index
+    HIPCHK(hipSetDevice(ctx->device));
+    HostSlot& sl = ctx->slot[0];
+    hipStream_t st = ctx->stream;
+    const size_t tb = 32 * (2 * n - 1), pb = 32 * depth;
+    if (sl.in[0].ensure(tb)) return PLUME_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(sl.in[0].p, tree, tb, hipMemcpyHostToDevice, st));
+    for (size_t i0 = 0; i0 < m; i0 += ctx->chunk) {
+        const size_t cnt = m - i0 < ctx->chunk ? m - i0 : ctx->chunk;
+        hipError_t e = hipSuccess;
+        if (sl.in[1].ensure(4 * cnt) || (pb && sl.out[0].ensure(pb * cnt)) || sl.out[1].ensure(cnt) ||
+            (e = hipMemcpyAsync(sl.in[1].p, pos + i0, 4 * cnt, hipMemcpyHostToDevice, st)) != hipSuccess) {
+            (void)hipStreamSynchronize(st);
+            return e != hipSuccess ? fail(PLUME_ERR_HIP, std::string("index upload: ") + hipGetErrorString(e)) : PLUME_ERR_HIP;
+        }
+        const int rc = merkle_proof_device(ctx, n, sl.in[0].as<uint8_t>(), cnt, sl.in[1].as<uint32_t>(), depth, pb ? sl.out[0].as<uint8_t>() : nullptr, sl.out[1].as<uint8_t>(), st, fn);
+        if (int rc2 = eth_tx_drain_piece(rc, st, {{pb ? proof + pb * i0 : nullptr, sl.out[0].p, pb * cnt}, {proof_len + i0, sl.out[1].p, cnt}})) return rc2;
+    }
+    return 0;
+}
+static int merkle_verify_args_ok(int leaf_format, int addr_format, size_t m, const void* in, const void* amount, size_t depth, const void* proof, const void* proof_len,
+                                 const void* root, const void* status, const MerkleLaunch* fn) {
+    if (int rc = merkle_formats_ok(leaf_format, addr_format, fn)) return rc;
+    if (depth > PLUME_MRK_MAX_DEPTH) return fail(PLUME_ERR_ARG, "depth above 64");
+    if (m > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "m too large");
+    if (m && (!in || !proof_len || !root || !status || (depth && !proof) || (leaf_format == PLUME_MRK_LEAF_ADDRESS_UINT256 && !amount))) return fail(PLUME_ERR_ARG, "null array");
+    return 0;
+}
+static int merkle_verify_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* in, const uint8_t* amount, size_t depth, const uint8_t* proof,
+                                const uint8_t* proof_len, const uint8_t* root, uint8_t* status, hipStream_t st, const MerkleLaunch* fn) {
+    if (m == 0) return 0;
+    MerkleVerifyArgs a; a.leaf_format = leaf_format; a.addr_format = addr_format; a.m = (uint32_t)m; a.depth = (uint32_t)depth; a.in = in; a.amount = amount; a.proof = proof;
+    a.proof_len = proof_len; a.root = root; a.status = status;
+    ctx->timer.begin(st);
+    fn->verify(a, st); ctx->timer.stage("merkle_verify", st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int plume::capi_merkle_verify_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* address_or_leaf, const uint8_t* amount, size_t depth,
+                                     const uint8_t* proof, const uint8_t* proof_len, const uint8_t* root32, uint8_t* status, void* stream, const MerkleLaunch* fn) {
+    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = merkle_verify_args_ok(leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, fn)) return rc;
+    return merkle_verify_device(ctx, leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, st_, fn);
+}
+static int merkle_verify_host(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* in, const uint8_t* amount, size_t depth, const uint8_t* proof,
+                              const uint8_t* proof_len, const uint8_t* root, uint8_t* status, const MerkleLaunch* fn) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HostSlot& sl = ctx->slot[0];
+    hipStream_t st = ctx->stream;
+    const size_t W = mrk_item_width(leaf_format, addr_format), pb = 32 * depth;
+    if (sl.in[4].ensure(32)) return PLUME_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(sl.in[4].p, root, 32, hipMemcpyHostToDevice, st));
+    for (size_t i0 = 0; i0 < m; i0 += ctx->chunk) {
+        const size_t cnt = m - i0 < ctx->chunk ? m - i0 : ctx->chunk;
+        hipError_t e = hipSuccess;
+        if (sl.in[0].ensure(W * cnt) || (amount && sl.in[1].ensure(32 * cnt)) || (pb && sl.in[2].ensure(pb * cnt)) || sl.in[3].ensure(cnt) || sl.out[0].ensure(cnt) ||
+            (e = hipMemcpyAsync(sl.in[0].p, in + W * i0, W * cnt, hipMemcpyHostToDevice, st)) != hipSuccess ||
+            (amount && (e = hipMemcpyAsync(sl.in[1].p, amount + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st)) != hipSuccess) ||
+            (pb && (e = hipMemcpyAsync(sl.in[2].p, proof + pb * i0, pb * cnt, hipMemcpyHostToDevice, st)) != hipSuccess) ||
+            (e = hipMemcpyAsync(sl.in[3].p, proof_len + i0, cnt, hipMemcpyHostToDevice, st)) != hipSuccess) {
+            (void)hipStreamSynchronize(st);
+            return e != hipSuccess ? fail(PLUME_ERR_HIP, std::string("proof upload: ") + hipGetErrorString(e)) : PLUME_ERR_HIP;
+        }
+        const int rc = merkle_verify_device(ctx, leaf_format, addr_format, cnt, sl.in[0].as<uint8_t>(), amount ? sl.in[1].as<uint8_t>() : nullptr, depth,
+                                            pb ? sl.in[2].as<uint8_t>() : nullptr, sl.in[3].as<uint8_t>(), sl.in[4].as<uint8_t>(), sl.out[0].as<uint8_t>(), st, fn);
+        if (int rc2 = eth_tx_drain_piece(rc, st, {{status + i0, sl.out[0].p, cnt}})) return rc2;
+    }
+    return 0;
+}
+int plume::capi_merkle_verify(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* address_or_leaf, const uint8_t* amount, size_t depth,
+                              const uint8_t* proof, const uint8_t* proof_len, const uint8_t* root32, uint8_t* status, const MerkleLaunch* fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = merkle_verify_args_ok(leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, fn)) return rc;
+    if (m == 0) return 0;
+    if (leaf_format != PLUME_MRK_LEAF_ADDRESS_UINT256) amount = nullptr;
+    if (ctx->shards.empty()) return merkle_verify_host(ctx, leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, fn);
+    const size_t W = mrk_item_width(leaf_format, addr_format), pb = 32 * depth;
+    return for_shards(ctx, m, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
+        return merkle_verify_host(sh, leaf_format, addr_format, hi - lo, address_or_leaf + W * lo, amount ? amount + 32 * lo : nullptr, depth, pb ? proof + pb * lo : nullptr,
+                                  proof_len + lo, root32, status + lo, fn);
     });
 }
 // The ECDSA signer (plume_capi_internal.h): the ABI and the launchers live in plume_ecdsa_sign_capi.hip.  The table of G is the signer's -- the comb, or at level 2 the

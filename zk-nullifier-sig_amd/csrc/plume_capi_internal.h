@@ -1,4 +1,4 @@
-// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_eth_hash_capi.hip, plume_ecdsa_capi.hip, plume_ecdsa_sign_capi.hip, plume_eth_tx_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
+// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_eth_hash_capi.hip, plume_ecdsa_capi.hip, plume_ecdsa_sign_capi.hip, plume_eth_tx_capi.hip, plume_merkle_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -102,6 +102,44 @@ __attribute__((visibility("hidden"))) int capi_eth_tx_sender_device(plume_ctx* c
                                                                     const uint64_t* tx_off, size_t txs_bytes, const uint8_t* expect, uint8_t* pk, uint8_t* address,
                                                                     uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream, EthTxLaunch tx_fn,
                                                                     const EcdsaLaunch* fn);
+
+// The Merkle calls (plume_merkle_leaf_batch*, plume_merkle_tree_build*, plume_merkle_proof_batch*, plume_merkle_verify_batch*).  leaf and verify are per-item calls on the
+// caller's arrays, routed like the address call (chunks through the first slot, the shards of a plume_init_multi context; the device forms one kernel, no workspace).
+// build and proof work on ONE tree: the host-pointer forms run on the context itself or on its first shard, the whole tree staged in the first slot; build's sort
+// takes its workspace (36 B per padded leaf) from the context, so its device form joins the ws_free chain.  fused_top = 0 (env PLUME_MERKLE_FUSED_TOP=0, the A/B
+// knob of tests/gpu_debug/merkle_timing.py) runs one k_merkle_level launch per depth instead of k_merkle_top.  The launchers come in as a hook struct.
+struct MerkleLeafArgs;
+struct MerkleSortArgs;
+struct MerkleTreeArgs;
+struct MerkleProofArgs;
+struct MerkleVerifyArgs;
+struct MerkleLaunch {
+    void (*leaf)(const MerkleLeafArgs& a, hipStream_t st);
+    void (*sort)(const MerkleSortArgs& a, hipStream_t st);
+    void (*place)(const MerkleTreeArgs& a, hipStream_t st);
+    void (*level)(uint8_t* tree, uint32_t n, uint32_t d, hipStream_t st);
+    void (*top)(uint8_t* tree, uint32_t n, uint32_t dtop, hipStream_t st);
+    void (*proof)(const MerkleProofArgs& a, hipStream_t st);
+    void (*verify)(const MerkleVerifyArgs& a, hipStream_t st);
+};
+__attribute__((visibility("hidden"))) int capi_merkle_leaf(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* address, const uint8_t* amount,
+                                                           uint8_t* leaf32, uint8_t* status, const MerkleLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_merkle_leaf_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* address, const uint8_t* amount,
+                                                                  uint8_t* leaf32, uint8_t* status, void* stream, const MerkleLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_merkle_tree_build(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf32, uint8_t* tree, uint32_t* leaf_pos,
+                                                                 const MerkleLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_merkle_tree_build_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf32, uint8_t* tree, uint32_t* leaf_pos,
+                                                                        void* stream, const MerkleLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_merkle_proof(plume_ctx* ctx, size_t n, const uint8_t* tree, size_t m, const uint32_t* pos, size_t depth, uint8_t* proof,
+                                                            uint8_t* proof_len, const MerkleLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_merkle_proof_device(plume_ctx* ctx, size_t n, const uint8_t* tree, size_t m, const uint32_t* pos, size_t depth,
+                                                                   uint8_t* proof, uint8_t* proof_len, void* stream, const MerkleLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_merkle_verify(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* address_or_leaf,
+                                                             const uint8_t* amount, size_t depth, const uint8_t* proof, const uint8_t* proof_len, const uint8_t* root32,
+                                                             uint8_t* status, const MerkleLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_merkle_verify_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* address_or_leaf,
+                                                                    const uint8_t* amount, size_t depth, const uint8_t* proof, const uint8_t* proof_len,
+                                                                    const uint8_t* root32, uint8_t* status, void* stream, const MerkleLaunch* fn);
 
 // The ECDSA signer (plume_ecdsa_sign_batch*): nonce, the comb, the conversion to affine, finalize; with plume_set_sign_selfcheck on, the recover stages over the staged
 // signatures and the release kernel behind them.  The launchers of its own kernels come in as a hook struct, with the recover stages' hooks beside them; the conversion and

@@ -21,7 +21,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .capi import ECDSA_INVALID, ETH_INVALID, ETH_MATCH, ETH_TX_OK, RECOVER_INVALID, RECOVER_MATCH, Engine, default_engine, pack_messages
+from .capi import ECDSA_INVALID, ETH_INVALID, ETH_MATCH, ETH_TX_OK, MERKLE_MATCH, RECOVER_INVALID, RECOVER_MATCH, Engine, default_engine, pack_messages
 
 DST = b"QUUX-V01-CS02-with-secp256k1_XMD:SHA-256_SSWU_RO_"  # rust-k256/src/lib.rs:61
 _P = 2**256 - 2**32 - 977
@@ -172,6 +172,16 @@ class PlumeSignature:  # rust-k256/src/lib.rs:67-80
             raise ValueError("addr20: 20 raw bytes")
         _, status = self._eth(engine, "raw20", expect=addr20)
         return int(status[0]) == ETH_MATCH and self.verify(engine)
+
+    def verify_for_root(self, root32: bytes, proof, amount: Optional[int] = None, engine: Optional[Engine] = None) -> bool:
+        """verify() AND "pk's address is on the allow-list whose Merkle root is root32": pk -> address -> leaf -> proof, the sibling of verify_for_address for a consumer
+        that holds one 32-byte root (OpenZeppelin's StandardMerkleTree of ["address"], or of ["address", "uint256"] when `amount` is given) and takes a proof from every
+        claimant.  proof: the 32-byte siblings, leaf side first.  False for a pk that has no address."""
+        eng = engine or default_engine()
+        address, status = self._eth(eng, "raw20")
+        if int(status[0]) == ETH_INVALID:
+            return False
+        return merkle_verify(address[0].tobytes(), proof, root32, amount, eng) and self.verify(eng)
 
     def recover_v1specific(self, engine: Optional[Engine] = None) -> PlumeSignatureV1Fields:
         """The V1-specific fields that pk, nullifier, c, s imply -- r_point = s G - c pk, hashed_to_curve_r = s H - c nullifier, recomputed on the GPU
@@ -441,3 +451,38 @@ def sign(rng, keypair: Tuple[AffinePoint, int], message: bytes, version: PlumeVe
     """plume_arkworks::sign (rust-arkworks/src/lib.rs:281-291): r = Fr::rand(rng)"""
     r = int.from_bytes(rng.fill_bytes(48), "big") % _N
     return sign_with_r(keypair, message, r, version, engine)
+
+
+def merkle_leaf(address20: bytes, amount: Optional[int] = None, engine: Optional[Engine] = None) -> bytes:
+    """The leaf of one account in OpenZeppelin's StandardMerkleTree, made on the GPU (plume_merkle_leaf_batch): Keccak(Keccak(abi.encode(address))) for the tree of
+    ["address"], Keccak(Keccak(abi.encode(address, amount))) for the tree of ["address", "uint256"] when amount is given."""
+    if len(bytes(address20)) != 20:
+        raise ValueError("merkle_leaf: address20 is 20 raw bytes")
+    leaf, _ = (engine or default_engine()).merkle_leaf_batch(np.frombuffer(bytes(address20), dtype=np.uint8), None if amount is None else [int(amount)],
+                                                             "address" if amount is None else "address_uint256")
+    return leaf[0].tobytes()
+
+
+def merkle_root(leaves, sort: bool = True, engine: Optional[Engine] = None) -> bytes:
+    """The root of the tree over 32-byte leaves, built on the GPU (plume_merkle_tree_build); sort: order the leaves by hash first, as StandardMerkleTree does"""
+    return (engine or default_engine()).merkle_tree(leaves, sort=sort, leaf_format="hash32").root
+
+
+def merkle_proof(leaves, index: int, sort: bool = True, engine: Optional[Engine] = None):
+    """The proof of leaf `index` of the tree over 32-byte leaves, as a list of 32-byte siblings (plume_merkle_tree_build, plume_merkle_proof_batch)"""
+    return (engine or default_engine()).merkle_tree(leaves, sort=sort, leaf_format="hash32").proof(index)
+
+
+def merkle_verify(leaf, proof, root32: bytes, amount: Optional[int] = None, engine: Optional[Engine] = None) -> bool:
+    """MerkleProof.verify on the GPU (plume_merkle_verify_batch).  leaf: 32 bytes, a leaf as it is; or 20 bytes, an address whose leaf is computed first (with `amount`
+    for the tree of ["address", "uint256"]).  proof: the 32-byte siblings, leaf side first."""
+    leaf, proof = bytes(leaf), [bytes(p) for p in proof]
+    if len(leaf) not in (20, 32) or any(len(p) != 32 for p in proof) or len(bytes(root32)) != 32:
+        raise ValueError("merkle_verify: leaf is 32 bytes (or a 20-byte address), proof elements and root are 32 bytes")
+    if len(proof) > 64:
+        return False
+    fmt = "hash32" if len(leaf) == 32 else "address" if amount is None else "address_uint256"
+    a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
+    st = (engine or default_engine()).merkle_verify_batch(a(leaf), a(b"".join(proof)).reshape(1, len(proof), 32), np.array([len(proof)], dtype=np.uint8), a(bytes(root32)),
+                                                          None if fmt != "address_uint256" else [int(amount)], fmt)
+    return int(st[0]) == MERKLE_MATCH
