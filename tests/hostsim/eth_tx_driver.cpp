@@ -4,7 +4,7 @@
 // n + 1 u64 offsets, the bytes, then what the parse writes (hash, r, s 32 n each; v, tx_type, status n each; chain_id 8 n) and what the sender writes under
 // PLUME_ECDSA_LOW_S in the 64-byte / raw formats (pk 64 n, address 20 n, status n).  Every call on a range of the items must reproduce those bytes: the host form with
 // chunks of 1, 7 and n, pageable and page-locked arrays, optional outputs absent, the device form on a caller stream (which must not have run anything when the call
-// returns, under the lazy scheduler), plume_init_multi contexts over three and eight mock devices, argument errors, the stage lists, and every allocation of a call
+// returns, under the lazy scheduler), plume_init_multi contexts over three and eight mock devices, empty items of a null buffer on one device and on several, argument errors, the stage lists, and every allocation of a call
 // failing in turn: an error code, untouched outputs, the outputs of a repeated call right, nothing leaked.  A context that only parses builds no table.
 #include <hip/hip_runtime.h>
 
@@ -136,6 +136,32 @@ static void group(plume_ctx* ctx, const char* what, int calls, bool device_form,
     if (st) REQUIRE(hipStreamDestroy(st) == hipSuccess);
 }
 
+// a batch of empty items needs no buffer: txs may be null when the offsets give it no bytes.  Every item comes out as the vectors' own empty item does, whichever piece
+// or shard it falls to
+static void group_null_buffer(plume_ctx* ctx, const char* what, size_t chunk) {
+    g_what = what;
+    size_t j = 0;
+    while (j < g_n && g_off[j + 1] != g_off[j]) j++;
+    REQUIRE(j < g_n);                                                                  // the vectors hold an empty item
+    if (chunk) REQUIRE(plume_set_chunk(ctx, chunk) == 0);
+    constexpr size_t m = 11;
+    const std::vector<uint64_t> off(m + 1, 5);
+    Arr hash(32 * m, 0), r(32 * m, 0), s(32 * m, 0), v(m, 0), chain(8 * m, 0), type(m, 0), status(m, 0), pk(64 * m, 0), addr(20 * m, 0), schain(8 * m, 0), stype(m, 0), sstatus(m, 0);
+    REQUIRE(plume_eth_tx_parse_batch(ctx, m, nullptr, off.data(), hash.p, r.p, s.p, v.p, (uint64_t*)chain.p, type.p, status.p) == 0);
+    REQUIRE(plume_eth_tx_sender_batch(ctx, PLUME_ECDSA_LOW_S, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, m, nullptr, off.data(), nullptr, pk.p, addr.p, (uint64_t*)schain.p, stype.p,
+                                      sstatus.p) == 0);
+    for (size_t i = 0; i < m; i++) {
+        REQUIRE(std::memcmp(hash.p + 32 * i, g_hash.data() + 32 * j, 32) == 0 && std::memcmp(r.p + 32 * i, g_r.data() + 32 * j, 32) == 0 &&
+                std::memcmp(s.p + 32 * i, g_s.data() + 32 * j, 32) == 0 && v.p[i] == g_v[j] && std::memcmp(chain.p + 8 * i, g_chain.data() + 8 * j, 8) == 0 && type.p[i] == g_type[j] &&
+                status.p[i] == g_status[j]);
+        REQUIRE(std::memcmp(pk.p + 64 * i, g_pk.data() + 64 * j, 64) == 0 && std::memcmp(addr.p + 20 * i, g_addr.data() + 20 * j, 20) == 0 && sstatus.p[i] == g_sstatus[j] &&
+                std::memcmp(schain.p + 8 * i, g_chain.data() + 8 * j, 8) == 0 && stype.p[i] == g_type[j]);
+    }
+    REQUIRE(plume_eth_tx_parse_batch(ctx, m, nullptr, g_off.data(), hash.p, r.p, s.p, v.p, nullptr, nullptr, nullptr) == PLUME_ERR_ARG &&
+            std::string(plume_last_error()).find("null transaction buffer") != std::string::npos);     // ... and only then
+    REQUIRE(plume_set_chunk(ctx, (size_t)1 << 20) == 0);
+}
+
 static std::vector<std::string> stage_names(plume_ctx* ctx) {
     const char* names[16]; float ms[16];
     const int k = plume_last_stage_times(ctx, names, ms, 16);
@@ -248,6 +274,7 @@ int main(int argc, char** argv) {
     group(ctx, "one device, host form, one chunk", 4, false, 0, 48);
     group(ctx, "one device, host form, chunks of 7", 8, false, 7, 40);
     group(ctx, "one device, host form, chunks of 1", 2, false, 1, 5);
+    group_null_buffer(ctx, "one device, empty items of a null buffer, chunks of 4", 4);
     REQUIRE(plume_set_chunk(ctx, (size_t)1 << 20) == 0);
     group(ctx, "one device, device form", 8, true, 0, 48);
     group_stages_and_order(ctx);
@@ -257,6 +284,7 @@ int main(int argc, char** argv) {
         REQUIRE(plume_init_multi(&multi, ids, devices) == 0);
         REQUIRE(plume_num_shards(multi) == devices);
         group(multi, devices == 3 ? "three devices, host form" : "eight devices, host form", 6, false, devices == 3 ? 5 : 0, 48);
+        group_null_buffer(multi, "several devices, empty items of a null buffer", devices == 3 ? 2 : 0);
         plume_destroy(multi);
     }
     group_arguments(ctx);

@@ -1320,29 +1320,6 @@ extern "C" int plume_nullifier_first_occurrence_device(plume_ctx* ctx, size_t n,
     if (n && (!nullifier || !first)) return fail(PLUME_ERR_ARG, "null array");
     return dedup_device(ctx, n, nullifier, live, ids, first, n_unique, st_);
 }
-// host-pointer form: one pass (every record has to be resident to be compared), staged through slot 0
-extern "C" int plume_nullifier_first_occurrence(plume_ctx* ctx, size_t n, const uint8_t* nullifier, const uint8_t* live, const uint64_t* ids, uint8_t* first,
-                                                uint64_t* n_unique) {
-    if (ctx && !ctx->shards.empty()) ctx = ctx->shards[0];   // every record has to meet every other: one device holds the whole set
-    if (int rc = bind(ctx)) return rc;
-    if (n && (!nullifier || !first)) return fail(PLUME_ERR_ARG, "null array");
-    if (n == 0) { if (n_unique) *n_unique = 0; return 0; }
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    if (sl.in[0].ensure(64 * n) || sl.in[1].ensure(n) || sl.in[2].ensure(8 * n) || sl.out[0].ensure(n) || sl.out[1].ensure(8)) return PLUME_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(sl.in[0].p, nullifier, 64 * n, hipMemcpyHostToDevice, st));
-    if (live) HIPCHK(hipMemcpyAsync(sl.in[1].p, live, n, hipMemcpyHostToDevice, st));
-    if (ids) HIPCHK(hipMemcpyAsync(sl.in[2].p, ids, 8 * n, hipMemcpyHostToDevice, st));
-    if (int rc = dedup_device(ctx, n, sl.in[0].as<uint8_t>(), live ? sl.in[1].as<uint8_t>() : nullptr, ids ? sl.in[2].as<uint64_t>() : nullptr, sl.out[0].as<uint8_t>(),
-                              sl.out[1].as<uint64_t>(), st))
-        return rc;
-    HIPCHK(hipMemcpyAsync(first, sl.out[0].p, n, hipMemcpyDeviceToHost, st));
-    uint64_t cnt = 0;
-    HIPCHK(hipMemcpyAsync(&cnt, sl.out[1].p, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (n_unique) *n_unique = cnt;
-    return 0;
-}
 
 // ------------------------------------------------------------------------------------- host-pointer pipelines
 // The batch is cut into pieces (ctx->host_piece items, the first one ctx->host_first_piece, at most ctx->chunk).  Piece k+1 is staged
@@ -1351,20 +1328,14 @@ extern "C" int plume_nullifier_first_occurrence(plume_ctx* ctx, size_t n, const 
 // range) is read and written by the copy engines directly and every copy is asynchronous; with pageable caller memory the copies block
 // the calling thread, which is why piece k-1 is drained only AFTER piece k has been submitted: the thread then waits on work that is
 // already behind it in the queue.
-static int stage_msgs(plume_ctx* ctx, HostSlot& sl, const uint8_t* msgs, const uint64_t* off, size_t i0, size_t cnt) {
-    if (sl.relbuf.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
-    uint64_t* rel = sl.rel = (uint64_t*)sl.relbuf.p;
-    const uint64_t base = off[i0];
-    switch (plume_host::rebase_offsets(off, i0, cnt, rel)) {
-        case 0: break;
-        case 1: return fail(PLUME_ERR_ARG, "msg_off is not non-decreasing");
-        default: return fail(PLUME_ERR_ARG, "message bytes per pass exceed 4 GiB");
-    }
-    if (sl.msgs.ensure((size_t)rel[cnt] + 16) || sl.off.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
-    if (rel[cnt]) HIPCHK(hipMemcpyAsync(sl.msgs.p, msgs + base, (size_t)rel[cnt], hipMemcpyHostToDevice, ctx->up));
-    HIPCHK(hipMemcpyAsync(sl.off.p, rel, (cnt + 1) * 8, hipMemcpyHostToDevice, ctx->up));
-    return 0;
-}
+//
+// The serial form (serial_host_call / serial_host_call_any, below the pipelined one) is the same table of caller arrays -- HostCall -- run one piece at a time: pieces of
+// at most ctx->chunk items through slot 0, everything on ctx->stream, one synchronise per piece; nothing overlaps, so it needs no events, no second lane and no
+// page-locked arrays, and its table may also name an input given once for the whole call (HostArray::whole) and a message buffer that is null.  Which one a new call
+// uses: the pipelined form where a piece's kernels take long enough to hide the next piece's upload behind them and callers send batches of many pieces (verify, sign,
+// recover, the aggregate check, hash to curve); the serial form for calls whose kernels are short beside their copies or that are rarely cut at all (addresses, ECDSA
+// recovery, message hashes, transactions, the Merkle calls, DER export).  Either way a call is: check the arguments, fill the table, hand the helper a lambda that
+// picks the slot's buffers and calls the *_device body -- never a chunk loop of its own.
 static int h2d(plume_ctx* ctx, DevBuf& b, const uint8_t* src, size_t bytes) {
     if (b.ensure(bytes)) return PLUME_ERR_HIP;
     HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->up));
@@ -1519,22 +1490,40 @@ static int host_pipeline(plume_ctx* ctx, size_t n, bool out_heavy, Up up, Run ru
 struct HostArray {
     const void* p = nullptr;   // the caller's array; null: not given
     size_t stride = 0;         // bytes per item; 0 = unused entry
-    bool secret = false;       // an input whose staged copy is wiped once the kernels have read it
+    bool secret = false;       // the staged copy is wiped once it has served: an input behind the kernels that read it, an output (serial calls only) behind its download
+    bool whole = false;        // serial calls only: `stride` bytes in all, not per item.  An input is given once for the call: uploaded in front of the first piece, not advanced by shard()
 };
 struct HostCall {
-    const uint8_t* msgs;
-    const uint64_t* msg_off;
+    const uint8_t* msgs;       // may be null when the offsets give it no bytes
+    const uint64_t* msg_off;   // null (serial calls only): the call has no messages and stages none
     HostArray in[6], out[7];
     bool out_heavy = false, may_use_two_lanes = false;
+    const char *off_name = "msg_off", *msgs_name = "message";         // what the argument errors of the message staging call the two
     // items [lo, ...) of the same call: msg_off keeps the caller's absolute offsets into the same msgs buffer
     HostCall shard(size_t lo) const {
         HostCall c = *this;
-        c.msg_off += lo;
-        for (HostArray& a : c.in) if (a.p) a.p = (const uint8_t*)a.p + a.stride * lo;
-        for (HostArray& a : c.out) if (a.p) a.p = (const uint8_t*)a.p + a.stride * lo;
+        if (c.msg_off) c.msg_off += lo;
+        for (HostArray& a : c.in) if (a.p && !a.whole) a.p = (const uint8_t*)a.p + a.stride * lo;
+        for (HostArray& a : c.out) if (a.p && !a.whole) a.p = (const uint8_t*)a.p + a.stride * lo;
         return c;
     }
 };
+// the messages of items [i0, i0 + cnt): their offsets rebased to the piece (page-locked, sl.rel) and the piece's bytes, uploaded through the slot on `st`.  sl.rel[cnt]: the bytes
+static int stage_msgs(const HostCall& call, HostSlot& sl, size_t i0, size_t cnt, hipStream_t st) {
+    if (sl.relbuf.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
+    uint64_t* rel = sl.rel = (uint64_t*)sl.relbuf.p;
+    switch (plume_host::rebase_offsets(call.msg_off, i0, cnt, rel)) {
+        case 0: break;
+        case 1: return fail(PLUME_ERR_ARG, std::string(call.off_name) + " is not non-decreasing");
+        default: return fail(PLUME_ERR_ARG, std::string(call.msgs_name) + " bytes per pass exceed 4 GiB");
+    }
+    const size_t bytes = (size_t)rel[cnt];
+    if (bytes && !call.msgs) return fail(PLUME_ERR_ARG, std::string("null ") + call.msgs_name + " buffer");
+    if (sl.msgs.ensure(bytes + 16) || sl.off.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
+    if (bytes) HIPCHK(hipMemcpyAsync(sl.msgs.p, call.msgs + call.msg_off[i0], bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sl.off.p, rel, (cnt + 1) * 8, hipMemcpyHostToDevice, st));
+    return 0;
+}
 
 // one single-device context, items [0, n > 0) of the call.  run(slot, cnt, lane) enqueues the kernels of one piece and picks which of the slot's buffers they get;
 // every output buffer is allocated, given or not.
@@ -1557,7 +1546,7 @@ static int host_call(plume_ctx* ctx, size_t n, const HostCall& call, Run run) {
     const int rc = host_pipeline(
         ctx, n, call.out_heavy,
         [&](HostSlot& sl, size_t i0, size_t cnt) -> int {
-            if (int rc = stage_msgs(ctx, sl, call.msgs, call.msg_off, i0, cnt)) return rc;
+            if (int rc = stage_msgs(call, sl, i0, cnt, ctx->up)) return rc;
             for (size_t k = 0; k < std::size(call.in); k++) {
                 const HostArray& a = call.in[k];
                 if (a.p) { if (int rc = h2d(ctx, sl.in[k], (const uint8_t*)a.p + a.stride * i0, a.stride * cnt)) return rc; }
@@ -1594,6 +1583,90 @@ static int host_call_any(plume_ctx* ctx, size_t n, const HostCall& call, Run run
     if (n == 0) return 0;
     if (ctx->shards.empty()) return host_call(ctx, n, call, run);
     return for_shards(ctx, n, [&](plume_ctx* sh, size_t lo, size_t hi) -> int { return host_call(sh, hi - lo, call.shard(lo), run); });
+}
+
+// ------------------------------------------------------------------------------------- serial host-pointer calls
+// One piece of a serial call (see the block comment above): items [i0, i0 + cnt) through ctx->slot[0] on ctx->stream, and the wait for it.  In queue order: the whole-call
+// inputs (first piece only), the messages, the inputs that are given, run(slot, cnt, ctx) -- the caller's lambda picks the slot's buffers and calls the *_device body --,
+// the wipe of the secret inputs, the downloads of the outputs that are given, the wipe of the secret outputs.  Whatever fails, the stream is synchronised before the
+// piece returns -- no copy stays queued on the caller's arrays, the slot is free for the next call -- and every secret staging buffer is wiped in front of that wait.
+// The result is the first failure: an argument or an allocation (DevBuf::ensure's text), run's, a copy's, the wait's.
+template <class Run>
+static int serial_host_piece(plume_ctx* ctx, const HostCall& call, size_t i0, size_t cnt, Run run) {
+    HostSlot& sl = ctx->slot[0];
+    const hipStream_t st = ctx->stream;
+    auto bytes = [&](const HostArray& a) { return a.whole ? a.stride : a.stride * cnt; };
+    auto at = [&](const HostArray& a) { return (uint8_t*)a.p + (a.whole ? 0 : a.stride * i0); };
+    auto copy = [&](void* dst, const void* src, size_t len, hipMemcpyKind kind) -> int {
+        const hipError_t e = hipMemcpyAsync(dst, src, len, kind, st);
+        return e == hipSuccess ? 0 : fail(PLUME_ERR_HIP, std::string(kind == hipMemcpyHostToDevice ? "host-pointer upload: " : "host-pointer download: ") + hipGetErrorString(e));
+    };
+    auto upload = [&](bool whole) -> int {
+        for (size_t k = 0; k < std::size(call.in); k++) {
+            const HostArray& a = call.in[k];
+            if (!a.p || a.whole != whole) continue;
+            if (sl.in[k].ensure(bytes(a))) return PLUME_ERR_HIP;
+            if (int rc = copy(sl.in[k].p, at(a), bytes(a), hipMemcpyHostToDevice)) return rc;
+        }
+        return 0;
+    };
+    auto enqueue = [&]() -> int {
+        if (i0 == 0) { if (int rc = upload(true)) return rc; }
+        if (call.msg_off) { if (int rc = stage_msgs(call, sl, i0, cnt, st)) return rc; }
+        if (int rc = upload(false)) return rc;
+        for (size_t k = 0; k < std::size(call.out); k++) if (call.out[k].p && sl.out[k].ensure(bytes(call.out[k]))) return PLUME_ERR_HIP;
+        if (int rc = run(sl, cnt, ctx)) return rc;
+        for (size_t k = 0; k < std::size(call.in); k++) if (call.in[k].secret && call.in[k].p) HIPCHK(hipMemsetAsync(sl.in[k].p, 0, bytes(call.in[k]), st));
+        for (size_t k = 0; k < std::size(call.out); k++) {
+            const HostArray& a = call.out[k];
+            if (a.p) { if (int rc = copy(at(a), sl.out[k].p, bytes(a), hipMemcpyDeviceToHost)) return rc; }
+        }
+        for (size_t k = 0; k < std::size(call.out); k++) if (call.out[k].secret && call.out[k].p) HIPCHK(hipMemsetAsync(sl.out[k].p, 0, bytes(call.out[k]), st));
+        return 0;
+    };
+    const int rc = enqueue();
+    if (rc) {   // staged secrets that no kernel read, or that no wipe followed
+        for (size_t k = 0; k < std::size(call.in); k++) if (call.in[k].secret && sl.in[k].p) (void)hipMemsetAsync(sl.in[k].p, 0, sl.in[k].cap, st);
+        for (size_t k = 0; k < std::size(call.out); k++) if (call.out[k].secret && sl.out[k].p) (void)hipMemsetAsync(sl.out[k].p, 0, sl.out[k].cap, st);
+    }
+    const hipError_t es = hipStreamSynchronize(st);
+    if (rc) return rc;
+    if (es != hipSuccess) return fail(PLUME_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
+    return 0;
+}
+// one single-device context, items [0, n > 0) of the call: pieces of at most ctx->chunk items, one after the other
+template <class Run>
+static int serial_host_call(plume_ctx* ctx, size_t n, const HostCall& call, Run run) {
+    HIPCHK(hipSetDevice(ctx->device));
+    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk)
+        if (int rc = serial_host_piece(ctx, call, i0, std::min(n - i0, ctx->chunk), run)) return rc;
+    return 0;
+}
+// a context of either kind, arguments already checked: a multi-device context runs every shard's items on that shard
+template <class Run>
+static int serial_host_call_any(plume_ctx* ctx, size_t n, const HostCall& call, Run run) {
+    if (n == 0) return 0;
+    if (ctx->shards.empty()) return serial_host_call(ctx, n, call, run);
+    return for_shards(ctx, n, [&](plume_ctx* sh, size_t lo, size_t hi) -> int { return serial_host_call(sh, hi - lo, call.shard(lo), run); });
+}
+
+// the first-occurrence flags over host arrays: one piece whatever the chunk size is (every record has to be resident to be compared)
+extern "C" int plume_nullifier_first_occurrence(plume_ctx* ctx, size_t n, const uint8_t* nullifier, const uint8_t* live, const uint64_t* ids, uint8_t* first,
+                                                uint64_t* n_unique) {
+    if (ctx && !ctx->shards.empty()) ctx = ctx->shards[0];   // every record has to meet every other: one device holds the whole set
+    if (int rc = bind(ctx)) return rc;
+    if (n && (!nullifier || !first)) return fail(PLUME_ERR_ARG, "null array");
+    uint64_t cnt = 0;
+    if (n) {
+        const HostCall call{nullptr, nullptr, {{nullifier, 64}, {live, 1}, {ids, 8}}, {{first, 1}, {&cnt, 8, false, true}}};
+        const int rc = serial_host_piece(ctx, call, 0, n, [&](HostSlot& sl, size_t, plume_ctx* on) -> int {
+            return dedup_device(on, n, sl.in[0].as<uint8_t>(), live ? sl.in[1].as<uint8_t>() : nullptr, ids ? sl.in[2].as<uint64_t>() : nullptr, sl.out[0].as<uint8_t>(),
+                                sl.out[1].as<uint64_t>(), on->stream);
+        });
+        if (rc) return rc;
+    }
+    if (n_unique) *n_unique = cnt;
+    return 0;
 }
 
 // verify, verify_sec1 (33-byte points) and verify_non_zk (c = digest_private)
@@ -1787,29 +1860,14 @@ extern "C" int plume_h2c_intermediates_batch(plume_ctx* ctx, size_t n, const uin
 extern "C" int plume_h2c_hints_batch(plume_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pk, int registers, uint8_t* hints) {
     return h2c_inter_host(ctx, true, n, msgs, msg_off, pk, registers, nullptr, nullptr, nullptr, nullptr, hints);
 }
-static int der_host(plume_ctx* ctx, size_t n, const uint8_t* scalars, uint8_t* der109, uint8_t* status) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
-        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
-        if (sl.in[0].ensure(32 * cnt) || sl.out[0].ensure(PLUME_DER_LEN * cnt) || sl.out[1].ensure(cnt)) return PLUME_ERR_HIP;
-        HIPCHK(hipMemcpyAsync(sl.in[0].p, scalars + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st));
-        if (int rc = der_device(ctx, cnt, sl.in[0].as<uint8_t>(), sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), st)) return rc;
-        HIPCHK(hipMemsetAsync(sl.in[0].p, 0, 32 * cnt, st));                       // the scalars may be secret keys: wipe the staged copy
-        HIPCHK(hipMemcpyAsync(der109 + PLUME_DER_LEN * i0, sl.out[0].p, PLUME_DER_LEN * cnt, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(status + i0, sl.out[1].p, cnt, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemsetAsync(sl.out[0].p, 0, PLUME_DER_LEN * cnt, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return 0;
-}
+// the scalars may be secret keys: their staged copy is wiped behind the kernel, the records' behind their download
 extern "C" int plume_scalars_to_sec1_der_batch(plume_ctx* ctx, size_t n, const uint8_t* scalars, uint8_t* der109, uint8_t* status) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
     if (n && (!scalars || !der109 || !status)) return fail(PLUME_ERR_ARG, "null array");
-    if (n == 0) return 0;
-    if (ctx->shards.empty()) return der_host(ctx, n, scalars, der109, status);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int { return der_host(sh, hi - lo, scalars + 32 * lo, der109 + PLUME_DER_LEN * lo, status + lo); });
+    const HostCall call{nullptr, nullptr, {{scalars, 32, true}}, {{der109, PLUME_DER_LEN, true}, {status, 1}}};
+    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return der_device(on, cnt, sl.in[0].as<uint8_t>(), sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), on->stream);
+    });
 }
 // The Ethereum-address call (plume_capi_internal.h): the ABI and the launcher live in plume_eth_capi.hip.  No table is needed and no workspace is touched -- the kernel
 // reads and writes the caller's arrays only -- so the call neither builds anything nor joins the ws_free chain.
@@ -1838,38 +1896,14 @@ int plume::capi_eth_address_device(plume_ctx* ctx, int pk_format, int addr_forma
     if (int rc = eth_args_ok(pk_format, addr_format, n, pk, address, status, eth_fn)) return rc;
     return eth_device(ctx, pk_format, addr_format, n, pk, expect, address, status, st_, eth_fn);
 }
-static int eth_host(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status, EthLaunch fn) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
-    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
-        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
-        if (sl.in[0].ensure(P * cnt) || (expect && sl.in[1].ensure(20 * cnt)) || (address && sl.out[0].ensure(W * cnt)) || (status && sl.out[1].ensure(cnt))) return PLUME_ERR_HIP;
-        HIPCHK(hipMemcpyAsync(sl.in[0].p, pk + P * i0, P * cnt, hipMemcpyHostToDevice, st));
-        if (expect) HIPCHK(hipMemcpyAsync(sl.in[1].p, expect + 20 * i0, 20 * cnt, hipMemcpyHostToDevice, st));
-        int rc = eth_device(ctx, pk_format, addr_format, cnt, sl.in[0].as<uint8_t>(), expect ? sl.in[1].as<uint8_t>() : nullptr, address ? sl.out[0].as<uint8_t>() : nullptr,
-                            status ? sl.out[1].as<uint8_t>() : nullptr, st, fn);
-        hipError_t e = hipSuccess;
-        if (!rc && address) e = hipMemcpyAsync(address + W * i0, sl.out[0].p, W * cnt, hipMemcpyDeviceToHost, st);
-        if (!rc && e == hipSuccess && status) e = hipMemcpyAsync(status + i0, sl.out[1].p, cnt, hipMemcpyDeviceToHost, st);
-        const hipError_t es = hipStreamSynchronize(st);                            // on failure too: the slot's buffers are reused by the next call
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(PLUME_ERR_HIP, std::string("address download: ") + hipGetErrorString(e));
-        if (es != hipSuccess) return fail(PLUME_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
-    }
-    return 0;
-}
 int plume::capi_eth_address(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status,
                             EthLaunch eth_fn) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
     if (int rc = eth_args_ok(pk_format, addr_format, n, pk, address, status, eth_fn)) return rc;
-    if (n == 0) return 0;
-    if (ctx->shards.empty()) return eth_host(ctx, pk_format, addr_format, n, pk, expect, address, status, eth_fn);
-    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
-        return eth_host(sh, pk_format, addr_format, hi - lo, pk + P * lo, expect ? expect + 20 * lo : nullptr, address ? address + W * lo : nullptr, status ? status + lo : nullptr,
-                        eth_fn);
+    const HostCall call{nullptr, nullptr, {{pk, eth_pk_width(pk_format)}, {expect, 20}}, {{address, eth_address_width(addr_format)}, {status, 1}}};
+    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return eth_device(on, pk_format, addr_format, cnt, sl.in[0].as<uint8_t>(), expect ? sl.in[1].as<uint8_t>() : nullptr, address ? sl.out[0].as<uint8_t>() : nullptr,
+                          status ? sl.out[1].as<uint8_t>() : nullptr, on->stream, eth_fn);
     });
 }
 // The ECDSA recovery (plume_capi_internal.h): the ABI and the launchers live in plume_ecdsa_capi.hip.  The comb of G is the only fixed table (never the 1 GiB window table);
@@ -1932,46 +1966,15 @@ int plume::capi_ecdsa_recover_device(plume_ctx* ctx, int flags, int pk_format, i
     if (int rc = ecdsa_args_ok(flags, pk_format, addr_format, n, hash, r, s, v, pk, address, status, fn)) return rc;
     return ecdsa_device(ctx, flags, pk_format, addr_format, n, hash, r, s, v, expect, pk, address, status, st_, fn);
 }
-static int ecdsa_host(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s, const uint8_t* v,
-                      const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, const EcdsaLaunch* fn) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
-    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
-        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
-        if (sl.in[0].ensure(32 * cnt) || sl.in[1].ensure(32 * cnt) || sl.in[2].ensure(32 * cnt) || sl.in[3].ensure(cnt) || (expect && sl.in[4].ensure(20 * cnt)) ||
-            (pk && sl.out[0].ensure(P * cnt)) || (address && sl.out[1].ensure(W * cnt)) || (status && sl.out[2].ensure(cnt)))
-            return PLUME_ERR_HIP;
-        HIPCHK(hipMemcpyAsync(sl.in[0].p, hash + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(sl.in[1].p, r + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(sl.in[2].p, s + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(sl.in[3].p, v + i0, cnt, hipMemcpyHostToDevice, st));
-        if (expect) HIPCHK(hipMemcpyAsync(sl.in[4].p, expect + 20 * i0, 20 * cnt, hipMemcpyHostToDevice, st));
-        int rc = ecdsa_device(ctx, flags, pk_format, addr_format, cnt, sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(), sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(),
-                              expect ? sl.in[4].as<uint8_t>() : nullptr, pk ? sl.out[0].as<uint8_t>() : nullptr, address ? sl.out[1].as<uint8_t>() : nullptr,
-                              status ? sl.out[2].as<uint8_t>() : nullptr, st, fn);
-        hipError_t e = hipSuccess;
-        if (!rc && pk) e = hipMemcpyAsync(pk + P * i0, sl.out[0].p, P * cnt, hipMemcpyDeviceToHost, st);
-        if (!rc && e == hipSuccess && address) e = hipMemcpyAsync(address + W * i0, sl.out[1].p, W * cnt, hipMemcpyDeviceToHost, st);
-        if (!rc && e == hipSuccess && status) e = hipMemcpyAsync(status + i0, sl.out[2].p, cnt, hipMemcpyDeviceToHost, st);
-        const hipError_t es = hipStreamSynchronize(st);                            // on failure too: the slot's buffers are reused by the next call
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(PLUME_ERR_HIP, std::string("recovery download: ") + hipGetErrorString(e));
-        if (es != hipSuccess) return fail(PLUME_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
-    }
-    return 0;
-}
 int plume::capi_ecdsa_recover(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s, const uint8_t* v,
                               const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, const EcdsaLaunch* fn) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
     if (int rc = ecdsa_args_ok(flags, pk_format, addr_format, n, hash, r, s, v, pk, address, status, fn)) return rc;
-    if (n == 0) return 0;
-    if (ctx->shards.empty()) return ecdsa_host(ctx, flags, pk_format, addr_format, n, hash, r, s, v, expect, pk, address, status, fn);
-    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
-        return ecdsa_host(sh, flags, pk_format, addr_format, hi - lo, hash + 32 * lo, r + 32 * lo, s + 32 * lo, v + lo, expect ? expect + 20 * lo : nullptr,
-                          pk ? pk + P * lo : nullptr, address ? address + W * lo : nullptr, status ? status + lo : nullptr, fn);
+    const HostCall call{nullptr, nullptr, {{hash, 32}, {r, 32}, {s, 32}, {v, 1}, {expect, 20}}, {{pk, eth_pk_width(pk_format)}, {address, eth_address_width(addr_format)}, {status, 1}}};
+    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return ecdsa_device(on, flags, pk_format, addr_format, cnt, sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(), sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(),
+                            expect ? sl.in[4].as<uint8_t>() : nullptr, pk ? sl.out[0].as<uint8_t>() : nullptr, address ? sl.out[1].as<uint8_t>() : nullptr,
+                            status ? sl.out[2].as<uint8_t>() : nullptr, on->stream, fn);
     });
 }
 // The message-hash call (plume_capi_internal.h): the ABI lives in plume_eth_hash_capi.hip, the launcher beside the address kernel's.  Like the address call it needs no table and touches no workspace.
@@ -1998,40 +2001,13 @@ int plume::capi_eth_message_hash_device(plume_ctx* ctx, int mode, size_t n, cons
     if (int rc = eth_hash_args_ok(mode, n, msg_off, hash32, hash_fn)) return rc;
     return eth_hash_device(ctx, mode, n, msgs, msg_off, msgs_bytes, hash32, st_, hash_fn);
 }
-static int eth_hash_host(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, uint8_t* hash, EthHashLaunch fn) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
-        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
-        if (sl.relbuf.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
-        uint64_t* rel = sl.rel = (uint64_t*)sl.relbuf.p;
-        switch (plume_host::rebase_offsets(msg_off, i0, cnt, rel)) {
-            case 0: break;
-            case 1: return fail(PLUME_ERR_ARG, "msg_off is not non-decreasing");
-            default: return fail(PLUME_ERR_ARG, "message bytes per pass exceed 4 GiB");
-        }
-        const size_t bytes = (size_t)rel[cnt];
-        if (bytes && !msgs) return fail(PLUME_ERR_ARG, "null message buffer");
-        if (sl.msgs.ensure(bytes + 16) || sl.off.ensure((cnt + 1) * 8) || sl.out[0].ensure(32 * cnt)) return PLUME_ERR_HIP;
-        if (bytes) HIPCHK(hipMemcpyAsync(sl.msgs.p, msgs + msg_off[i0], bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(sl.off.p, rel, (cnt + 1) * 8, hipMemcpyHostToDevice, st));
-        int rc = eth_hash_device(ctx, mode, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), bytes, sl.out[0].as<uint8_t>(), st, fn);
-        hipError_t e = hipSuccess;
-        if (!rc) e = hipMemcpyAsync(hash + 32 * i0, sl.out[0].p, 32 * cnt, hipMemcpyDeviceToHost, st);
-        const hipError_t es = hipStreamSynchronize(st);                            // on failure too: the slot's buffers (and the page-locked offsets) are reused by the next call
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(PLUME_ERR_HIP, std::string("digest download: ") + hipGetErrorString(e));
-        if (es != hipSuccess) return fail(PLUME_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
-    }
-    return 0;
-}
 int plume::capi_eth_message_hash(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, uint8_t* hash32, EthHashLaunch hash_fn) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
     if (int rc = eth_hash_args_ok(mode, n, msg_off, hash32, hash_fn)) return rc;
-    if (n == 0) return 0;
-    if (ctx->shards.empty()) return eth_hash_host(ctx, mode, n, msgs, msg_off, hash32, hash_fn);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int { return eth_hash_host(sh, mode, hi - lo, msgs, msg_off + lo, hash32 + 32 * lo, hash_fn); });
+    const HostCall call{msgs, msg_off, {}, {{hash32, 32}}};
+    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return eth_hash_device(on, mode, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.out[0].as<uint8_t>(), on->stream, hash_fn);
+    });
 }
 // The transaction calls (plume_capi_internal.h): the ABI and the launcher live in plume_eth_tx_capi.hip.  parse is the message-hash call with more outputs: no table, no
 // workspace.  sender runs the same kernel into ctx->txstage and the recover stages (ecdsa_device, on this workspace and this stream) on what it staged, so it holds the
@@ -2064,66 +2040,17 @@ int plume::capi_eth_tx_parse_device(plume_ctx* ctx, size_t n, const uint8_t* txs
     if (int rc = eth_tx_parse_args_ok(n, tx_off, hash32, r, s, v, tx_fn)) return rc;
     return eth_tx_parse_device(ctx, n, txs, tx_off, txs_bytes, hash32, r, s, v, chain_id, tx_type, status, st_, tx_fn);
 }
-// one piece of a host-pointer transaction call: the offsets rebased to the piece and the piece's bytes, uploaded through the slot.  bytes: what the piece holds
-static int eth_tx_stage_piece(plume_ctx* ctx, HostSlot& sl, const uint8_t* txs, const uint64_t* tx_off, size_t i0, size_t cnt, size_t& bytes, hipStream_t st) {
-    if (sl.relbuf.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
-    uint64_t* rel = sl.rel = (uint64_t*)sl.relbuf.p;
-    switch (plume_host::rebase_offsets(tx_off, i0, cnt, rel)) {
-        case 0: break;
-        case 1: return fail(PLUME_ERR_ARG, "tx_off is not non-decreasing");
-        default: return fail(PLUME_ERR_ARG, "transaction bytes per pass exceed 4 GiB");
-    }
-    bytes = (size_t)rel[cnt];
-    if (bytes && !txs) return fail(PLUME_ERR_ARG, "null transaction buffer");
-    if (sl.msgs.ensure(bytes + 16) || sl.off.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
-    if (bytes) HIPCHK(hipMemcpyAsync(sl.msgs.p, txs + tx_off[i0], bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sl.off.p, rel, (cnt + 1) * 8, hipMemcpyHostToDevice, st));
-    return 0;
-}
-// downloads behind a piece's kernels, then the wait -- on failure too: the slot's buffers (and the page-locked offsets) are reused by the next call
-static int eth_tx_drain_piece(int rc, hipStream_t st, std::initializer_list<std::tuple<void*, const void*, size_t>> copies) {
-    hipError_t e = hipSuccess;
-    for (const auto& c : copies)
-        if (!rc && e == hipSuccess && std::get<0>(c)) e = hipMemcpyAsync(std::get<0>(c), std::get<1>(c), std::get<2>(c), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(PLUME_ERR_HIP, std::string("transaction download: ") + hipGetErrorString(e));
-    if (es != hipSuccess) return fail(PLUME_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
-    return 0;
-}
-static int eth_tx_parse_host(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, uint8_t* hash, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
-                             uint8_t* tx_type, uint8_t* status, EthTxLaunch fn) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
-        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
-        size_t bytes = 0;
-        if (int rc = eth_tx_stage_piece(ctx, sl, txs, tx_off, i0, cnt, bytes, st)) { (void)hipStreamSynchronize(st); return rc; }
-        if (sl.out[0].ensure(32 * cnt) || sl.out[1].ensure(32 * cnt) || sl.out[2].ensure(32 * cnt) || sl.out[3].ensure(cnt) || (chain_id && sl.out[4].ensure(8 * cnt)) ||
-            (tx_type && sl.out[5].ensure(cnt)) || (status && sl.out[6].ensure(cnt))) {
-            (void)hipStreamSynchronize(st);
-            return PLUME_ERR_HIP;
-        }
-        const int rc = eth_tx_parse_device(ctx, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), bytes, sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(),
-                                           sl.out[3].as<uint8_t>(), chain_id ? sl.out[4].as<uint64_t>() : nullptr, tx_type ? sl.out[5].as<uint8_t>() : nullptr,
-                                           status ? sl.out[6].as<uint8_t>() : nullptr, st, fn);
-        if (int rc2 = eth_tx_drain_piece(rc, st, {{hash + 32 * i0, sl.out[0].p, 32 * cnt}, {r + 32 * i0, sl.out[1].p, 32 * cnt}, {s + 32 * i0, sl.out[2].p, 32 * cnt},
-                                                  {v + i0, sl.out[3].p, cnt}, {chain_id ? chain_id + i0 : nullptr, sl.out[4].p, 8 * cnt},
-                                                  {tx_type ? tx_type + i0 : nullptr, sl.out[5].p, cnt}, {status ? status + i0 : nullptr, sl.out[6].p, cnt}}))
-            return rc2;
-    }
-    return 0;
-}
+// the host-pointer forms stage their bytes as a message-hash call does; the argument errors speak of transactions
+static HostCall eth_tx_call(const HostCall& call) { HostCall c = call; c.off_name = "tx_off"; c.msgs_name = "transaction"; return c; }
 int plume::capi_eth_tx_parse(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
                              uint8_t* tx_type, uint8_t* status, EthTxLaunch tx_fn) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
     if (int rc = eth_tx_parse_args_ok(n, tx_off, hash32, r, s, v, tx_fn)) return rc;
-    if (n == 0) return 0;
-    if (ctx->shards.empty()) return eth_tx_parse_host(ctx, n, txs, tx_off, hash32, r, s, v, chain_id, tx_type, status, tx_fn);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
-        return eth_tx_parse_host(sh, hi - lo, txs, tx_off + lo, hash32 + 32 * lo, r + 32 * lo, s + 32 * lo, v + lo, chain_id ? chain_id + lo : nullptr,
-                                 tx_type ? tx_type + lo : nullptr, status ? status + lo : nullptr, tx_fn);
+    const HostCall call = eth_tx_call({txs, tx_off, {}, {{hash32, 32}, {r, 32}, {s, 32}, {v, 1}, {chain_id, 8}, {tx_type, 1}, {status, 1}}});
+    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return eth_tx_parse_device(on, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(),
+                                   sl.out[3].as<uint8_t>(), chain_id ? sl.out[4].as<uint64_t>() : nullptr, tx_type ? sl.out[5].as<uint8_t>() : nullptr,
+                                   status ? sl.out[6].as<uint8_t>() : nullptr, on->stream, tx_fn);
     });
 }
 static int eth_tx_sender_args_ok(int flags, int pk_format, int addr_format, size_t n, const void* off, const void* pk, const void* address, const void* status,
@@ -2159,44 +2086,16 @@ int plume::capi_eth_tx_sender_device(plume_ctx* ctx, int flags, int pk_format, i
     if (int rc = eth_tx_sender_args_ok(flags, pk_format, addr_format, n, tx_off, pk, address, status, tx_fn, fn)) return rc;
     return eth_tx_sender_device(ctx, flags, pk_format, addr_format, n, txs, tx_off, txs_bytes, expect, pk, address, chain_id, tx_type, status, st_, tx_fn, fn);
 }
-static int eth_tx_sender_host(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, const uint8_t* expect,
-                              uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, EthTxLaunch tx_fn, const EcdsaLaunch* fn) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
-    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
-        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
-        size_t bytes = 0;
-        if (int rc = eth_tx_stage_piece(ctx, sl, txs, tx_off, i0, cnt, bytes, st)) { (void)hipStreamSynchronize(st); return rc; }
-        hipError_t eu = hipSuccess;
-        if ((expect && sl.in[0].ensure(20 * cnt)) || (pk && sl.out[0].ensure(P * cnt)) || (address && sl.out[1].ensure(W * cnt)) || (status && sl.out[2].ensure(cnt)) ||
-            (chain_id && sl.out[3].ensure(8 * cnt)) || (tx_type && sl.out[4].ensure(cnt)) ||
-            (expect && (eu = hipMemcpyAsync(sl.in[0].p, expect + 20 * i0, 20 * cnt, hipMemcpyHostToDevice, st)) != hipSuccess)) {
-            (void)hipStreamSynchronize(st);
-            return eu != hipSuccess ? fail(PLUME_ERR_HIP, std::string("expect upload: ") + hipGetErrorString(eu)) : PLUME_ERR_HIP;
-        }
-        const int rc = eth_tx_sender_device(ctx, flags, pk_format, addr_format, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), bytes, expect ? sl.in[0].as<uint8_t>() : nullptr,
-                                            pk ? sl.out[0].as<uint8_t>() : nullptr, address ? sl.out[1].as<uint8_t>() : nullptr, chain_id ? sl.out[3].as<uint64_t>() : nullptr,
-                                            tx_type ? sl.out[4].as<uint8_t>() : nullptr, status ? sl.out[2].as<uint8_t>() : nullptr, st, tx_fn, fn);
-        if (int rc2 = eth_tx_drain_piece(rc, st, {{pk ? pk + P * i0 : nullptr, sl.out[0].p, P * cnt}, {address ? address + W * i0 : nullptr, sl.out[1].p, W * cnt},
-                                                  {status ? status + i0 : nullptr, sl.out[2].p, cnt}, {chain_id ? chain_id + i0 : nullptr, sl.out[3].p, 8 * cnt},
-                                                  {tx_type ? tx_type + i0 : nullptr, sl.out[4].p, cnt}}))
-            return rc2;
-    }
-    return 0;
-}
 int plume::capi_eth_tx_sender(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, const uint8_t* expect,
                               uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, EthTxLaunch tx_fn, const EcdsaLaunch* fn) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
     if (int rc = eth_tx_sender_args_ok(flags, pk_format, addr_format, n, tx_off, pk, address, status, tx_fn, fn)) return rc;
-    if (n == 0) return 0;
-    if (ctx->shards.empty()) return eth_tx_sender_host(ctx, flags, pk_format, addr_format, n, txs, tx_off, expect, pk, address, chain_id, tx_type, status, tx_fn, fn);
-    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
-        return eth_tx_sender_host(sh, flags, pk_format, addr_format, hi - lo, txs, tx_off + lo, expect ? expect + 20 * lo : nullptr, pk ? pk + P * lo : nullptr,
-                                  address ? address + W * lo : nullptr, chain_id ? chain_id + lo : nullptr, tx_type ? tx_type + lo : nullptr, status ? status + lo : nullptr,
-                                  tx_fn, fn);
+    const HostCall call = eth_tx_call({txs, tx_off, {{expect, 20}},
+                                       {{pk, eth_pk_width(pk_format)}, {address, eth_address_width(addr_format)}, {status, 1}, {chain_id, 8}, {tx_type, 1}}});
+    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return eth_tx_sender_device(on, flags, pk_format, addr_format, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], expect ? sl.in[0].as<uint8_t>() : nullptr,
+                                    pk ? sl.out[0].as<uint8_t>() : nullptr, address ? sl.out[1].as<uint8_t>() : nullptr, chain_id ? sl.out[3].as<uint64_t>() : nullptr,
+                                    tx_type ? sl.out[4].as<uint8_t>() : nullptr, status ? sl.out[2].as<uint8_t>() : nullptr, on->stream, tx_fn, fn);
     });
 }
 // The Merkle calls (plume_capi_internal.h): the ABI and the launchers live in plume_merkle_capi.hip.  leaf and verify are the address call over again: per-item kernels
@@ -2232,35 +2131,15 @@ int plume::capi_merkle_leaf_device(plume_ctx* ctx, int leaf_format, int addr_for
     if (int rc = merkle_leaf_args_ok(leaf_format, addr_format, n, address, amount, leaf32, fn)) return rc;
     return merkle_leaf_device(ctx, leaf_format, addr_format, n, address, amount, leaf32, status, st_, fn);
 }
-static int merkle_leaf_host(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* in, const uint8_t* amount, uint8_t* leaf, uint8_t* status,
-                            const MerkleLaunch* fn) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    const size_t W = mrk_item_width(leaf_format, addr_format);
-    for (size_t i0 = 0; i0 < n; i0 += ctx->chunk) {
-        const size_t cnt = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
-        if (sl.in[0].ensure(W * cnt) || (amount && sl.in[1].ensure(32 * cnt)) || sl.out[0].ensure(32 * cnt) || (status && sl.out[1].ensure(cnt))) return PLUME_ERR_HIP;
-        HIPCHK(hipMemcpyAsync(sl.in[0].p, in + W * i0, W * cnt, hipMemcpyHostToDevice, st));
-        hipError_t e = hipSuccess;
-        if (amount) e = hipMemcpyAsync(sl.in[1].p, amount + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st);
-        int rc = e != hipSuccess ? fail(PLUME_ERR_HIP, std::string("amount upload: ") + hipGetErrorString(e))
-                                 : merkle_leaf_device(ctx, leaf_format, addr_format, cnt, sl.in[0].as<uint8_t>(), amount ? sl.in[1].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(),
-                                                      status ? sl.out[1].as<uint8_t>() : nullptr, st, fn);
-        if (int rc2 = eth_tx_drain_piece(rc, st, {{leaf + 32 * i0, sl.out[0].p, 32 * cnt}, {status ? status + i0 : nullptr, sl.out[1].p, cnt}})) return rc2;
-    }
-    return 0;
-}
 int plume::capi_merkle_leaf(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* address, const uint8_t* amount, uint8_t* leaf32, uint8_t* status,
                             const MerkleLaunch* fn) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
     if (int rc = merkle_leaf_args_ok(leaf_format, addr_format, n, address, amount, leaf32, fn)) return rc;
-    if (n == 0) return 0;
     if (leaf_format != PLUME_MRK_LEAF_ADDRESS_UINT256) amount = nullptr;
-    if (ctx->shards.empty()) return merkle_leaf_host(ctx, leaf_format, addr_format, n, address, amount, leaf32, status, fn);
-    const size_t W = mrk_item_width(leaf_format, addr_format);
-    return for_shards(ctx, n, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
-        return merkle_leaf_host(sh, leaf_format, addr_format, hi - lo, address + W * lo, amount ? amount + 32 * lo : nullptr, leaf32 + 32 * lo, status ? status + lo : nullptr, fn);
+    const HostCall call{nullptr, nullptr, {{address, mrk_item_width(leaf_format, addr_format)}, {amount, 32}}, {{leaf32, 32}, {status, 1}}};
+    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return merkle_leaf_device(on, leaf_format, addr_format, cnt, sl.in[0].as<uint8_t>(), amount ? sl.in[1].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(),
+                                  status ? sl.out[1].as<uint8_t>() : nullptr, on->stream, fn);
     });
 }
 static int merkle_build_args_ok(int flags, size_t n, const void* leaf, const void* tree, const MerkleLaunch* fn) {
@@ -2304,18 +2183,16 @@ int plume::capi_merkle_tree_build_device(plume_ctx* ctx, int flags, size_t n, co
     if (int rc = merkle_build_args_ok(flags, n, leaf32, tree, fn)) return rc;
     return merkle_build_device(ctx, flags, n, leaf32, tree, leaf_pos, st_, fn);
 }
+// one piece whatever the chunk size is: the tree is built where all of its leaves are
 int plume::capi_merkle_tree_build(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf32, uint8_t* tree, uint32_t* leaf_pos, const MerkleLaunch* fn) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
     if (int rc = merkle_build_args_ok(flags, n, leaf32, tree, fn)) return rc;
     if (!ctx->shards.empty()) ctx = ctx->shards[0];                             // one tree: one device holds all of it
     HIPCHK(hipSetDevice(ctx->device));
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    const size_t tb = 32 * (2 * n - 1);
-    if (sl.in[0].ensure(32 * n) || sl.out[0].ensure(tb) || (leaf_pos && sl.out[1].ensure(4 * n))) return PLUME_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(sl.in[0].p, leaf32, 32 * n, hipMemcpyHostToDevice, st));
-    const int rc = merkle_build_device(ctx, flags, n, sl.in[0].as<uint8_t>(), sl.out[0].as<uint8_t>(), leaf_pos ? sl.out[1].as<uint32_t>() : nullptr, st, fn);
-    return eth_tx_drain_piece(rc, st, {{tree, sl.out[0].p, tb}, {leaf_pos, sl.out[1].p, 4 * n}});
+    const HostCall call{nullptr, nullptr, {{leaf32, 32}}, {{tree, 32 * (2 * n - 1), false, true}, {leaf_pos, 4}}};
+    return serial_host_piece(ctx, call, 0, n, [&](HostSlot& sl, size_t, plume_ctx* on) -> int {
+        return merkle_build_device(on, flags, n, sl.in[0].as<uint8_t>(), sl.out[0].as<uint8_t>(), leaf_pos ? sl.out[1].as<uint32_t>() : nullptr, on->stream, fn);
+    });
 }
 static int merkle_proof_args_ok(size_t n, const void* tree, size_t m, const void* pos, size_t depth, const void* proof, const void* proof_len, const MerkleLaunch* fn) {
     if (int rc = merkle_formats_ok(PLUME_MRK_LEAF_HASH32, PLUME_ETHK_ADDR_RAW20, fn)) return rc;
@@ -2347,24 +2224,11 @@ int plume::capi_merkle_proof(plume_ctx* ctx, size_t n, const uint8_t* tree, size
     if (int rc = merkle_proof_args_ok(n, tree, m, pos, depth, proof, proof_len, fn)) return rc;
     if (m == 0) return 0;
     if (!ctx->shards.empty()) ctx = ctx->shards[0];                             // the tree is staged once: one device answers every index
-    HIPCHK(hipSetDevice(ctx->device));
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    const size_t tb = 32 * (2 * n - 1), pb = 32 * depth;
-    if (sl.in[0].ensure(tb)) return PLUME_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(sl.in[0].p, tree, tb, hipMemcpyHostToDevice, st));
-    for (size_t i0 = 0; i0 < m; i0 += ctx->chunk) {
-        const size_t cnt = m - i0 < ctx->chunk ? m - i0 : ctx->chunk;
-        hipError_t e = hipSuccess;
-        if (sl.in[1].ensure(4 * cnt) || (pb && sl.out[0].ensure(pb * cnt)) || sl.out[1].ensure(cnt) ||
-            (e = hipMemcpyAsync(sl.in[1].p, pos + i0, 4 * cnt, hipMemcpyHostToDevice, st)) != hipSuccess) {
-            (void)hipStreamSynchronize(st);
-            return e != hipSuccess ? fail(PLUME_ERR_HIP, std::string("index upload: ") + hipGetErrorString(e)) : PLUME_ERR_HIP;
-        }
-        const int rc = merkle_proof_device(ctx, n, sl.in[0].as<uint8_t>(), cnt, sl.in[1].as<uint32_t>(), depth, pb ? sl.out[0].as<uint8_t>() : nullptr, sl.out[1].as<uint8_t>(), st, fn);
-        if (int rc2 = eth_tx_drain_piece(rc, st, {{pb ? proof + pb * i0 : nullptr, sl.out[0].p, pb * cnt}, {proof_len + i0, sl.out[1].p, cnt}})) return rc2;
-    }
-    return 0;
+    const size_t pb = 32 * depth;
+    const HostCall call{nullptr, nullptr, {{tree, 32 * (2 * n - 1), false, true}, {pos, 4}}, {{pb ? proof : nullptr, pb}, {proof_len, 1}}};
+    return serial_host_call(ctx, m, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return merkle_proof_device(on, n, sl.in[0].as<uint8_t>(), cnt, sl.in[1].as<uint32_t>(), depth, pb ? sl.out[0].as<uint8_t>() : nullptr, sl.out[1].as<uint8_t>(), on->stream, fn);
+    });
 }
 static int merkle_verify_args_ok(int leaf_format, int addr_format, size_t m, const void* in, const void* amount, size_t depth, const void* proof, const void* proof_len,
                                  const void* root, const void* status, const MerkleLaunch* fn) {
@@ -2391,42 +2255,17 @@ int plume::capi_merkle_verify_device(plume_ctx* ctx, int leaf_format, int addr_f
     if (int rc = merkle_verify_args_ok(leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, fn)) return rc;
     return merkle_verify_device(ctx, leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, st_, fn);
 }
-static int merkle_verify_host(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* in, const uint8_t* amount, size_t depth, const uint8_t* proof,
-                              const uint8_t* proof_len, const uint8_t* root, uint8_t* status, const MerkleLaunch* fn) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HostSlot& sl = ctx->slot[0];
-    hipStream_t st = ctx->stream;
-    const size_t W = mrk_item_width(leaf_format, addr_format), pb = 32 * depth;
-    if (sl.in[4].ensure(32)) return PLUME_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(sl.in[4].p, root, 32, hipMemcpyHostToDevice, st));
-    for (size_t i0 = 0; i0 < m; i0 += ctx->chunk) {
-        const size_t cnt = m - i0 < ctx->chunk ? m - i0 : ctx->chunk;
-        hipError_t e = hipSuccess;
-        if (sl.in[0].ensure(W * cnt) || (amount && sl.in[1].ensure(32 * cnt)) || (pb && sl.in[2].ensure(pb * cnt)) || sl.in[3].ensure(cnt) || sl.out[0].ensure(cnt) ||
-            (e = hipMemcpyAsync(sl.in[0].p, in + W * i0, W * cnt, hipMemcpyHostToDevice, st)) != hipSuccess ||
-            (amount && (e = hipMemcpyAsync(sl.in[1].p, amount + 32 * i0, 32 * cnt, hipMemcpyHostToDevice, st)) != hipSuccess) ||
-            (pb && (e = hipMemcpyAsync(sl.in[2].p, proof + pb * i0, pb * cnt, hipMemcpyHostToDevice, st)) != hipSuccess) ||
-            (e = hipMemcpyAsync(sl.in[3].p, proof_len + i0, cnt, hipMemcpyHostToDevice, st)) != hipSuccess) {
-            (void)hipStreamSynchronize(st);
-            return e != hipSuccess ? fail(PLUME_ERR_HIP, std::string("proof upload: ") + hipGetErrorString(e)) : PLUME_ERR_HIP;
-        }
-        const int rc = merkle_verify_device(ctx, leaf_format, addr_format, cnt, sl.in[0].as<uint8_t>(), amount ? sl.in[1].as<uint8_t>() : nullptr, depth,
-                                            pb ? sl.in[2].as<uint8_t>() : nullptr, sl.in[3].as<uint8_t>(), sl.in[4].as<uint8_t>(), sl.out[0].as<uint8_t>(), st, fn);
-        if (int rc2 = eth_tx_drain_piece(rc, st, {{status + i0, sl.out[0].p, cnt}})) return rc2;
-    }
-    return 0;
-}
 int plume::capi_merkle_verify(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* address_or_leaf, const uint8_t* amount, size_t depth,
                               const uint8_t* proof, const uint8_t* proof_len, const uint8_t* root32, uint8_t* status, const MerkleLaunch* fn) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
     if (int rc = merkle_verify_args_ok(leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, fn)) return rc;
-    if (m == 0) return 0;
     if (leaf_format != PLUME_MRK_LEAF_ADDRESS_UINT256) amount = nullptr;
-    if (ctx->shards.empty()) return merkle_verify_host(ctx, leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, fn);
-    const size_t W = mrk_item_width(leaf_format, addr_format), pb = 32 * depth;
-    return for_shards(ctx, m, [=](plume_ctx* sh, size_t lo, size_t hi) -> int {
-        return merkle_verify_host(sh, leaf_format, addr_format, hi - lo, address_or_leaf + W * lo, amount ? amount + 32 * lo : nullptr, depth, pb ? proof + pb * lo : nullptr,
-                                  proof_len + lo, root32, status + lo, fn);
+    const size_t pb = 32 * depth;
+    const HostCall call{nullptr, nullptr, {{address_or_leaf, mrk_item_width(leaf_format, addr_format)}, {amount, 32}, {pb ? proof : nullptr, pb}, {proof_len, 1}, {root32, 32, false, true}},
+                        {{status, 1}}};
+    return serial_host_call_any(ctx, m, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        return merkle_verify_device(on, leaf_format, addr_format, cnt, sl.in[0].as<uint8_t>(), amount ? sl.in[1].as<uint8_t>() : nullptr, depth,
+                                    pb ? sl.in[2].as<uint8_t>() : nullptr, sl.in[3].as<uint8_t>(), sl.in[4].as<uint8_t>(), sl.out[0].as<uint8_t>(), on->stream, fn);
     });
 }
 // The ECDSA signer (plume_capi_internal.h): the ABI and the launchers live in plume_ecdsa_sign_capi.hip.  The table of G is the signer's -- the comb, or at level 2 the

@@ -49,8 +49,9 @@ __attribute__((visibility("hidden"))) int capi_recover_device(plume_ctx* ctx, in
                                                               uint8_t* hashed_to_curve_r, uint8_t* hashed_to_curve, uint8_t* status, void* stream, RecoverLaunch recover_fn);
 
 // The Ethereum-address call (plume_eth_address_batch*): one kernel on the caller's arrays, no tables and no workspace.  Its launcher comes in as a hook, like the three
-// above.  The host-pointer form stages chunks of at most plume_set_chunk items through the context's first slot and splits over the shards of a plume_init_multi context, as
-// plume_scalars_to_sec1_der_batch does; the device form enqueues on the caller's stream and does not synchronise.
+// above.  The host-pointer form is a serial call (serial_host_call_any in plume_capi.hip: chunks of at most plume_set_chunk items through the context's first slot,
+// one synchronise per chunk, the shards of a plume_init_multi context), as plume_scalars_to_sec1_der_batch is; the device form enqueues on the caller's stream and does
+// not synchronise.
 struct EthArgs;
 typedef void (*EthLaunch)(const EthArgs& a, hipStream_t st);
 __attribute__((visibility("hidden"))) int capi_eth_address(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect,
@@ -60,8 +61,8 @@ __attribute__((visibility("hidden"))) int capi_eth_address_device(plume_ctx* ctx
 
 // The ECDSA recovery (plume_ecdsa_recover_batch*): prepare, the table stage, the multiplication and its redo launch, the conversion to affine, finalize.  The three launchers
 // of its own kernels come in as a hook struct, like the four above; the table stage and the conversion are plume_capi.hip's own.  The device form takes its workspace from the
-// context (it joins the ws_free chain), honours plume_set_sub_batches and does not synchronise; the host-pointer form stages chunks of at most plume_set_chunk items through
-// the context's first slot and splits over the shards of a plume_init_multi context, as plume_eth_address_batch does.
+// context (it joins the ws_free chain), honours plume_set_sub_batches and does not synchronise; the host-pointer form goes through serial_host_call_any, as
+// plume_eth_address_batch does.
 struct EcdsaArgs;
 struct EcdsaLaunch {
     void (*prepare)(const EcdsaArgs& a, hipStream_t st);
@@ -75,9 +76,9 @@ __attribute__((visibility("hidden"))) int capi_ecdsa_recover_device(plume_ctx* c
                                                                     const uint8_t* s, const uint8_t* v, const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status,
                                                                     void* stream, const EcdsaLaunch* fn);
 
-// The message-hash call (plume_eth_message_hash_batch*): one kernel on the caller's arrays, no tables and no workspace, like the address call.  The host-pointer form stages
-// chunks of at most plume_set_chunk items (their message bytes and offsets rebased to the chunk) through the context's first slot and splits over the shards of a
-// plume_init_multi context; the device form enqueues on the caller's stream and does not synchronise.
+// The message-hash call (plume_eth_message_hash_batch*): one kernel on the caller's arrays, no tables and no workspace, like the address call.  The host-pointer form goes
+// through serial_host_call_any with the messages in its table (every chunk's bytes and its offsets, rebased to the chunk, are staged by stage_msgs; msgs may be null when
+// it holds no bytes); the device form enqueues on the caller's stream and does not synchronise.
 struct EthHashArgs;
 typedef void (*EthHashLaunch)(const EthHashArgs& a, hipStream_t st);
 __attribute__((visibility("hidden"))) int capi_eth_message_hash(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, uint8_t* hash32,
@@ -85,7 +86,7 @@ __attribute__((visibility("hidden"))) int capi_eth_message_hash(plume_ctx* ctx, 
 __attribute__((visibility("hidden"))) int capi_eth_message_hash_device(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes,
                                                                        uint8_t* hash32, void* stream, EthHashLaunch hash_fn);
 
-// The transaction calls (plume_eth_tx_parse_batch*, plume_eth_tx_sender_batch*).  parse: one kernel on the caller's arrays, routed like the message-hash call.  sender: the
+// The transaction calls (plume_eth_tx_parse_batch*, plume_eth_tx_sender_batch*).  parse: one kernel on the caller's arrays, through serial_host_call_any like the message-hash call.  sender: the
 // same kernel into the context's staging (hash, r, s, v: 97 B / item), then the recover stages on it -- workspace, sub-batches, chunk limit and routing are those of
 // capi_ecdsa_recover*.  The kernel's launcher comes in as a hook, the recover stages' as theirs.
 struct EthTxArgs;
@@ -104,8 +105,9 @@ __attribute__((visibility("hidden"))) int capi_eth_tx_sender_device(plume_ctx* c
                                                                     const EcdsaLaunch* fn);
 
 // The Merkle calls (plume_merkle_leaf_batch*, plume_merkle_tree_build*, plume_merkle_proof_batch*, plume_merkle_verify_batch*).  leaf and verify are per-item calls on the
-// caller's arrays, routed like the address call (chunks through the first slot, the shards of a plume_init_multi context; the device forms one kernel, no workspace).
-// build and proof work on ONE tree: the host-pointer forms run on the context itself or on its first shard, the whole tree staged in the first slot; build's sort
+// caller's arrays, through serial_host_call_any like the address call (verify's root is a whole-call input; the device forms one kernel, no workspace).
+// build and proof work on ONE tree: the host-pointer forms run on the context itself or on its first shard, the whole tree staged in the first slot (proof:
+// serial_host_call with the tree as a whole-call input; build: one piece, serial_host_piece); build's sort
 // takes its workspace (36 B per padded leaf) from the context, so its device form joins the ws_free chain.  fused_top = 0 (env PLUME_MERKLE_FUSED_TOP=0, the A/B
 // knob of tests/gpu_debug/merkle_timing.py) runs one k_merkle_level launch per depth instead of k_merkle_top.  The launchers come in as a hook struct.
 struct MerkleLeafArgs;
