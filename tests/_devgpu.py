@@ -44,3 +44,4 @@ def poisoned():
 GPU = _devsim.Lanes(lib, "dg_", _failed)
 fe_op, fe_raw, group_raw, sc_op, glv, sha256 = GPU.fe_op, GPU.fe_raw, GPU.group_raw, GPU.sc_op, GPU.glv, GPU.sha256
 eisd_entries, eis_half_gcd, eis_consistent = GPU.eisd_entries, GPU.eis_half_gcd, GPU.eis_consistent
+h2c_op, rfc6979 = GPU.h2c_op, GPU.rfc6979

@@ -45,7 +45,7 @@ NPOS = 65          # PLUME_NPOS: positions of the Eisenstein digits of a pair of
 
 
 class Lanes:
-    """The field, scalar, group-law, recoding, SHA-256 and half-GCD unit entry points of ONE build of tests/devsim/lane_ops.h: the host build (prefix ds_, this module's
+    """The field, scalar, group-law, recoding, SHA-256, half-GCD, hash-to-curve-map and nonce-loop unit entry points of ONE build of tests/devsim/lane_ops.h: the host build (prefix ds_, this module's
     library) or the GPU build (prefix dg_, tests/_devgpu.py).  `lib` is a callable that returns the loaded library (and may refuse to), `failed(name, rc)` is called
     with every non-zero return value.  tests/_lane_cases.py holds the checks that take one of these as their backend."""
 
@@ -138,6 +138,36 @@ class Lanes:
         return out.astype(bool)
 
 
+    def h2c_op(self, op, *cols, placed=None):
+        """the map behind hash_to_curve on chosen field elements (tests/devsim/lane_ops.h h2c_op): up to six columns of ints (< 2^256; op 6: ONE column of ints < 2^384)
+        -> [(the op's values, flag)].  placed, if given, is called with the order the elements go to the library in (here the caller's) before anything runs."""
+        nout = {0: 5, 1: 3, 2: 3, 3: 4, 4: 3, 5: 3, 6: 1}[op]
+        n = len(cols[0])
+        if placed is not None:
+            placed(list(range(n)))
+        inp = np.zeros((n, 48), dtype=np.uint32)
+        if op == 6:
+            inp[:, :12] = np.array([[(v >> (32 * (11 - j))) & 0xFFFFFFFF for j in range(12)] for v in cols[0]], dtype=np.uint32).reshape(n, 12)
+        else:
+            for c, col in enumerate(cols):
+                inp[:, 8 * c:8 * c + 8] = to_limbs(col).reshape(n, 8)
+        out = np.zeros((n, 49), dtype=np.uint32)
+        self._call("h2c_op", C.c_int(op), C.c_size_t(n), _p(inp, u32p), _p(out, u32p))
+        assert not out[:, 8 * nout:48].any()
+        return [(from_limbs(out[r, :8 * nout].reshape(nout, 8)), int(out[r, 48])) for r in range(n)]
+
+    def rfc6979(self, cap, q, x, h1, aux=None, placed=None):
+        """rfc6979_k_core<cap, aux given> per element (tests/devsim/lane_ops.h rfc6979_lane): columns of ints < 2^256 (q: top bit set) -> [(k, used)]"""
+        n = len(q)
+        if placed is not None:
+            placed(list(range(n)))
+        be = lambda col: np.ascontiguousarray(to_limbs(col).reshape(n, 8)[:, ::-1])  # noqa: E731
+        Q, X, H, A = be(q), be(x), be(h1), be(aux if aux is not None else [0] * n)
+        k, used = np.zeros((n, 8), dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        self._call("rfc6979", C.c_int(cap), C.c_int(0 if aux is None else 1), C.c_size_t(n), _p(Q, u32p), _p(X, u32p), _p(H, u32p), _p(A, u32p), _p(k, u32p), _p(used, u32p))
+        return list(zip(from_limbs(np.ascontiguousarray(k[:, ::-1])), [int(u) for u in used]))
+
+
 def _host_failed(name, rc):
     raise AssertionError(f"{name} returned {rc}")
 
@@ -145,6 +175,7 @@ def _host_failed(name, rc):
 HOST = Lanes(lib, "ds_", _host_failed)
 fe_op, fe_raw, group_raw, sc_op, glv, sha256 = HOST.fe_op, HOST.fe_raw, HOST.group_raw, HOST.sc_op, HOST.glv, HOST.sha256
 eisd_entries, eis_half_gcd, eis_consistent = HOST.eisd_entries, HOST.eis_half_gcd, HOST.eis_consistent
+h2c_op, rfc6979 = HOST.h2c_op, HOST.rfc6979
 
 def eis_digit(code):
     """digit code of csrc/plume_ec.h -> the Eisenstein integer (a, b) = a + b w it stands for: 0 -> 0; 1 + 6 row + 2 j + neg -> (-1)^neg w^j (1 | theta = 1 - w | 2)"""

@@ -1,13 +1,16 @@
-"""Case generators and checks of the field, scalar, group-law, recoding, SHA-256 and half-GCD unit tests, as functions of a BACKEND: a tests/_devsim.Lanes -- the host
-build of tests/devsim/lane_ops.h (tests/test_devsim.py) or its gfx950 build (tests/test_gpu_devlanes.py).  The reference in every check is Python integers, pow,
-hashlib and oracle.plume_oracle -- never the other build of the header."""
+"""Case generators and checks of the field, scalar, group-law, recoding, SHA-256, half-GCD, hash-to-curve-map and nonce-loop unit tests, as functions of a BACKEND: a
+tests/_devsim.Lanes -- the host build of tests/devsim/lane_ops.h (tests/test_devsim.py) or its gfx950 build (tests/test_gpu_devlanes.py).  The reference in every check
+is Python integers, pow, hashlib, hmac (tests/_rfc6979.py) and oracle.plume_oracle -- never the other build of the header."""
+import functools
 import hashlib
 import random
 import re
+from collections import namedtuple
 from pathlib import Path
 
 from oracle import plume_oracle as O
 from tests import _devsim
+from tests import _rfc6979 as RF
 
 ROOT = Path(__file__).resolve().parent.parent
 P, N = O.P, O.N
@@ -52,9 +55,20 @@ class Placed:
         self._rng.shuffle(perm)
         return perm
 
-    def _run(self, fn, cols, fixed=()):
+    def _perm_in_groups(self, n, group=64):
+        """shuffled inside every run of 64 elements: what shares a wavefront in the caller's order still does, in other lanes"""
+        perm = []
+        for g0 in range(0, n, group):
+            blk = list(range(g0, min(n, g0 + group)))
+            self._rng.shuffle(blk)
+            perm += blk
+        return perm
+
+    def _run(self, fn, cols, fixed=(), perm=None, placed=None):
         n = len(cols[0])
-        perm = self._perm(n)
+        perm = self._perm(n) if perm is None else perm
+        if placed is not None:
+            placed(perm)                                   # the order the backend gets: the coverage conditions of a check are asserted on THIS order
         out = fn(*fixed, *[None if c is None else [c[i] for i in perm] for c in cols])
         back = [None] * n
         for k, i in enumerate(perm):
@@ -81,6 +95,12 @@ class Placed:
 
     def eis_consistent(self, cs, which=0):
         return self._run(lambda c: list(self._b.eis_consistent(c, which)), [cs])
+
+    def h2c_op(self, op, *cols, placed=None):
+        return self._run(self._b.h2c_op, list(cols), (op,), self._perm_in_groups(len(cols[0])), placed)
+
+    def rfc6979(self, cap, q, x, h1, aux=None, placed=None):
+        return self._run(self._b.rfc6979, [q, x, h1, aux], (cap,), self._perm_in_groups(len(q)), placed)
 
     def sha256(self, data):
         return self._b.sha256(data)
@@ -528,3 +548,274 @@ def check_one_wave_of_edge_pairs(B):
     assert B.fe_op(15, ea) == [pow(x % P, -1, P) if x % P else 0 for x in ea]
     assert B.fe_op(26, ea, eb) == [(y if x & 1 else x) % P for x, y in zip(ea, eb)]
     assert B.fe_op(22, ea) == [11 * x % P for x in ea]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------- the map behind hash_to_curve
+ISO_A, ISO_B, SSWU_Z = O.ISO_A, O.ISO_B, O.Z
+SQRT11 = pow(11, (P + 1) // 4, P)                                 # plume_h2c.h fe_sqrt_neg_z
+assert SQRT11 * SQRT11 % P == 11
+U_EXC = (pow(SQRT11, -1, P), P - pow(SQRT11, -1, P))              # Z u^2 = -1: tv2 = tv1 (tv1 + 1) = 0 with u != 0
+SswuRef = namedtuple("SswuRef", "pt tv1 tv2_zero gx1 is_sq flip")
+
+
+def _inv(x):
+    return pow(x, -1, P)
+
+
+def on_eprime(pt):
+    return (pt[1] * pt[1] - pt[0] ** 3 - ISO_A * pt[0] - ISO_B) % P == 0
+
+
+def eprime_add(p, q):
+    """affine addition on E': y^2 = x^3 + A' x + B' over Python integers; None is the identity"""
+    if p is None or q is None:
+        return q if p is None else p
+    (x0, y0), (x1, y1) = p, q
+    if x0 == x1:
+        if (y0 + y1) % P == 0:
+            return None
+        lam = (3 * x0 * x0 + ISO_A) * _inv(2 * y0) % P
+    else:
+        lam = (y1 - y0) * _inv(x1 - x0) % P
+    x3 = (lam * lam - x0 - x1) % P
+    return x3, (lam * (x0 - x3) - y0) % P
+
+
+def pair_kind(p, q):
+    """which branch of eprime_add_frac the points take"""
+    if p[0] != q[0]:
+        return "chord"
+    return "identity" if (p[1] + q[1]) % P == 0 else "tangent"
+
+
+@functools.lru_cache(maxsize=None)
+def sswu_ref(u):
+    """the oracle's simplified SWU of u and what classifies it: tv1 = Z u^2, whether tv2 = tv1 (tv1 + 1) is zero, gx1 = g(x1), Euler's criterion on it, and whether the
+    last step negates y (sgn0(u) != sgn0(y) before it; y before it from the oracle's sqrt_ratio)"""
+    tv1 = SSWU_Z * u * u % P
+    tv2 = (tv1 * tv1 + tv1) % P
+    tv3 = ISO_B * (tv2 + 1) % P
+    tv4 = ISO_A * (SSWU_Z if tv2 == 0 else -tv2) % P
+    x1 = tv3 * _inv(tv4) % P
+    gx1 = (x1 ** 3 + ISO_A * x1 + ISO_B) % P
+    is_sq = pow(gx1, (P - 1) // 2, P) == 1
+    _, y1 = O.sqrt_ratio_3mod4((tv3 ** 3 + ISO_A * tv3 * tv4 * tv4 + ISO_B * tv4 ** 3) % P, pow(tv4, 3, P))
+    y_pre = y1 if is_sq else tv1 * u % P * y1 % P
+    pt = O.map_to_curve_sswu(u)
+    assert on_eprime(pt) and gx1 != 0 and pt[1] in (y_pre, P - y_pre)
+    return SswuRef(pt, tv1, tv2 == 0, gx1, is_sq, (u & 1) != (y_pre & 1))
+
+
+@functools.lru_cache(maxsize=None)
+def map2_ref(u0, u1):
+    """(iso(sswu(u0)) + iso(sswu(u1)) on secp256k1, the branch the sum on E' takes)"""
+    p0, p1 = sswu_ref(u0).pt, sswu_ref(u1).pt
+    return O.pt_add(O.iso_map(p0), O.iso_map(p1)), pair_kind(p0, p1)
+
+
+def _full_waves(order, wave=64):
+    return [order[w:w + wave] for w in range(0, len(order) - wave + 1, wave)]
+
+
+def _scaled(rng, v):
+    """v as a fraction with a random nonzero denominator"""
+    s = rng.randrange(1, P)
+    return v * s % P, s
+
+
+def _jac_affine(X, Y, Z):
+    zi = _inv(Z)
+    return X * zi * zi % P, Y * zi ** 3 % P
+
+
+def check_sswu(B, groups=8):
+    """sswu_frac (op 0) and its intermediates against the oracle's map, every full wavefront holding a tv2 == 0 lane and lanes of both is_sq values"""
+    rng = random.Random(61)
+    edge = [0, 1, 2, P - 1, P - 2, U_EXC[0], U_EXC[1]]
+    us = []
+    for _ in range(groups):
+        us += edge + [rng.randrange(P) for _ in range(64 - len(edge))]
+    us += [rng.randrange(P) for _ in range(37)]                    # a ragged last wavefront
+    ref = [sswu_ref(u) for u in us]
+    assert {0, 1, 2, P - 1, P - 2, U_EXC[0], U_EXC[1]} <= set(us) and all(SSWU_Z * u * u % P == P - 1 for u in U_EXC)
+    assert {u for u, r in zip(us, ref) if r.tv2_zero} == {0, U_EXC[0], U_EXC[1]}
+    for sq in (False, True):
+        for flip in (False, True):
+            assert sum(1 for r in set(ref) if (r.is_sq, r.flip) == (sq, flip)) >= 20, (sq, flip)
+
+    def placed(order):
+        waves = _full_waves(order)
+        assert len(waves) >= groups
+        for w in waves:
+            assert any(ref[i].tv2_zero for i in w) and {ref[i].is_sq for i in w} == {False, True}
+    got = B.h2c_op(0, us, placed=placed)
+    for u, r, ((xn, xd, y, tv1, root), is_sq) in zip(us, ref, got):
+        assert xd != 0, hex(u)
+        assert (xn * _inv(xd) % P, y) == r.pt, hex(u)
+        assert tv1 == (-11 * u * u) % P == r.tv1, hex(u)
+        assert is_sq == int(r.is_sq), hex(u)
+        assert root * root % P == (r.gx1 if r.is_sq else SSWU_Z * r.gx1 % P), hex(u)
+
+
+def _eprime_points(rng, count):
+    return [sswu_ref(rng.randrange(P)).pt for _ in range(count)]
+
+
+def check_eprime_add(B, groups=6):
+    """eprime_add_frac (op 3) against the affine addition on E' over Python integers: equal points arrive as DIFFERENT fractions (independent random denominators), every
+    full wavefront holds tangent, identity and chord lanes"""
+    rng = random.Random(62)
+    pts = _eprime_points(rng, 48)
+    neg = lambda p: (p[0], (-p[1]) % P)  # noqa: E731
+    pairs = []
+    for g in range(groups):
+        pairs += [(p, p) for p in rng.sample(pts, 5)] + [(p, neg(p)) for p in rng.sample(pts, 5)]
+        pairs += [tuple(rng.sample(pts, 2)) for _ in range(10)]                                            # distinct points
+        pairs += [(rng.choice(pts), rng.choice([neg, lambda p: p])(rng.choice(pts))) for _ in range(44)]   # random pairs, whatever they are
+    pairs += [tuple(rng.sample(pts, 2)) for _ in range(29)]
+    kinds = [pair_kind(p, q) for p, q in pairs]
+    cols = [[], [], [], [], [], []]
+    for p, q in pairs:
+        a, b = _scaled(rng, p[0])
+        c, d = _scaled(rng, q[0])
+        for col, v in zip(cols, (a, b, p[1], c, d, q[1])):
+            col.append(v)
+    assert all(b != d for b, d in zip(cols[1], cols[4]))
+
+    def placed(order):
+        waves = _full_waves(order)
+        assert len(waves) >= groups
+        for w in waves:
+            assert {kinds[i] for i in w} == {"tangent", "identity", "chord"}
+    got = B.h2c_op(3, *cols, placed=placed)
+    for (p, q), kind, ((xn, xd, yn, yd), flag) in zip(pairs, kinds, got):
+        want = eprime_add(p, q)
+        assert (want is None) == (kind == "identity")
+        assert flag == int(want is not None), (kind, p, q)
+        if want is not None:
+            assert xd != 0 and yd != 0, (kind, p, q)
+            assert (xn * _inv(xd) % P, yn * _inv(yd) % P) == want, (kind, p, q)
+
+
+def check_iso3(B, count=300):
+    """iso3_frac_to_jac with y affine (op 4) and y a fraction (op 5): the affine value of the Jacobian output is the oracle's iso_map, a point of secp256k1"""
+    rng = random.Random(63)
+    pts = _eprime_points(rng, count - 3) + [sswu_ref(u).pt for u in (0, U_EXC[0], U_EXC[1])]
+    fx = [_scaled(rng, p[0]) for p in pts]
+    fy = [_scaled(rng, p[1]) for p in pts]
+    xn, xd, yn, yd = [f[0] for f in fx], [f[1] for f in fx], [f[0] for f in fy], [f[1] for f in fy]
+    for got in (B.h2c_op(4, xn, xd, [p[1] for p in pts]), B.h2c_op(5, xn, xd, yn, yd)):
+        for p, ((X, Y, Z), inf) in zip(pts, got):
+            assert inf == 0 and Z != 0, p
+            q = _jac_affine(X, Y, Z)
+            assert q == O.iso_map(p) and O.is_on_curve(q), p
+
+
+def map2_pairs(groups):
+    """pairs (u0, u1) in 64-lane groups that each hold the pairs the chord cannot take -- (u, u), (u, -u), (0, 0), and the u whose tv2 is zero among themselves: 0 and
+    +-1/sqrt(11) share ONE x on E', so (0, +-1/sqrt(11)) are a tangent and an identity pair of DIFFERENT u -- among random pairs"""
+    rng = random.Random(64)
+    e0, e1 = U_EXC
+    pairs = []
+    for _ in range(groups):
+        us = [rng.randrange(P) for _ in range(3)] + [1, 2, P - 1]
+        grp = [(u, u) for u in us[:4]] + [(u, P - u) for u in us[:4]] + [(0, 0), (0, e0), (0, e1), (e0, 0), (e0, e1), (e1, e0), (e0, e0), (e1, e1)]
+        grp += [(rng.randrange(P), rng.randrange(P)) for _ in range(64 - len(grp))]
+        pairs += grp
+    return pairs
+
+
+def check_map2(B, groups=6, counts=(1, 63, 64, 65, 4096 + 37)):
+    """map2_to_curve_jac (op 1) against iso(sswu(u0)) + iso(sswu(u1)) of the oracle, inf exactly for the opposite pairs; the same Jacobian words from the two maps run
+    apart and maps_to_curve_jac (op 2: the two-role ingest kernel's form); then op 1 at the batch sizes around a wavefront"""
+    pairs = map2_pairs(groups)
+    assert {(0, 0), (0, U_EXC[0]), (0, U_EXC[1]), (U_EXC[0], U_EXC[1])} <= set(pairs) and any(a == b for a, b in pairs) and any(a and a == P - b for a, b in pairs)
+    assert {map2_ref(0, U_EXC[0])[1], map2_ref(0, U_EXC[1])[1]} == {"tangent", "identity"}
+
+    def run(op, prs):
+        ref = [map2_ref(*pr) for pr in prs]
+
+        def placed(order):
+            for w in _full_waves(order):
+                assert {ref[i][1] for i in w} == {"tangent", "identity", "chord"}
+        got = B.h2c_op(op, [pr[0] for pr in prs], [pr[1] for pr in prs], placed=placed)
+        for pr, (want, kind), ((X, Y, Z), inf) in zip(prs, ref, got):
+            assert (want is None) == (kind == "identity")
+            assert inf == int(kind == "identity"), (op, kind, pr)
+            if not inf:
+                assert Z != 0 and _jac_affine(X, Y, Z) == want, (op, kind, pr)
+        return got
+    assert len(_full_waves(pairs)) == groups
+    assert run(2, pairs) == run(1, pairs)
+    for n in counts:
+        run(1, [pairs[i % len(pairs)] for i in range(n)])
+
+
+def check_be48(B):
+    """fe_from_be48_words (op 6): OS2IP of 48 bytes mod p, at the multiples of p, the word boundaries and both ends"""
+    rng = random.Random(65)
+    top = (2**384 // P) * P
+    vals = [0, 1, P - 1, P, P + 1, 2 * P, 2**256 - 1, 2**256, 2**256 + 1, 2**384 - 1, top - 1, top, top + 1]
+    vals += [2**(32 * k) + d for k in range(1, 12) for d in (-1, 1)]
+    vals += [rng.getrandbits(384) for _ in range(300)] + [rng.randrange(2**128) * P + rng.choice([-1, 0, 1]) for _ in range(40)]
+    assert all(0 <= v < 2**384 for v in vals) and top + P >= 2**384
+    got = B.h2c_op(6, vals)
+    assert [g[0][0] for g in got] == [v % P for v in vals]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------- RFC 6979's retry loop
+Q_N, Q_HALF, Q_64TH = N, 2**255 + 1, 2**256 - 2**250             # a retry with probability 2^-128 | about 1/2 | 1/64: about one lane of a wavefront
+NONCE_LANES = 4096 + 37
+NONCE_SEED = 6979
+
+
+@functools.lru_cache(maxsize=None)
+def nonce_reference():
+    """seeded x, h1 and aux of NONCE_LANES lanes and tests/_rfc6979.py's (k, used) for every modulus, with and without aux: computed once per process, never changed"""
+    rng = random.Random(NONCE_SEED)
+    x = [rng.getrandbits(256) for _ in range(NONCE_LANES)]
+    h1 = [rng.getrandbits(256) for _ in range(NONCE_LANES)]
+    aux = [rng.getrandbits(256) for _ in range(NONCE_LANES)]
+    edge_h = [0, 1, 2**255, Q_HALF - 1, Q_HALF, Q_HALF + 1, Q_64TH - 1, Q_64TH, Q_64TH + 1, N - 1, N, N + 1, 2**256 - 1]     # bits2octets: h1 around every modulus
+    edge_x = [0, 1, 2**256 - 1]
+    h1[3:3 + len(edge_h)] = edge_h
+    x[20:20 + len(edge_x)] = edge_x
+    b = lambda v: v.to_bytes(32, "big")  # noqa: E731
+    ref = {(q, with_aux): [RF.rfc6979_k(q, b(xi), b(hi), b(ai) if with_aux else None) for xi, hi, ai in zip(x, h1, aux)]
+           for q in (Q_N, Q_HALF, Q_64TH) for with_aux in (False, True)}
+    return x, h1, aux, ref
+
+
+def nonce_want(q, with_aux, cap, n=NONCE_LANES):
+    """the reference under a cap: k = 0, used = 0 where the first `cap` candidates were all out of range"""
+    return [(k, used) if used <= cap else (0, 0) for k, used in nonce_reference()[3][(q, with_aux)][:n]]
+
+
+def check_nonce_retries(B, counts=(1, 63, 64, 65)):
+    """rfc6979_k_core for three moduli x CAP 16 | 4 x aux off | on against tests/_rfc6979.py, k and used of every lane.  What the reference must show, per wavefront of
+    the order the backend gets, before anything is compared: q = n: every lane 1; q = 2^255 + 1: at least three distinct counts in every full wavefront, and under CAP 4
+    both an exhausted lane (0) and one that took the last candidate (4); q = 2^256 - 2^250: at least half the wavefronts with one to three retrying lanes among lanes
+    that must keep their k"""
+    x, h1, aux, _ = nonce_reference()
+    for q in (Q_N, Q_HALF, Q_64TH):
+        for with_aux in (False, True):
+            for cap in (16, 4):
+                for n in ((NONCE_LANES,) + tuple(counts) if q == Q_HALF else (NONCE_LANES,)):
+                    want = nonce_want(q, with_aux, cap, n)
+
+                    def placed(order):
+                        waves = _full_waves(order)
+                        assert len(waves) == n // 64
+                        if q == Q_N:
+                            assert all(used == 1 for _, used in want)
+                        elif q == Q_HALF:
+                            assert all(len({want[i][1] for i in w}) >= 3 for w in waves)
+                            if cap == 4 and n == NONCE_LANES:
+                                assert {0, 4} <= {used for _, used in want}
+                        else:
+                            few = sum(1 for w in waves if 1 <= sum(1 for i in w if want[i][1] != 1) <= 3)
+                            assert 2 * few >= len(waves) > 0, (few, len(waves))
+                    got = B.rfc6979(cap, [q] * n, x[:n], h1[:n], aux[:n] if with_aux else None, placed=placed)
+                    assert all((k == 0) == (used == 0) and k < q and used <= cap for k, used in want)
+                    bad = [i for i in range(n) if got[i] != want[i]]
+                    assert not bad, (hex(q), with_aux, cap, n, bad[:8], [got[i] for i in bad[:3]], [want[i] for i in bad[:3]])

@@ -104,6 +104,16 @@ __global__ __launch_bounds__(64) void k_eisd_entries(uint32_t* out) {
     const uint32_t idx = blockIdx.x * kWave + threadIdx.x;
     if (idx < 81u) L::eisd_entries_lane(idx, out + 2 * idx);
 }
+template <int OP>
+__global__ __launch_bounds__(64) void k_h2c_op(size_t count, const uint32_t* in, uint32_t* out) {
+    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
+    if (i < count) L::h2c_op<OP>(in + L::kH2cInWords * i, out + L::kH2cOutWords * i);
+}
+template <int CAP, bool AUX>
+__global__ __launch_bounds__(64) void k_rfc6979(size_t count, const uint32_t* q, const uint32_t* x, const uint32_t* h1, const uint32_t* aux, uint32_t* k, uint32_t* used) {
+    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
+    if (i < count) L::rfc6979_lane<CAP, AUX>(q + 8 * i, x + 8 * i, h1 + 8 * i, aux + 8 * i, k + 8 * i, used + i);
+}
 }  // namespace
 
 extern "C" {
@@ -197,6 +207,28 @@ int dg_eis_consistent(uint32_t n, const uint8_t* c_be, int which, uint8_t* out) 
         c.fail("no such tamper");
     c.sync();
     c.back(out, dout, n);
+    return c.finish();
+}
+int dg_h2c_op(int op, size_t count, const uint32_t* in, uint32_t* out) {
+    Call c("dg_h2c_op");
+    const uint32_t* din = c.in(in, L::kH2cInWords * count);
+    uint32_t* dout = c.out<uint32_t>(L::kH2cOutWords * count);
+    if (c.ok() && count && !L::dispatch<L::kH2cOps>(op, [&](auto OP) { hipLaunchKernelGGL(k_h2c_op<decltype(OP)::value>, grid_for(count), dim3(kWave), 0, 0, count, din, dout); }))
+        c.fail("no such op");
+    c.sync();
+    c.back(out, dout, L::kH2cOutWords * count);
+    return c.finish();
+}
+int dg_rfc6979(int cap, int aux_on, size_t count, const uint32_t* q, const uint32_t* x, const uint32_t* h1, const uint32_t* aux, uint32_t* k, uint32_t* used) {
+    Call c("dg_rfc6979");
+    const uint32_t *dq = c.in(q, 8 * count), *dx = c.in(x, 8 * count), *dh = c.in(h1, 8 * count), *da = c.in(aux, 8 * count);
+    uint32_t *dk = c.out<uint32_t>(8 * count), *du = c.out<uint32_t>(count);
+    if (c.ok() && count && !L::dispatch_nonce(cap, aux_on, [&](auto CAP, auto AUX) {
+            hipLaunchKernelGGL((k_rfc6979<decltype(CAP)::value, decltype(AUX)::value>), grid_for(count), dim3(kWave), 0, 0, count, dq, dx, dh, da, dk, du); }))
+        c.fail("no such cap");
+    c.sync();
+    c.back(k, dk, 8 * count);
+    c.back(used, du, count);
     return c.finish();
 }
 }

@@ -44,6 +44,18 @@ int ds_group_raw(int op, size_t count, const uint32_t* px, const uint32_t* py, c
 int ds_sc_op(int op, size_t count, const uint32_t* a, const uint32_t* b, uint32_t* out) {
     return L::dispatch<L::kScOps>(op, [&](auto OP) { for (size_t i = 0; i < count; i++) L::sc_op<decltype(OP)::value>(a + 8 * i, b + 8 * i, out + 8 * i); }) ? 0 : -1;
 }
+// the map behind hash_to_curve on chosen field elements (lane_ops.h h2c_op): 48 words in, 49 out per element
+int ds_h2c_op(int op, size_t count, const uint32_t* in, uint32_t* out) {
+    return L::dispatch<L::kH2cOps>(op, [&](auto OP) {
+        for (size_t i = 0; i < count; i++) L::h2c_op<decltype(OP)::value>(in + L::kH2cInWords * i, out + L::kH2cOutWords * i);
+    }) ? 0 : -1;
+}
+// RFC 6979's candidate loop for any modulus (lane_ops.h rfc6979_lane): cap 16 or 4, aux on or off for the whole call; 8 big-endian words per value
+int ds_rfc6979(int cap, int aux_on, size_t count, const uint32_t* q, const uint32_t* x, const uint32_t* h1, const uint32_t* aux, uint32_t* k, uint32_t* used) {
+    return L::dispatch_nonce(cap, aux_on, [&](auto CAP, auto AUX) {
+        for (size_t i = 0; i < count; i++) L::rfc6979_lane<decltype(CAP)::value, decltype(AUX)::value>(q + 8 * i, x + 8 * i, h1 + 8 * i, aux + 8 * i, k + 8 * i, used + i);
+    }) ? 0 : -1;
+}
 uint32_t ds_wbits() { return PLUME_WBITS; }                  // width of the grid the generator's wide digits sit on (4)
 // k (8 limbs) -> m1[4], neg1, m2[4], neg2 (10 words) and the PLUME_NPOS Eisenstein digit codes of the pair (int8, rows of 65)
 int ds_glv(size_t count, const uint32_t* k, uint32_t* out, int8_t* digits) {

@@ -1,4 +1,4 @@
-// Per-element bodies of the field, scalar and group-law unit tests -- TEST INFRASTRUCTURE ONLY (never linked into the product library).
+// Per-element bodies of the field, scalar, group-law, hash-to-curve-map and nonce unit tests -- TEST INFRASTRUCTURE ONLY (never linked into the product library).
 // One set of bodies, two builds: tests/devsim/devsim.cpp loops over them on the host (g++, the plain-C branch of every product, PLUME_FE_CHECK's assertions), and
 // tests/devgpu/devgpu.hip runs one lane per element on gfx950 (the inline-asm branch of every product, the device forms of mad_i64 / sel32 / opaque_*, the GPU's doubles).
 // The OP is a template parameter everywhere: each op is compiled the way a production kernel sees it, with its constants visible -- never a runtime switch in a kernel.
@@ -10,12 +10,16 @@
 
 #include "plume_eis.h"        // -> plume_ec.h -> plume_field.h
 #include "plume_sha256.h"
+#include "plume_h2c.h"
+#include "plume_nonce.h"      // -> plume_stages.h
 
 namespace plume_lanes {
 using namespace plume;
 
 constexpr int kFeOps = 28, kFeRawOps = 18, kGroupRawOps = 6, kScOps = 4, kEisTampers = 5;
 constexpr int kFeRawOutWords = 18;      // r, then the second output of the forms that have one (zeros otherwise)
+constexpr int kH2cOps = 7;
+constexpr int kH2cInWords = 48, kH2cOutWords = 49;      // six field elements in; six out (zeros where an op has fewer), then one word of flag
 
 // host side: the runtime op number -> f(std::integral_constant<int, OP>); false if there is no such op
 template <int N, class F>
@@ -209,6 +213,68 @@ PLUME_HD void eisd_entries_lane(uint32_t idx, uint32_t* out) {
     const int ta = (int)(idx / 9u) - 4, tb = (int)(idx % 9u) - 4;
     out[0] = eisd_entry_table(ta, tb);
     out[1] = eisd_entry(ta, tb);
+}
+
+// The map behind hash_to_curve (plume_h2c.h) on CHOSEN field elements -- through the ABI u0 and u1 are SHA-256 outputs, so the branches that depend on them (the tangent
+// and the identity of eprime_add_frac, SSWU's tv2 == 0 exception) are reached from here only.
+// op: 0 sswu_frac(u, &extra) -> xn, xd, y, extra.tv1, extra.root | extra.is_sq
+//     1 map2_to_curve_jac(u0, u1) -> X, Y, Z | inf (the raw Jacobian representative)
+//     2 the same from two sswu_frac calls and maps_to_curve_jac, (a, b, y0) = map(u1), (c, d, y1) = map(u0) as its comment states -> X, Y, Z | inf
+//     3 eprime_add_frac(a, b, y0, c, d, y1) -> xn, xd, yn, yd | the returned bool (zeros when false)
+//     4 iso3_frac_to_jac(xn, xd, y) -> X, Y, Z | inf,  5 iso3_frac_to_jac(xn, xd, yn, &yd) -> X, Y, Z | inf
+//     6 fe_from_be48_words on the first 12 words of in (big-endian, most significant first) -> the value
+// in: six 256-bit integers as 8 little-endian words each (any value, also >= p); out: six canonical values, then the flag
+template <int OP>
+PLUME_HD void h2c_op(const uint32_t* in, uint32_t* out) {
+    fe i0, i1, i2, i3, i4, i5;
+    fe o0 = fe_zero(), o1 = fe_zero(), o2 = fe_zero(), o3 = fe_zero(), o4 = fe_zero(), o5 = fe_zero();
+    uint32_t flag = 0;
+    fe_from_words(i0, in); fe_from_words(i1, in + 8); fe_from_words(i2, in + 16); fe_from_words(i3, in + 24); fe_from_words(i4, in + 32); fe_from_words(i5, in + 40);
+    if constexpr (OP == 0) {
+        sswu_extra ex;
+        sswu_frac(o0, o1, o2, i0, &ex);
+        o3 = ex.tv1; o4 = ex.root; flag = ex.is_sq ? 1u : 0u;
+    } else if constexpr (OP == 1 || OP == 2) {
+        jac h;
+        if constexpr (OP == 1) map2_to_curve_jac(h, i0, i1);
+        else {
+            fe a, b, y0, c, d, y1;
+            sswu_frac(c, d, y1, i0);
+            sswu_frac(a, b, y0, i1);
+            maps_to_curve_jac(h, a, b, y0, c, d, y1);
+        }
+        o0 = h.x; o1 = h.y; o2 = h.z; flag = h.inf;
+    } else if constexpr (OP == 3) {
+        flag = eprime_add_frac(o0, o1, o2, o3, i0, i1, i2, i3, i4, i5) ? 1u : 0u;
+        if (!flag) { o0 = fe_zero(); o1 = fe_zero(); o2 = fe_zero(); o3 = fe_zero(); }
+    } else if constexpr (OP == 4 || OP == 5) {
+        jac h;
+        if constexpr (OP == 4) iso3_frac_to_jac(h, i0, i1, i2); else iso3_frac_to_jac(h, i0, i1, i2, &i3);
+        o0 = h.x; o1 = h.y; o2 = h.z; flag = h.inf;
+    } else {
+        fe_from_be48_words(o0, in);
+    }
+    fe_normalize(o0); fe_normalize(o1); fe_normalize(o2); fe_normalize(o3); fe_normalize(o4); fe_normalize(o5);
+    fe_to_words(out, o0); fe_to_words(out + 8, o1); fe_to_words(out + 16, o2); fe_to_words(out + 24, o3); fe_to_words(out + 32, o4); fe_to_words(out + 40, o5);
+    out[48] = flag;
+}
+
+// RFC 6979's candidate loop (plume_nonce.h rfc6979_k_core) for ANY modulus q of 256 bits with its top bit set: with q = n a retry has probability 2^-128, with other
+// moduli the loop body runs, and on the GPU it runs while any lane of the wavefront still needs a candidate (nonce_any), the lanes that have their k keeping it.
+// q, x, h1, aux: 8 big-endian words each (aux is not read when AUX is off: on or off for the whole launch, as in sign_nonce); k: 8 big-endian words, *used: the count
+template <int CAP, bool AUX>
+PLUME_HD void rfc6979_lane(const uint32_t* q, const uint32_t* x, const uint32_t* h1, const uint32_t* aux, uint32_t* k, uint32_t* used) {
+    uint32_t qw[8], xw[8], hw[8], aw[8], kw[8];
+    PLUME_UNROLL for (int j = 0; j < 8; j++) { qw[j] = q[j]; xw[j] = x[j]; hw[j] = h1[j]; aw[j] = AUX ? aux[j] : x[j]; }
+    *used = rfc6979_k_core<CAP, AUX>(kw, qw, xw, hw, aw);
+    PLUME_UNROLL for (int j = 0; j < 8; j++) k[j] = kw[j];
+}
+// host side: (cap, aux) -> f(std::integral_constant<int, CAP>, std::bool_constant<AUX>); false for a cap that is not compiled
+template <class F>
+inline bool dispatch_nonce(int cap, int aux, F&& f) {
+    if (cap == 16) { if (aux) f(std::integral_constant<int, 16>{}, std::true_type{}); else f(std::integral_constant<int, 16>{}, std::false_type{}); return true; }
+    if (cap == 4) { if (aux) f(std::integral_constant<int, 4>{}, std::true_type{}); else f(std::integral_constant<int, 4>{}, std::false_type{}); return true; }
+    return false;
 }
 
 }  // namespace plume_lanes

@@ -536,12 +536,44 @@ def test_one_isogeny_after_adding_on_the_isogenous_curve():
     Python oracle for random pairs and for the pairs the chord formula cannot take -- u1 = u0 (a doubling) and u1 = -u0 (opposite points: the identity) -- which go through
     the two-isogeny fallback"""
     rng = random.Random(99)
-    us = [rng.randrange(P) for _ in range(24)] + [0, 1, 2, P - 1]
+    us = [rng.randrange(P) for _ in range(24)] + [0, 1, 2, P - 1] + list(LC.U_EXC)          # +-1/sqrt(11): Z u^2 = -1, SSWU's tv2 == 0 exception with u != 0
     pairs = [(rng.choice(us), rng.choice(us)) for _ in range(40)] + [(u, u) for u in us[:6]] + [(u, (P - u) % P) for u in us[:6]]
+    pairs += [(u, 5) for u in LC.U_EXC] + [(u, v) for u in (0,) + LC.U_EXC for v in (0,) + LC.U_EXC]
     for u0, u1 in pairs:
         want = O.pt_add(O.iso_map(O.map_to_curve_sswu(u0)), O.iso_map(O.map_to_curve_sswu(u1)))
         assert D.map2_to_curve(u0, u1) == O.pt_bytes(want), (u0, u1)
     assert D.map2_to_curve(5, P - 5) == bytes(64)
+
+
+def test_sswu_on_chosen_field_elements():
+    """the lane checks of the map behind hash_to_curve (tests/_lane_cases.py; tests/test_gpu_devlanes.py runs them on the gfx950 build), on the host build, in the
+    caller's order and in a shuffled one"""
+    LC.check_sswu(D.HOST)
+    LC.check_sswu(LC.Placed(D.HOST, 11))
+
+
+def test_addition_on_the_isogenous_curve_takes_its_tangent_and_identity_branches():
+    LC.check_eprime_add(D.HOST)
+    LC.check_eprime_add(LC.Placed(D.HOST, 12))
+
+
+def test_isogeny_on_fractions():
+    LC.check_iso3(LC.Placed(D.HOST, 13))
+
+
+def test_map2_on_chosen_pairs_and_the_two_role_form():
+    LC.check_map2(D.HOST, counts=(1, 63, 64, 65, 193))
+    LC.check_map2(LC.Placed(D.HOST, 14), counts=())
+
+
+def test_forty_eight_byte_reduction_at_the_multiples_of_p():
+    LC.check_be48(LC.Placed(D.HOST, 15))
+
+
+def test_nonce_retry_loop_for_moduli_that_retry():
+    """rfc6979_k_core for q = n, 2^255 + 1 and 2^256 - 2^250, CAP 16 and 4, with and without aux, against tests/_rfc6979.py.  On the host the any-lane vote is the
+    identity (one lane at a time): the lanes that must KEEP their k through another lane's round exist on the GPU only (tests/test_gpu_devlanes.py)"""
+    LC.check_nonce_retries(LC.Placed(D.HOST, 16))
 
 
 def _check_h2c_hints(get_hints, get_inter):

@@ -1,4 +1,4 @@
-"""The field, scalar, group-law, recoding, SHA-256 and half-GCD unit tests on the GPU's own code: the lane bodies of tests/devsim/lane_ops.h built for gfx950
+"""The field, scalar, group-law, recoding, SHA-256, half-GCD, hash-to-curve-map and nonce-loop unit tests on the GPU's own code: the lane bodies of tests/devsim/lane_ops.h built for gfx950
 (tests/devgpu/devgpu.hip, one lane per element, the op a template parameter of the kernel) under the same checks as the host build (tests/_lane_cases.py) -- the
 DEVICE branch of every product in plume_fe_mul.inc, the device forms of mad_i64 / sel32 / opaque_*, the GPU's doubles in plume_eis.h.  The reference is Python integers,
 pow, hashlib and the oracles; never the host build of the header (one count below compares the two builds, and asserts nothing).
@@ -83,6 +83,37 @@ def test_eis_half_gcd_on_the_gpus_doubles(B):
 
 def test_eis_pair_is_checked_before_it_is_used(B):
     LC.check_eis_pair_is_checked(B)
+
+
+# ------------------------------------------------------------------------------------------------------- the map behind hash_to_curve, the nonce's retry loop
+# Through the C ABI u0 and u1 are SHA-256 outputs and the modulus is n: the tangent and identity branches of the addition on E', SSWU's tv2 == 0 exception and the retry
+# loop's body run here only.  Every check asserts, from the reference and the order the GPU gets, that each full wavefront mixes these lanes with ordinary ones
+# (tests/_lane_cases.py) before it compares anything; batches are shuffled inside their 64-lane groups.
+def test_sswu_on_chosen_field_elements(B):
+    LC.check_sswu(B)
+
+
+def test_addition_on_the_isogenous_curve_takes_its_tangent_and_identity_branches(B):
+    LC.check_eprime_add(B)
+
+
+def test_isogeny_on_fractions(B):
+    LC.check_iso3(B)
+
+
+def test_map2_on_chosen_pairs_and_the_two_role_form(B):
+    """also 1, 63, 64, 65 and 4133 lanes through map2_to_curve_jac"""
+    LC.check_map2(B)
+
+
+def test_forty_eight_byte_reduction_at_the_multiples_of_p(B):
+    LC.check_be48(B)
+
+
+def test_nonce_retry_loop_keeps_every_lanes_k_while_other_lanes_retry(B):
+    """the loop runs while ANY lane of the wavefront needs a candidate (__any): with q = 2^255 + 1 half of all candidates are rejected, with q = 2^256 - 2^250 about one
+    lane of 64 retries while the others must keep their k; 4133 lanes per instantiation, and 1, 63, 64, 65"""
+    LC.check_nonce_retries(B)
 
 
 # ------------------------------------------------------------------------------------------------------- wavefronts that mix scalar lengths, through the C ABI
