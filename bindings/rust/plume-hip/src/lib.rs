@@ -72,6 +72,7 @@ pub const PLUME_STATUS_C_NOT_CANONICAL: u8 = 1;
 pub const PLUME_STATUS_BAD_SCALAR: u8 = 2;
 pub const PLUME_STATUS_IDENTITY: u8 = 4;
 pub const PLUME_STATUS_SELFCHECK_FAILED: u8 = 8;
+pub const PLUME_STATUS_BAD_TX: u8 = 16;
 pub const PLUME_RECOVER_MISMATCH: u8 = 0;
 pub const PLUME_RECOVER_MATCH: u8 = 1;
 pub const PLUME_RECOVER_INVALID: u8 = 3;
@@ -196,6 +197,12 @@ extern "C" {
         proof: *const u8, proof_len: *const u8, root32: *const u8, status: *mut u8) -> c_int;
     fn plume_merkle_verify_batch_device(ctx: *mut plume_ctx, leaf_format: c_int, addr_format: c_int, m: usize, address_or_leaf: *const u8, amount: *const u8, depth: usize,
         proof: *const u8, proof_len: *const u8, root32: *const u8, status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_eth_tx_sign_out_bytes(n: usize, txs_bytes: u64) -> usize;
+    fn plume_eth_tx_sign_batch(ctx: *mut plume_ctx, flags: c_int, n: usize, txs: *const u8, tx_off: *const u64, sk: *const u8, aux: *const u8, out: *mut u8,
+        out_len: *mut u32, hash32: *mut u8, r: *mut u8, s: *mut u8, v: *mut u8, chain_id: *mut u64, tx_type: *mut u8, status: *mut u8) -> c_int;
+    fn plume_eth_tx_sign_batch_device(ctx: *mut plume_ctx, flags: c_int, n: usize, txs: *const u8, tx_off: *const u64, txs_bytes: usize, sk: *const u8, aux: *const u8,
+        out: *mut u8, out_bytes: usize, out_len: *mut u32, hash32: *mut u8, r: *mut u8, s: *mut u8, v: *mut u8, chain_id: *mut u64, tx_type: *mut u8, status: *mut u8,
+        stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -378,6 +385,24 @@ impl HipEngine {
         if rc != 0 { return Err(last_error()); }
         if status[0] != PLUME_ETH_TX_OK { return Err(HipError("tx_signing_hash: not a signed transaction of a known kind".to_string())); }
         Ok(h)
+    }
+    /// The signed raw transaction of one UNSIGNED serialization (`plume_eth_tx_sign_batch`): legacy with 6 items (unprotected) or 9 (EIP-155: chainId, then two empty
+    /// strings), or a typed envelope 01 - 04 without its last three fields.  The signature is `ecdsa_sign`'s over Keccak-256 of `unsigned`, hedged with `aux` when
+    /// given.  An error for an item that is no such payload (the error `tx_signing_hash` gives for a bad item), for a key outside [1, n - 1] or a degenerate outcome, and
+    /// `HipError::self_check_failed()` when the self-check withheld the signature.
+    pub fn sign_tx(&self, sk: &[u8; 32], unsigned: &[u8], aux: Option<&[u8; 32]>) -> Result<Vec<u8>, HipError> {
+        let off = [0u64, unsigned.len() as u64];
+        let mut out = vec![0u8; unsafe { plume_eth_tx_sign_out_bytes(1, unsigned.len() as u64) }];
+        let (mut out_len, mut status) = ([0u32; 1], [0u8; 1]);
+        let null = std::ptr::null_mut::<u8>();
+        let rc = unsafe { plume_eth_tx_sign_batch(self.0, 0, 1, unsigned.as_ptr(), off.as_ptr(), sk.as_ptr(), aux.map_or(std::ptr::null(), |a| a.as_ptr()), out.as_mut_ptr(),
+                                                  out_len.as_mut_ptr(), null, null, null, null, std::ptr::null_mut(), null, status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        if status[0] & PLUME_STATUS_BAD_TX != 0 { return Err(HipError("sign_tx: not an unsigned transaction of a known kind".to_string())); }
+        if status[0] & PLUME_STATUS_SELFCHECK_FAILED != 0 { return Err(HipError::self_check_failed()); }
+        if status[0] != 0 { return Err(HipError(format!("sign_tx: no signature (status {})", status[0]))); }
+        out.truncate(out_len[0] as usize);
+        Ok(out)
     }
     /// The public key and the address of the sender of one raw signed transaction (`plume_eth_tx_sender_batch`), with the EIP-2 low-`s` rule.  An error when there is no
     /// sender: the framing is broken or the signature recovers no key.

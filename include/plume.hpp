@@ -423,6 +423,24 @@ inline Bytes32 tx_signing_hash(const uint8_t* raw, size_t len, Engine& eng = Eng
     if (st != PLUME_ETH_TX_OK) throw SignatureError();
     return h;
 }
+// The signed raw transaction of one UNSIGNED serialization -- exactly the bytes whose Keccak-256 the sender signs --, framed, hashed, signed and assembled on the GPU
+// (plume_hip.h plume_eth_tx_sign_batch): legacy with 6 items (unprotected) or 9 (EIP-155: chainId, then two empty strings), or a typed envelope 01 - 04 without its last three
+// fields.  The signature is ecdsa_sign's over that hash, hedged with aux when given.  Throws SignatureError for an item that is no such payload (as tx_signing_hash does for a
+// bad item) and for a degenerate outcome, plume_hip::SelfCheckError when the self-check withheld the signature.  tx_sender of the result is the key's address.
+inline std::vector<uint8_t> sign_tx(const SecretKey& sk, const uint8_t* unsigned_tx, size_t len, const Bytes32* aux = nullptr, Engine& eng = Engine::shared()) {
+    const uint64_t off[2] = {0, (uint64_t)len};
+    std::vector<uint8_t> out(plume_eth_tx_sign_out_bytes(1, len));
+    uint32_t out_len = 0;
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_eth_tx_sign_batch(eng.ctx(), 0, 1, unsigned_tx, off, sk.to_bytes().data(), aux ? aux->data() : nullptr, out.data(), &out_len, nullptr, nullptr, nullptr,
+                                             nullptr, nullptr, nullptr, &st),
+                     "plume_eth_tx_sign_batch");
+    if (st & PLUME_STATUS_BAD_TX) throw SignatureError();
+    if (st & PLUME_STATUS_SELFCHECK_FAILED) throw plume_hip::SelfCheckError("the signature does not recover the signer's key and was withheld (plume_set_sign_selfcheck)");
+    if (st) throw SignatureError();
+    out.resize(out_len);
+    return out;
+}
 inline std::pair<AffinePoint, std::array<uint8_t, 20>> tx_sender(const uint8_t* raw, size_t len, Engine& eng = Engine::shared(), bool low_s = true) {
     const uint64_t off[2] = {0, (uint64_t)len};
     uint8_t pk[64], st = 0xFF;

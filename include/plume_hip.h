@@ -46,6 +46,8 @@ typedef struct plume_ctx plume_ctx;
 #define PLUME_STATUS_IDENTITY 4        /* H == identity (randomizedsigner.rs:61) or s == 0 (randomizedsigner.rs:95) */
 #define PLUME_STATUS_SELFCHECK_FAILED 8 /* plume_set_sign_selfcheck(ctx, 1) only: the signer called the item good (no other bit) but its records do not verify; \
                                            every output record of the item is all zero */
+#define PLUME_STATUS_BAD_TX 16         /* plume_eth_tx_sign_batch* only: the unsigned transaction breaks a framing rule, its offsets are rejected or its slot reaches past \
+                                          out_bytes; reported alone, whatever the key is */
 
 /* Create a context bound to HIP device `device_id` (>= 0): streams, events and a small scratch area; about 1.5 ms.  The generator's fixed tables are built by the first call
  * that needs them, ONCE per device and process -- (1..2^23)*G for the verifier's 24-bit windows (1 GiB, first verify / verify_non_zk call) and the signer's doubling-free
@@ -76,7 +78,8 @@ void plume_destroy(plume_ctx* ctx);
 /* Last error text of this thread (valid until the next failing call on the thread). */
 const char* plume_last_error(void);
 /* Library / build information: "plume_hip <major.minor> gfx950 build=<hash of the device sources>".  The number in the string stays 0.12 for library 0.13: callers
- * that need the 0.13, 0.14 or 0.15 entry points look for the symbols (dlsym / getattr), as zk-nullifier-sig_amd/capi.py does.  0.15: Keccak Merkle allow-lists
+ * that need the 0.13, 0.14, 0.15 or 0.16 entry points look for the symbols (dlsym / getattr), as zk-nullifier-sig_amd/capi.py does.  0.16: signed raw Ethereum
+ * transactions from unsigned payloads (plume_eth_tx_sign_batch*); 0.15: Keccak Merkle allow-lists
  * (plume_merkle_*); 0.14: the senders of raw Ethereum transactions
  * (plume_eth_tx_parse_batch*, plume_eth_tx_sender_batch*); 0.13: deterministic ECDSA signatures with a recovery id
  * (plume_ecdsa_sign_batch*) and the digest a wallet signs (plume_eth_message_hash_batch*: Keccak-256 of ragged messages, EIP-191); 0.12: public keys and addresses from
@@ -628,6 +631,55 @@ int plume_eth_tx_sender_batch(plume_ctx* ctx, int flags, int pk_format, int addr
                               uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status);
 int plume_eth_tx_sender_batch_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes,
                                      const uint8_t* expect, uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream);
+
+/* ---- signing raw Ethereum transactions: unsigned payload in, wire bytes out  (library 0.16) ------------------------
+ * The producer of what the 0.14 calls parse.  Item i is txs[tx_off[i] .. tx_off[i + 1]), n + 1 offsets as everywhere else: the UNSIGNED serialization wallets pass around,
+ * exactly the bytes whose Keccak-256 the sender signs.  THIS IS A SIGNER OF WELL-FRAMED PAYLOADS, NOT A CONSENSUS ENCODER: the envelope, the outer header and every
+ * top-level header must be canonical and tile the payload exactly, by the rules stated for the parser above; inner fields are skipped by their header and copied verbatim.
+ *   input     legacy, unprotected: one list that covers the item, 6 items (nonce, gasPrice, gasLimit, to, value, data).  Legacy, EIP-155: one list, 9 items, the seventh
+ *             chainId, a canonical integer in 1 .. 2^63 - 18 (the range the parser accepts: v fits 64 bits), the eighth and ninth each exactly the empty string 80; nine
+ *             items with anything else in the last three are invalid (so a signed transaction given as input is).  Typed: first byte 01, 02, 03 or 04, then one list that
+ *             covers the rest, with 8, 9, 11 or 10 items (the signed form's count less three), the first chainId, a canonical integer of at most 8 bytes.
+ *   hash      Keccak-256(item): the whole item, no prefix, no suffix.
+ *   signature exactly plume_ecdsa_sign_batch on that hash: RFC 6979 over the digest, aux (optional, 32 bytes per item) hedges it, always low s, parity 0 / 1, the same
+ *             nonce cap, no retry.
+ *   output    with body = the input from the first top-level item to the end of the last unsigned field (EIP-155: to the start of the chainId item) and list(x) the
+ *             canonical list header of len(x), then x:
+ *                 legacy, unprotected   list(body || rlp_int(27 + parity) || rlp_int(r) || rlp_int(s))
+ *                 legacy, EIP-155       list(body || rlp_int(35 + 2 chainId + parity) || rlp_int(r) || rlp_int(s))
+ *                 typed                 type || list(body || rlp_int(parity) || rlp_int(r) || rlp_int(s))
+ *             integers canonical: no leading zero byte, zero is 80, a value below 0x80 is its own byte.
+ *   slots     nothing depends on lengths that are only known after signing: slot i starts at out + (tx_off[i] - tx_off[0]) + 68 i and is len_i + 68 bytes long;
+ *             out_len[i] (uint32_t) is the signed length and the slot's bytes beyond it are written as zero, so whole buffers compare byte for byte.  out needs
+ *             tx_off[n] - tx_off[0] + 68 n bytes: plume_eth_tx_sign_out_bytes(n, tx_off[n] - tx_off[0]).  Why 68 (PLUME_ETH_TX_SIGN_GROWTH): the payload gains at most
+ *             1 + 33 + 33 bytes; an EIP-155 item trades rlp_int(chainId) 80 80 for rlp_int(v), at most two bytes longer than rlp_int(chainId), never a net gain; a growth
+ *             of at most 67 crosses at most one of the header thresholds 55/56, 255/256, 65535/65536, so the list header gains at most one byte.
+ *   records   (each optional) hash32, r, s: 32 bytes per item; v: the parity, 0 / 1; chain_id: uint64_t (0 for an unprotected legacy item); tx_type: one byte.  They are
+ *             what plume_eth_tx_parse_batch would report for the item written, so a caller need not parse its own output again.
+ *   status    (required) the sign status bits.  0: signed.  PLUME_STATUS_BAD_SCALAR, PLUME_STATUS_IDENTITY, PLUME_STATUS_SELFCHECK_FAILED: as in plume_ecdsa_sign_batch.
+ *             PLUME_STATUS_BAD_TX: the item breaks a rule above; or, in the device form, its offsets decrease or reach past txs_bytes (such an item never reads txs and,
+ *             having no slot, writes no byte of out), or its slot reaches past out_bytes (it then writes no byte of out either).  BAD_TX is reported alone, whatever the
+ *             key is.  One outcome is added to PLUME_STATUS_IDENTITY: chainId 2^63 - 18 signed with parity 1 has v = 2^64, which 64 bits -- and the parser -- do not
+ *             hold; like R.x >= n it is a recovery id without a representation, and there is no retry.  Any non-zero status: an all-zero slot, out_len = 0 and zero in
+ *             every optional record.
+ * Device side: k_eth_tx_sign_frame (framing and hash, into staging the context owns), the unchanged stages of plume_ecdsa_sign_batch on the staged hash --
+ * plume_set_sub_batches, plume_set_sign_uniform, plume_set_sign_selfcheck and the chunk limit apply as they do there --, k_eth_tx_sign_assemble (one lane per item writes
+ * exactly its slot).  The staged signatures are wiped behind it: what was signed for an item that reports a status is never released.  With stage timing on the stages are
+ * "eth_tx_sign_frame", the signer's own, "eth_tx_sign_assemble".  The device form needs a single-device context and n <= the chunk size, waits for and leaves the
+ * workspace event, builds the signer's tables on first use (plus the comb with the self-check on), never the 1 GiB window table, and does not synchronise; with device
+ * offsets that are not non-decreasing the slots of sound items may overlap, and what an overlap holds is unspecified (nothing outside out_bytes is ever written).  The host
+ * form is a serial call like plume_eth_tx_sender_batch: pieces of at most plume_set_chunk items, the shards of a plume_init_multi context, sk and aux wiped from the staging
+ * behind the kernels.  Decreasing offsets anywhere in tx_off[0 .. n] return PLUME_ERR_ARG before anything is staged or written: the offsets of the whole call place every
+ * piece's and every shard's share of out.
+ * Both: flags must be 0 (unknown bits return PLUME_ERR_ARG); n = 0 is a successful no-op; byte arrays may sit at any byte offset; tx_off and chain_id are 8-byte aligned,
+ * out_len 4-byte aligned.  The transaction id is Keccak-256 of the signed item: plume_eth_message_hash_batch over the compacted output gives it. */
+#define PLUME_ETH_TX_SIGN_GROWTH 68
+size_t plume_eth_tx_sign_out_bytes(size_t n, uint64_t txs_bytes);
+int plume_eth_tx_sign_batch(plume_ctx* ctx, int flags, size_t n, const uint8_t* txs, const uint64_t* tx_off, const uint8_t* sk, const uint8_t* aux, uint8_t* out,
+                            uint32_t* out_len, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status);
+int plume_eth_tx_sign_batch_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, const uint8_t* sk, const uint8_t* aux,
+                                   uint8_t* out, size_t out_bytes, uint32_t* out_len, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
+                                   uint8_t* tx_type, uint8_t* status, void* stream);
 
 /* ---- Keccak Merkle allow-lists of addresses  (library 0.15) -------------------------------------------------------
  * An application that gates on a list of accounts usually publishes ONE 32-byte root and lets every claimant bring a proof.  These calls build that tree, hand out proofs

@@ -175,6 +175,14 @@ def _load():
     fn = getattr(lib, "plume_merkle_max_proof_len", None)
     if fn is not None:
         fn.argtypes, fn.restype = [sz], C.c_void_p                                 # (a size_t: ctypes hands back None for 0)
+    # signing raw transactions (library 0.16; Engine.eth_tx_sign_batch* raise PlumeHipError on an older build)
+    for name, args in (("plume_eth_tx_sign_batch", [vp, i, sz] + [vp] * 13), ("plume_eth_tx_sign_batch_device", [vp, i, sz, vp, vp, sz, vp, vp, vp, sz] + [vp] * 9)):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
+    fn = getattr(lib, "plume_eth_tx_sign_out_bytes", None)
+    if fn is not None:
+        fn.argtypes, fn.restype = [sz, C.c_uint64], C.c_void_p                     # (a size_t)
     _lib = lib
     # (the 0.13 entry points are told by their symbols: plume_version() still begins "plume_hip 0.12")
     if (_version(lib) < (0, 12) or getattr(lib, "plume_ecdsa_sign_batch", None) is None) and not os.environ.get("PLUME_HIP_LIB"):
@@ -198,7 +206,8 @@ def exported_symbols():
             "plume_eth_message_hash_batch", "plume_eth_message_hash_batch_device", "plume_ecdsa_sign_batch", "plume_ecdsa_sign_batch_device",
             "plume_eth_tx_parse_batch", "plume_eth_tx_parse_batch_device", "plume_eth_tx_sender_batch", "plume_eth_tx_sender_batch_device",
             "plume_merkle_max_proof_len", "plume_merkle_leaf_batch", "plume_merkle_leaf_batch_device", "plume_merkle_tree_build", "plume_merkle_tree_build_device",
-            "plume_merkle_proof_batch", "plume_merkle_proof_batch_device", "plume_merkle_verify_batch", "plume_merkle_verify_batch_device"]
+            "plume_merkle_proof_batch", "plume_merkle_proof_batch_device", "plume_merkle_verify_batch", "plume_merkle_verify_batch_device",
+            "plume_eth_tx_sign_out_bytes", "plume_eth_tx_sign_batch", "plume_eth_tx_sign_batch_device"]
 
 
 def pack_messages(msgs):
@@ -238,6 +247,9 @@ ETH_HASH_MODES = {"keccak256": 0, "eip191": 1}
 ECDSA_SIGN_V27 = 1
 # plume_eth_tx_parse_batch (include/plume_hip.h): the status of an item (plume_eth_tx_sender_batch reports the recovery's: ECDSA_*)
 ETH_TX_OK, ETH_TX_INVALID = 1, 3
+# plume_eth_tx_sign_batch (include/plume_hip.h): the status bit it adds to the signer's (0, 2, 4, 8) and the bytes a slot has beyond its unsigned item
+STATUS_BAD_TX = 16
+ETH_TX_SIGN_GROWTH = 68
 # plume_merkle_* (include/plume_hip.h): leaf formats -> (PLUME_MERKLE_LEAF_*), the sort flag, the status of an item, the proof length of a refused index
 MERKLE_LEAF_FORMATS = {"hash32": 0, "address": 1, "address_uint256": 2}
 MERKLE_SORT_LEAVES = 1
@@ -647,6 +659,45 @@ class Engine:
                      _ptr(status)), "plume_eth_tx_sender_batch")
         return pk, address, status, chain_id, tx_type
 
+    def _eth_tx_sign_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no transaction signing: {name} came with library 0.16 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    def eth_tx_sign_slots(self, txs, tx_off, sk, aux=None, want=("hash", "r", "s", "v", "chain_id", "tx_type")):
+        """plume_eth_tx_sign_batch as the library writes it: a dict with out (the slots: item i's at (tx_off[i] - tx_off[0]) + 68 i, len_i + 68 bytes, zero beyond
+        out_len[i]), out_len (n uint32), status (n) and the records named in `want`.  txs, tx_off as pack_messages returns them: UNSIGNED transactions."""
+        fn = self._eth_tx_sign_fn("plume_eth_tx_sign_batch")
+        tx_off = np.ascontiguousarray(tx_off, dtype=np.uint64)
+        n = len(tx_off) - 1
+        txs = np.ascontiguousarray(txs, dtype=np.uint8)
+        sk = _np(sk, 32, n, "sk")
+        aux = None if aux is None else _np(aux, 32, n, "aux")
+        nbytes = int(tx_off[n]) - int(tx_off[0]) if n else 0
+        res = {"out": np.zeros(nbytes + ETH_TX_SIGN_GROWTH * n, np.uint8), "out_len": np.zeros(n, np.uint32), "status": np.zeros(n, np.uint8)}
+        rec = {"hash": (n, 32), "r": (n, 32), "s": (n, 32), "v": (n,), "tx_type": (n,)}
+        for k in want:
+            res[k] = np.zeros(n, np.uint64) if k == "chain_id" else np.zeros(rec[k], np.uint8)
+        self._chk(fn(self._ctx, 0, n, _ptr(txs), _ptr(tx_off), _ptr(sk), _ptr(aux), _ptr(res["out"]), _ptr(res["out_len"]),
+                     *(_ptr(res.get(k)) for k in ("hash", "r", "s", "v", "chain_id", "tx_type")), _ptr(res["status"])), "plume_eth_tx_sign_batch")
+        return res
+
+    def eth_tx_sign_batch(self, unsigned, sk, aux=None, records=False):
+        """Signed raw transactions from unsigned payloads (plume_eth_tx_sign_batch): legacy (6 items: unprotected; 9 items ending chainId, 80, 80: EIP-155) and the typed
+        envelopes 01 - 04 without their last three fields.  unsigned: a list of bytes, or (txs, tx_off) as pack_messages returns them; sk: n x 32 big-endian bytes; aux:
+        None, or n x 32 bytes that hedge the RFC 6979 nonce.  Returns (raw, status): raw[i] the signed item as bytes (empty unless status[i] is 0), status[i] 0 (signed),
+        2, 4, 8 as ecdsa_sign_batch reports them, or STATUS_BAD_TX (16: an ill-framed item, whatever the key is).  records=True: a third value, the dict of hash, r, s,
+        v (the parity), chain_id and tx_type of every item -- what eth_tx_parse_batch would say of raw[i]."""
+        txs, tx_off = unsigned if isinstance(unsigned, tuple) else pack_messages([bytes(u) for u in unsigned])
+        res = self.eth_tx_sign_slots(txs, tx_off, sk, aux, want=("hash", "r", "s", "v", "chain_id", "tx_type") if records else ())
+        ob = res["out"].tobytes()
+        base = int(tx_off[0]) if len(tx_off) else 0
+        raw = [ob[int(tx_off[i]) - base + ETH_TX_SIGN_GROWTH * i:][:int(ln)] for i, ln in enumerate(res["out_len"])]
+        if records:
+            return raw, res["status"], {k: res[k] for k in ("hash", "r", "s", "v", "chain_id", "tx_type")}
+        return raw, res["status"]
+
     def _merkle_fn(self, name):
         fn = getattr(self._lib, name, None)
         if fn is None:
@@ -959,6 +1010,17 @@ class Engine:
         d = self._dp
         self._chk(fn(self._ctx, ECDSA_LOW_S if low_s else 0, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(txs), d(tx_off), int(txs_bytes),
                      d(expect), d(pk), d(address), d(chain_id), d(tx_type), d(status), C.c_void_p(st)), "plume_eth_tx_sender_batch_device")
+
+    def eth_tx_sign_batch_device(self, n, txs, tx_off, txs_bytes, sk, aux, out, out_bytes, out_len, status, hash32=None, r=None, s=None, v=None, chain_id=None, tx_type=None,
+                                 stream=None):
+        """the device form of eth_tx_sign_batch on torch tensors (tx_off: n + 1 uint64 offsets; out: the slots, out_bytes of them; out_len: n 4-byte words; chain_id: n
+        8-byte words; the byte arrays at any byte offset; aux and the records may be None); enqueues on `stream` (None = current stream); does not synchronise"""
+        import torch
+        fn = self._eth_tx_sign_fn("plume_eth_tx_sign_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, 0, int(n), d(txs), d(tx_off), int(txs_bytes), d(sk), d(aux), d(out), int(out_bytes), d(out_len), d(hash32), d(r), d(s), d(v), d(chain_id),
+                     d(tx_type), d(status), C.c_void_p(st)), "plume_eth_tx_sign_batch_device")
 
     def merkle_leaf_batch_device(self, n, items, amounts, leaf32, status, leaf_format="address", addr_format="raw20", stream=None):
         """the device form of merkle_leaf_batch on torch tensors; amounts (n x 32 big-endian bytes) and status may be None; one kernel on `stream` (None = current

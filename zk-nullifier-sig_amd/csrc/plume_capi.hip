@@ -31,6 +31,7 @@
 #include "plume_ecdsa.h"
 #include "plume_ecdsa_sign.h"
 #include "plume_eth_tx.h"
+#include "plume_eth_tx_sign.h"
 #include "plume_host_logic.h"
 #include "plume_keccak.h"
 #include "plume_launch.h"
@@ -103,7 +104,8 @@ struct StageTimer {
 
 // staging for one piece of a host-pointer call
 struct HostSlot {
-    DevBuf msgs, off, in[6], out[7];
+    DevBuf msgs, off, in[6], out[8];
+    DevBuf ragged;                                                    // the ragged output of a serial call that has one (HostCall::ragged)
     PinnedBuf relbuf;                                                 // piece-relative message offsets (source of an upload: lives until the slot is reused), page-locked
     uint64_t* rel = nullptr;
     hipEvent_t ready = nullptr, computed = nullptr, drained = nullptr;   // uploads landed / kernels finished / downloads landed
@@ -184,6 +186,7 @@ struct plume_ctx {
     int sign_selfcheck = 0;                                        // plume_set_sign_selfcheck: 1 = every sign call stages its outputs here, verifies them and releases what verifies (sign_device)
     DevBuf scstage;                                                // ... the staging: six records in the 64-byte form, the signer's status and the check's verdict, 322 B / item; wiped after the release
     DevBuf txstage;                                                // plume_eth_tx_sender_batch: what k_eth_tx_parse hands the recover stages -- hash, r, s, v, 97 B / item (public data: not wiped)
+    DevBuf txsign;                                                 // plume_eth_tx_sign_batch: the framing (chain id, packed frame word), the signing hash and what the sign stages make of it -- 114 B / item; r, s, v and status wiped behind the assemble
     DevBuf mrksort;                                                // plume_merkle_tree_build: the sort's records, nine word arrays of npad words, 36 B / padded leaf (public data: not wiped)
     DevBuf nonce;                                                  // the derived-nonce signer: r of the call in flight, 32 B / item, wiped on the call's stream after sign_final
     int eq1_short = 1;                                             // verify calls that give R: equation 1 in its short form (plume_eis.h).  0 = long form always (A/B), 2 = test: every item takes the fallback
@@ -306,7 +309,7 @@ static void destroy_single(plume_ctx* ctx) {
     if (ctx->ws_used && ctx->ws_free) (void)hipEventSynchronize(ctx->ws_free);
     for (hipStream_t q : {ctx->stream, ctx->up, ctx->down, ctx->side, ctx->pre}) if (q) (void)hipStreamSynchronize(q);
     for (DevBuf* b : {&ctx->bases, &ctx->jobflags, &ctx->itemflags, &ctx->tab, &ctx->tabscr, &ctx->res, &ctx->resinf, &ctx->res2, &ctx->res2inf, &ctx->pkaff,
-                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->scstage, &ctx->txstage, &ctx->mrksort, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
+                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->scstage, &ctx->txstage, &ctx->txsign, &ctx->mrksort, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
         b->release();
     for (DevBuf& b : ctx->agg) b.release();
     if (ctx->fixed) {
@@ -318,7 +321,7 @@ static void destroy_single(plume_ctx* ctx) {
         ctx->fixed = nullptr;
     }
     for (HostSlot& sl : ctx->slot) {
-        sl.msgs.release(); sl.off.release(); sl.relbuf.release(); sl.rel = nullptr;
+        sl.msgs.release(); sl.off.release(); sl.ragged.release(); sl.relbuf.release(); sl.rel = nullptr;
         for (DevBuf& b : sl.in) b.release();
         for (DevBuf& b : sl.out) b.release();
         for (hipEvent_t e : {sl.ready, sl.computed, sl.drained}) if (e) (void)hipEventDestroy(e);
@@ -1496,12 +1499,18 @@ struct HostArray {
 struct HostCall {
     const uint8_t* msgs;       // may be null when the offsets give it no bytes
     const uint64_t* msg_off;   // null (serial calls only): the call has no messages and stages none
-    HostArray in[6], out[7];
+    HostArray in[6], out[8];
     bool out_heavy = false, may_use_two_lanes = false;
     const char *off_name = "msg_off", *msgs_name = "message";         // what the argument errors of the message staging call the two
+    // serial calls only: a ragged output tied to the messages.  Item i owns the ragged_growth i + (msg_off[i] - msg_off[0]) .. bytes of it, its message's length plus
+    // ragged_growth of them; a piece's share is contiguous, staged in HostSlot::ragged and downloaded in one copy behind the fixed-stride outputs
+    void* ragged = nullptr;
+    size_t ragged_growth = 0;
+    size_t ragged_at(size_t i) const { return (size_t)(msg_off[i] - msg_off[0]) + ragged_growth * i; }
     // items [lo, ...) of the same call: msg_off keeps the caller's absolute offsets into the same msgs buffer
     HostCall shard(size_t lo) const {
         HostCall c = *this;
+        if (c.ragged) c.ragged = (uint8_t*)c.ragged + ragged_at(lo);
         if (c.msg_off) c.msg_off += lo;
         for (HostArray& a : c.in) if (a.p && !a.whole) a.p = (const uint8_t*)a.p + a.stride * lo;
         for (HostArray& a : c.out) if (a.p && !a.whole) a.p = (const uint8_t*)a.p + a.stride * lo;
@@ -1615,12 +1624,15 @@ static int serial_host_piece(plume_ctx* ctx, const HostCall& call, size_t i0, si
         if (call.msg_off) { if (int rc = stage_msgs(call, sl, i0, cnt, st)) return rc; }
         if (int rc = upload(false)) return rc;
         for (size_t k = 0; k < std::size(call.out); k++) if (call.out[k].p && sl.out[k].ensure(bytes(call.out[k]))) return PLUME_ERR_HIP;
+        const size_t rag_bytes = call.ragged ? call.ragged_at(i0 + cnt) - call.ragged_at(i0) : 0;
+        if (rag_bytes && sl.ragged.ensure(rag_bytes)) return PLUME_ERR_HIP;
         if (int rc = run(sl, cnt, ctx)) return rc;
         for (size_t k = 0; k < std::size(call.in); k++) if (call.in[k].secret && call.in[k].p) HIPCHK(hipMemsetAsync(sl.in[k].p, 0, bytes(call.in[k]), st));
         for (size_t k = 0; k < std::size(call.out); k++) {
             const HostArray& a = call.out[k];
             if (a.p) { if (int rc = copy(at(a), sl.out[k].p, bytes(a), hipMemcpyDeviceToHost)) return rc; }
         }
+        if (rag_bytes) { if (int rc = copy((uint8_t*)call.ragged + call.ragged_at(i0), sl.ragged.p, rag_bytes, hipMemcpyDeviceToHost)) return rc; }
         for (size_t k = 0; k < std::size(call.out); k++) if (call.out[k].secret && call.out[k].p) HIPCHK(hipMemsetAsync(sl.out[k].p, 0, bytes(call.out[k]), st));
         return 0;
     };
@@ -1646,6 +1658,12 @@ static int serial_host_call(plume_ctx* ctx, size_t n, const HostCall& call, Run 
 template <class Run>
 static int serial_host_call_any(plume_ctx* ctx, size_t n, const HostCall& call, Run run) {
     if (n == 0) return 0;
+    // A ragged output is placed by the offsets of the WHOLE call -- where every piece and every shard downloads its share, and how large the caller made the array -- while
+    // stage_msgs only ever sees the offsets of the piece it stages.  One pass over all of them, before anything is staged or written: a decrease anywhere is an argument error
+    if (call.ragged) {
+        for (size_t i = 0; i < n; i++)
+            if (call.msg_off[i + 1] < call.msg_off[i]) return fail(PLUME_ERR_ARG, std::string(call.off_name) + " is not non-decreasing");
+    }
     if (ctx->shards.empty()) return serial_host_call(ctx, n, call, run);
     return for_shards(ctx, n, [&](plume_ctx* sh, size_t lo, size_t hi) -> int { return serial_host_call(sh, hi - lo, call.shard(lo), run); });
 }
@@ -2281,14 +2299,14 @@ static int ecdsa_sign_args_ok(int flags, size_t n, const void* hash, const void*
     return 0;
 }
 static int ecdsa_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v, uint8_t* status,
-                             hipStream_t st, const EcdsaSignLaunch* fn) {
+                             hipStream_t st, const EcdsaSignLaunch* fn, bool continue_timer = false) {
     if (n == 0) return 0;
     if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
     if (int rc = need_sign_tables(ctx)) return rc;
     const bool selfcheck = ctx->sign_selfcheck != 0;
     if (selfcheck) { if (int rc = need_gcomb(ctx)) return rc; }                  // the recover stages' table, built before anything is queued
-    if (int rc = ws_acquire(ctx, st)) return rc;
-    WsHold hold(ctx, st);
+    if (!continue_timer) { if (int rc = ws_acquire(ctx, st)) return rc; }       // continue_timer: the caller (the transaction signer) holds the workspace already and has begun the timeline
+    std::unique_ptr<WsHold> hold(continue_timer ? nullptr : new WsHold(ctx, st));
     const std::vector<size_t> cut = sub_batch_bounds(ctx, n);
     const size_t nsub = cut.size() - 1;
     const size_t T = selfcheck ? 2 : 1;                                         // points per item
@@ -2304,7 +2322,7 @@ static int ecdsa_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t*
         ~StageWipe() { if (bytes) (void)hipMemsetAsync(ctx->scstage.p, 0, bytes, st); }
     } stage_wipe{ctx, selfcheck ? kEcdsaStageBytes * n : 0, st};
     StageTimer& t = ctx->timer;
-    t.begin(st);
+    if (!continue_timer) t.begin(st);
     for (size_t k = 0; k < nsub; k++) {
         const size_t lo = cut[k], cnt = cut[k + 1] - cut[k];
         EcdsaSignArgs a;                                                        // the slice [lo, lo + cnt) as a batch of its own
@@ -2336,7 +2354,7 @@ static int ecdsa_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t*
         HIPCHK(hipMemsetAsync(ctx->scstage.p, 0, kEcdsaStageBytes * n, st));        // a withheld s is precisely the value that must not linger
         stage_wipe.bytes = 0;
     }
-    return hold.release();
+    return hold ? hold->release() : 0;
 }
 int plume::capi_ecdsa_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v,
                                   uint8_t* status, void* stream, const EcdsaSignLaunch* fn) {
@@ -2357,6 +2375,75 @@ int plume::capi_ecdsa_sign(plume_ctx* ctx, int flags, size_t n, const uint8_t* h
     return host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
         return ecdsa_sign_device(on, flags, cnt, sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(), aux ? sl.in[2].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(),
                                  sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(), sl.out[3].as<uint8_t>(), on->stream, fn);
+    });
+}
+// The transaction signer (plume_capi_internal.h): the ABI and the launchers live in plume_eth_tx_sign_capi.hip.  k_eth_tx_sign_frame stages the framing and the signing
+// hash in ctx->txsign, the ECDSA signer's stages (ecdsa_sign_device, on this workspace and this stream, self-check included) sign the staged hash into the same staging,
+// k_eth_tx_sign_assemble writes the caller's slots and records; the staged r, s, v and status are wiped behind it (an item the framing rejected was signed over the zero hash: that
+// signature is never released).  The call holds the workspace from in front of the frame to behind the wipe.
+static int eth_tx_sign_args_ok(int flags, size_t n, const void* off, const void* sk, const void* out, const void* out_len, const void* status, const EthTxSignLaunch* fn) {
+    if (flags) return fail(PLUME_ERR_ARG, "unknown flag bits");
+    if (!fn || !fn->frame || !fn->assemble || !fn->sign) return fail(PLUME_ERR_ARG, "the transaction signing kernels are not part of this build");
+    if (n && (!off || !sk || !out || !out_len || !status)) return fail(PLUME_ERR_ARG, "null array");
+    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
+    const uint8_t one = 0;                                                      // (hash, r, s, v are the staging's: any non-null pointer passes the signer's own check)
+    return ecdsa_sign_args_ok(0, n, &one, sk ? sk : &one, &one, &one, &one, &one, fn->sign);
+}
+static int eth_tx_sign_device(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, const uint8_t* sk, const uint8_t* aux, uint8_t* out,
+                              size_t out_bytes, uint32_t* out_len, uint8_t* hash, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status,
+                              hipStream_t st, const EthTxSignLaunch* fn) {
+    if (n == 0) return 0;
+    if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
+    if (!txs && txs_bytes) return fail(PLUME_ERR_ARG, "null transaction buffer");
+    if (int rc = need_sign_tables(ctx)) return rc;                              // the signer's tables, built before anything is queued
+    if (ctx->sign_selfcheck) { if (int rc = need_gcomb(ctx)) return rc; }
+    if (int rc = ws_acquire(ctx, st)) return rc;
+    WsHold hold(ctx, st);
+    if (ctx->txsign.ensure((size_t)PLUME_ETHTXK_SIGN_STAGE * n)) return PLUME_ERR_HIP;
+    uint8_t* const stg = ctx->txsign.as<uint8_t>();
+    uint8_t *const g_hash = stg + 16 * n, *const g_r = stg + 48 * n, *const g_s = stg + 80 * n, *const g_v = stg + 112 * n, *const g_status = stg + 113 * n;
+    struct StageWipe {                                                          // failure paths only: whatever fails behind the sign stages, the staged signatures do not linger (queued in front of ws_free: ~WsHold runs later)
+        uint8_t* p; size_t bytes; hipStream_t st;
+        ~StageWipe() { if (bytes) (void)hipMemsetAsync(p, 0, bytes, st); }
+    } stage_wipe{g_r, 66 * n, st};
+    EthTxSignArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = (uint32_t)n; a.txs = txs; a.tx_off = tx_off; a.txs_bytes = txs ? txs_bytes : 0;
+    a.st_chain = (uint64_t*)stg; a.st_frame = (uint64_t*)(stg + 8 * n); a.st_hash = g_hash; a.st_r = g_r; a.st_s = g_s; a.st_v = g_v; a.st_status = g_status;
+    a.out = out; a.out_bytes = out_bytes; a.out_len = out_len; a.hash = hash; a.r = r; a.s = s; a.v = v; a.chain_id = chain_id; a.tx_type = tx_type; a.status = status;
+    ctx->timer.begin(st);
+    fn->frame(a, st); ctx->timer.stage("eth_tx_sign_frame", st);
+    HIPCHK(hipGetLastError());
+    if (int rc = ecdsa_sign_device(ctx, 0, n, g_hash, sk, aux, g_r, g_s, g_v, g_status, st, fn->sign, true)) return rc;
+    fn->assemble(a, st); ctx->timer.stage("eth_tx_sign_assemble", st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(g_r, 0, 66 * n, st));                                  // r, s, v, status: contiguous in the staging
+    stage_wipe.bytes = 0;
+    return hold.release();
+}
+int plume::capi_eth_tx_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, const uint8_t* sk, const uint8_t* aux,
+                                   uint8_t* out, size_t out_bytes, uint32_t* out_len, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
+                                   uint8_t* tx_type, uint8_t* status, void* stream, const EthTxSignLaunch* fn) {
+    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = eth_tx_sign_args_ok(flags, n, tx_off, sk, out, out_len, status, fn)) return rc;
+    return eth_tx_sign_device(ctx, n, txs, tx_off, txs_bytes, sk, aux, out, out_bytes, out_len, hash32, r, s, v, chain_id, tx_type, status, st_, fn);
+}
+// the host-pointer form: a serial call with the transactions as its messages, sk and aux staged as secrets, and `out` as the call's ragged output
+int plume::capi_eth_tx_sign(plume_ctx* ctx, int flags, size_t n, const uint8_t* txs, const uint64_t* tx_off, const uint8_t* sk, const uint8_t* aux, uint8_t* out,
+                            uint32_t* out_len, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status,
+                            const EthTxSignLaunch* fn) {
+    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
+    if (int rc = eth_tx_sign_args_ok(flags, n, tx_off, sk, out, out_len, status, fn)) return rc;
+    HostCall call = eth_tx_call({txs, tx_off, {{sk, 32, true}, {aux, 32, true}},
+                                 {{out_len, 4}, {status, 1}, {hash32, 32}, {r, 32}, {s, 32}, {v, 1}, {chain_id, 8}, {tx_type, 1}}});
+    call.ragged = out; call.ragged_growth = PLUME_ETHTXK_SIGN_GROWTH;
+    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
+        const size_t out_bytes = (size_t)sl.rel[cnt] + (size_t)PLUME_ETHTXK_SIGN_GROWTH * cnt;
+        return eth_tx_sign_device(on, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), aux ? sl.in[1].as<uint8_t>() : nullptr,
+                                  sl.ragged.as<uint8_t>(), out_bytes, sl.out[0].as<uint32_t>(), hash32 ? sl.out[2].as<uint8_t>() : nullptr,
+                                  r ? sl.out[3].as<uint8_t>() : nullptr, s ? sl.out[4].as<uint8_t>() : nullptr, v ? sl.out[5].as<uint8_t>() : nullptr,
+                                  chain_id ? sl.out[6].as<uint64_t>() : nullptr, tx_type ? sl.out[7].as<uint8_t>() : nullptr, sl.out[1].as<uint8_t>(), on->stream, fn);
     });
 }
 // The STRUCTURE half of SecretKey::from_sec1_der for the fixed 109-byte form above (what the wasm layer emits): ok[i] = 1 iff the record has that exact shape and

@@ -1,4 +1,4 @@
-// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_eth_hash_capi.hip, plume_ecdsa_capi.hip, plume_ecdsa_sign_capi.hip, plume_eth_tx_capi.hip, plume_merkle_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
+// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_eth_hash_capi.hip, plume_ecdsa_capi.hip, plume_ecdsa_sign_capi.hip, plume_eth_tx_capi.hip, plume_eth_tx_sign_capi.hip, plume_merkle_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -160,5 +160,23 @@ __attribute__((visibility("hidden"))) int capi_ecdsa_sign(plume_ctx* ctx, int fl
                                                           uint8_t* s, uint8_t* v, uint8_t* status, const EcdsaSignLaunch* fn);
 __attribute__((visibility("hidden"))) int capi_ecdsa_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux,
                                                                  uint8_t* r, uint8_t* s, uint8_t* v, uint8_t* status, void* stream, const EcdsaSignLaunch* fn);
+
+// The transaction signer (plume_eth_tx_sign_batch*): k_eth_tx_sign_frame into staging the context owns (the framing, the signing hash), the ECDSA signer's stages above on the
+// staged hash -- tables, workspace, sub-batches, the uniform level, the self-check and the chunk limit are theirs --, k_eth_tx_sign_assemble into the caller's slots.  The two
+// launchers come in as hooks, the signer's as its own hook struct.  The host-pointer form is a serial call (serial_host_call_any): the transactions staged as messages, sk and
+// aux as secrets, `out` as the call's ragged output -- one contiguous download per piece.
+struct EthTxSignArgs;
+struct EthTxSignLaunch {
+    void (*frame)(const EthTxSignArgs& a, hipStream_t st);
+    void (*assemble)(const EthTxSignArgs& a, hipStream_t st);
+    const EcdsaSignLaunch* sign;
+};
+__attribute__((visibility("hidden"))) int capi_eth_tx_sign(plume_ctx* ctx, int flags, size_t n, const uint8_t* txs, const uint64_t* tx_off, const uint8_t* sk, const uint8_t* aux,
+                                                           uint8_t* out, uint32_t* out_len, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
+                                                           uint8_t* tx_type, uint8_t* status, const EthTxSignLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_eth_tx_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes,
+                                                                  const uint8_t* sk, const uint8_t* aux, uint8_t* out, size_t out_bytes, uint32_t* out_len, uint8_t* hash32,
+                                                                  uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream,
+                                                                  const EthTxSignLaunch* fn);
 
 }  // namespace plume

@@ -21,7 +21,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .capi import ECDSA_INVALID, ETH_INVALID, ETH_MATCH, ETH_TX_OK, MERKLE_MATCH, RECOVER_INVALID, RECOVER_MATCH, Engine, default_engine, pack_messages
+from .capi import ECDSA_INVALID, ETH_INVALID, ETH_MATCH, ETH_TX_OK, MERKLE_MATCH, RECOVER_INVALID, RECOVER_MATCH, STATUS_BAD_TX, Engine, default_engine, pack_messages
 
 DST = b"QUUX-V01-CS02-with-secp256k1_XMD:SHA-256_SSWU_RO_"  # rust-k256/src/lib.rs:61
 _P = 2**256 - 2**32 - 977
@@ -391,6 +391,25 @@ def tx_signing_hash(raw: bytes, engine: Optional[Engine] = None) -> bytes:
     if int(out["status"][0]) != ETH_TX_OK:
         raise SignatureError("tx_signing_hash: not a signed transaction of a known kind")
     return out["hash"][0].tobytes()
+
+
+def sign_tx(sk, unsigned: bytes, aux: Optional[bytes] = None, engine: Optional[Engine] = None) -> bytes:
+    """The signed raw transaction of one UNSIGNED serialization -- exactly the bytes whose Keccak-256 the sender signs --, framed, hashed, signed and assembled on the GPU
+    (include/plume_hip.h, plume_eth_tx_sign_batch): legacy with 6 items (unprotected) or 9 (EIP-155: chainId, then two empty strings), or a typed envelope 01 - 04 without
+    its last three fields.  The signature is ecdsa_sign's over that hash, hedged with the 32 bytes of aux when given.  sk: a SecretKey or 32 big-endian bytes.  Raises
+    SignatureError for an item that is no such payload, for an sk outside [1, n - 1] and for a degenerate outcome, PlumeSelfCheckError when the self-check withheld the
+    signature.  tx_sender(sign_tx(sk, u)) is the key's address."""
+    sk32 = _b32("sign_tx", "sk", sk.to_bytes() if isinstance(sk, SecretKey) else sk)
+    a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
+    raw, status = (engine or default_engine()).eth_tx_sign_batch([bytes(unsigned)], a(sk32), None if aux is None else a(_b32("sign_tx", "aux", aux)))
+    st = int(status[0])
+    if st & STATUS_BAD_TX:
+        raise SignatureError("sign_tx: not an unsigned transaction of a known kind")
+    if st & 8:
+        raise PlumeSelfCheckError("sign_tx: the signature did not recover the signer's key and was withheld")
+    if st:
+        raise SignatureError(f"sign_tx: no signature (status {st}: {'sk outside [1, n - 1]' if st == 2 else 'a degenerate outcome'})")
+    return raw[0]
 
 
 def _tx_sender(what: str, want, raw: bytes, engine: Optional[Engine], low_s: bool):
