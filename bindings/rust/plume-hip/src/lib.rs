@@ -73,6 +73,9 @@ pub const PLUME_STATUS_BAD_SCALAR: u8 = 2;
 pub const PLUME_STATUS_IDENTITY: u8 = 4;
 pub const PLUME_STATUS_SELFCHECK_FAILED: u8 = 8;
 pub const PLUME_STATUS_BAD_TX: u8 = 16;
+pub const PLUME_STATUS_HD_NO_KEY: u8 = 32;
+pub const PLUME_STATUS_HD_HARDENED: u8 = 64;
+pub const PLUME_HD_MAX_DEPTH: usize = 8;
 pub const PLUME_RECOVER_MISMATCH: u8 = 0;
 pub const PLUME_RECOVER_MATCH: u8 = 1;
 pub const PLUME_RECOVER_INVALID: u8 = 3;
@@ -203,6 +206,16 @@ extern "C" {
     fn plume_eth_tx_sign_batch_device(ctx: *mut plume_ctx, flags: c_int, n: usize, txs: *const u8, tx_off: *const u64, txs_bytes: usize, sk: *const u8, aux: *const u8,
         out: *mut u8, out_bytes: usize, out_len: *mut u32, hash32: *mut u8, r: *mut u8, s: *mut u8, v: *mut u8, chain_id: *mut u64, tx_type: *mut u8, status: *mut u8,
         stream: *mut c_void) -> c_int;
+    fn plume_hd_master_batch(ctx: *mut plume_ctx, n: usize, seed: *const u8, seed_len: usize, sk32: *mut u8, chain32: *mut u8, status: *mut u8) -> c_int;
+    fn plume_hd_master_batch_device(ctx: *mut plume_ctx, n: usize, seed: *const u8, seed_len: usize, sk32: *mut u8, chain32: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_hd_derive_priv_batch(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, parent_sk32: *const u8, parent_chain32: *const u8,
+        path: *const u32, depth: usize, child_sk32: *mut u8, child_chain32: *mut u8, child_pk: *mut u8, address: *mut u8, status: *mut u8) -> c_int;
+    fn plume_hd_derive_priv_batch_device(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, parent_sk32: *const u8, parent_chain32: *const u8,
+        path: *const u32, depth: usize, child_sk32: *mut u8, child_chain32: *mut u8, child_pk: *mut u8, address: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_hd_derive_pub_batch(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, parent_pk: *const u8, parent_chain32: *const u8,
+        path: *const u32, depth: usize, child_pk: *mut u8, child_chain32: *mut u8, address: *mut u8, status: *mut u8) -> c_int;
+    fn plume_hd_derive_pub_batch_device(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, parent_pk: *const u8, parent_chain32: *const u8,
+        path: *const u32, depth: usize, child_pk: *mut u8, child_chain32: *mut u8, address: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -219,6 +232,88 @@ fn put_point(dst: &mut [u8], p: &AffinePoint) {
     let e = p.to_encoded_point(false);               // 04 || x || y, or 00 for the identity
     if let (Some(x), Some(y)) = (e.x(), e.y()) { dst[..32].copy_from_slice(x); dst[32..64].copy_from_slice(y); }
     // identity: the 64 bytes stay zero
+}
+fn hd_status(what: &str, st: u8) -> Result<(), HipError> {
+    if st == PLUME_STATUS_HD_HARDENED { return Err(HipError(format!("{what}: a public key has no hardened children"))); }
+    if st == PLUME_STATUS_HD_NO_KEY { return Err(HipError(format!("{what}: the path has no key"))); }
+    if st != 0 { return Err(HipError(format!("{what}: the parent key is not valid (status {st})"))); }
+    Ok(())
+}
+/// The indices of a BIP-32 path, "m/44'/60'/0'/0/3" or, relative to a node, "0/3": decimal components below 2^31, a trailing `'` or `h` adds 2^31 (hardened);
+/// 1 .. `PLUME_HD_MAX_DEPTH` of them.  An error for "m", "m/", an empty component, anything that is no index, too many components.
+pub fn parse_path(path: &str) -> Result<Vec<u32>, HipError> {
+    let bad = || HipError(format!("parse_path: {path:?} is not a path of 1 .. {PLUME_HD_MAX_DEPTH} indices below 2^31"));
+    let rest = if path == "m" { return Err(bad()); } else { path.strip_prefix("m/").unwrap_or(path) };
+    let mut out = Vec::new();
+    for c in rest.split('/') {
+        let (num, hard) = match c.strip_suffix('\'').or_else(|| c.strip_suffix('h')) { Some(n) => (n, true), None => (c, false) };
+        if num.is_empty() || num.len() > 10 || !num.bytes().all(|b| b.is_ascii_digit()) { return Err(bad()); }
+        let v: u64 = num.parse().map_err(|_| bad())?;
+        if v >= 1 << 31 || out.len() == PLUME_HD_MAX_DEPTH { return Err(bad()); }
+        out.push(v as u32 + if hard { 1 << 31 } else { 0 });
+    }
+    Ok(out)
+}
+/// What an extended key string holds: `key` is `00 || sk` for an xprv, the 33 SEC1 bytes of `pk` for an xpub.
+pub struct ExtendedKey { pub depth: u8, pub child_number: u32, pub chain: [u8; 32], pub key: [u8; 33] }
+fn xkey_sha256(msg: &[u8]) -> [u8; 32] {          // host-side, for the four checksum bytes only
+    const K: [u32; 64] = [
+        0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74,
+        0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d,
+        0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e,
+        0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5,
+        0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2];
+    let mut h: [u32; 8] = [0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19];
+    let mut m = msg.to_vec();
+    m.push(0x80);
+    while m.len() % 64 != 56 { m.push(0); }
+    m.extend_from_slice(&((msg.len() as u64) * 8).to_be_bytes());
+    for blk in m.chunks(64) {
+        let mut w = [0u32; 64];
+        for i in 0..16 { w[i] = u32::from_be_bytes([blk[4 * i], blk[4 * i + 1], blk[4 * i + 2], blk[4 * i + 3]]); }
+        for i in 16..64 {
+            let (a, b) = (w[i - 15], w[i - 2]);
+            w[i] = w[i - 16].wrapping_add(a.rotate_right(7) ^ a.rotate_right(18) ^ (a >> 3)).wrapping_add(w[i - 7]).wrapping_add(b.rotate_right(17) ^ b.rotate_right(19) ^ (b >> 10));
+        }
+        let mut v = h;
+        for i in 0..64 {
+            let t1 = v[7].wrapping_add(v[4].rotate_right(6) ^ v[4].rotate_right(11) ^ v[4].rotate_right(25)).wrapping_add((v[4] & v[5]) ^ (!v[4] & v[6])).wrapping_add(K[i]).wrapping_add(w[i]);
+            let t2 = (v[0].rotate_right(2) ^ v[0].rotate_right(13) ^ v[0].rotate_right(22)).wrapping_add((v[0] & v[1]) ^ (v[0] & v[2]) ^ (v[1] & v[2]));
+            v = [t1.wrapping_add(t2), v[0], v[1], v[2], v[3].wrapping_add(t1), v[4], v[5], v[6]];
+        }
+        for i in 0..8 { h[i] = h[i].wrapping_add(v[i]); }
+    }
+    let mut out = [0u8; 32];
+    for i in 0..8 { out[4 * i..4 * i + 4].copy_from_slice(&h[i].to_be_bytes()); }
+    out
+}
+fn parse_xkey(s: &str, version: [u8; 4]) -> Result<ExtendedKey, HipError> {
+    const DIGITS: &[u8] = b"123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz";
+    let bad = |why: &str| HipError(format!("extended key: {why}"));
+    let mut raw = [0u8; 82];
+    for ch in s.bytes() {
+        let mut carry = DIGITS.iter().position(|d| *d == ch).ok_or_else(|| bad("not a base58 digit"))? as u32;
+        for b in raw.iter_mut().rev() { carry += 58 * *b as u32; *b = carry as u8; carry >>= 8; }
+        if carry != 0 { return Err(bad("longer than 82 bytes")); }
+    }
+    if xkey_sha256(&xkey_sha256(&raw[..78]))[..4] != raw[78..] { return Err(bad("checksum")); }
+    if raw[..4] != version { return Err(bad("version bytes")); }
+    let (mut chain, mut key) = ([0u8; 32], [0u8; 33]);
+    chain.copy_from_slice(&raw[13..45]);
+    key.copy_from_slice(&raw[45..78]);
+    Ok(ExtendedKey { depth: raw[4], child_number: u32::from_be_bytes([raw[9], raw[10], raw[11], raw[12]]), chain, key })
+}
+/// A mainnet "xprv..." string, base58check DECODE only: `hd_derive(&key[1..], &chain, path)` takes it from there.
+pub fn parse_xprv(s: &str) -> Result<ExtendedKey, HipError> {
+    let k = parse_xkey(s, [0x04, 0x88, 0xAD, 0xE4])?;
+    if k.key[0] != 0 { return Err(HipError("parse_xprv: the key is not 00 || 32 bytes".to_string())); }
+    Ok(k)
+}
+/// A mainnet "xpub..." string, base58check DECODE only.
+pub fn parse_xpub(s: &str) -> Result<ExtendedKey, HipError> {
+    let k = parse_xkey(s, [0x04, 0x88, 0xB2, 0x1E])?;
+    if k.key[0] != 2 && k.key[0] != 3 { return Err(HipError("parse_xpub: the key is not a compressed point".to_string())); }
+    Ok(k)
 }
 fn get_point(src: &[u8]) -> AffinePoint {
     if src[..64].iter().all(|b| *b == 0) { return AffinePoint::IDENTITY; }
@@ -403,6 +498,59 @@ impl HipEngine {
         if status[0] != 0 { return Err(HipError(format!("sign_tx: no signature (status {})", status[0]))); }
         out.truncate(out_len[0] as usize);
         Ok(out)
+    }
+    /// The BIP-32 master node `(sk, chain)` of a seed of 16 .. 64 bytes (`plume_hd_master_batch`): HMAC-SHA512("Bitcoin seed", seed), on the GPU.
+    pub fn hd_master(&self, seed: &[u8]) -> Result<([u8; 32], [u8; 32]), HipError> {
+        let (mut sk, mut chain, mut status) = ([0u8; 32], [0u8; 32], [0u8; 1]);
+        let rc = unsafe { plume_hd_master_batch(self.0, 1, seed.as_ptr(), seed.len(), sk.as_mut_ptr(), chain.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        hd_status("hd_master", status[0])?;
+        Ok((sk, chain))
+    }
+    /// The node `(sk, chain)` at `path` ("m/44'/60'/0'/0/3") below the node `(sk, chain)`: BIP-32's CKDpriv on the GPU (`plume_hd_derive_priv_batch`).
+    pub fn hd_derive(&self, sk: &[u8; 32], chain: &[u8; 32], path: &str) -> Result<([u8; 32], [u8; 32]), HipError> {
+        let idx = parse_path(path)?;
+        let (mut csk, mut cchain, mut status) = ([0u8; 32], [0u8; 32], [0u8; 1]);
+        let null = std::ptr::null_mut::<u8>();
+        let rc = unsafe { plume_hd_derive_priv_batch(self.0, 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, sk.as_ptr(), chain.as_ptr(), idx.as_ptr(), idx.len(), csk.as_mut_ptr(),
+                                                     cchain.as_mut_ptr(), null, null, status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        hd_status("hd_derive", status[0])?;
+        Ok((csk, cchain))
+    }
+    /// The public node `(pk, chain)` at the non-hardened `path` ("0/3") below the public node `(pk, chain)`: BIP-32's CKDpub on the GPU (`plume_hd_derive_pub_batch`).
+    pub fn hd_derive_pub(&self, pk: &AffinePoint, chain: &[u8; 32], path: &str) -> Result<(AffinePoint, [u8; 32]), HipError> {
+        let idx = parse_path(path)?;
+        let (mut par, mut cpk, mut cchain, mut status) = ([0u8; 64], [0u8; 64], [0u8; 32], [0u8; 1]);
+        put_point(&mut par, pk);
+        let rc = unsafe { plume_hd_derive_pub_batch(self.0, 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, par.as_ptr(), chain.as_ptr(), idx.as_ptr(), idx.len(), cpk.as_mut_ptr(),
+                                                    cchain.as_mut_ptr(), std::ptr::null_mut(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        hd_status("hd_derive_pub", status[0])?;
+        Ok((get_point(&cpk), cchain))
+    }
+    /// The 20-byte Ethereum address of the key at `path` below a private node.
+    pub fn hd_address(&self, sk: &[u8; 32], chain: &[u8; 32], path: &str) -> Result<[u8; 20], HipError> {
+        let idx = parse_path(path)?;
+        let (mut csk, mut addr, mut status) = ([0u8; 32], [0u8; 20], [0u8; 1]);
+        let null = std::ptr::null_mut::<u8>();
+        let rc = unsafe { plume_hd_derive_priv_batch(self.0, 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, sk.as_ptr(), chain.as_ptr(), idx.as_ptr(), idx.len(), csk.as_mut_ptr(),
+                                                     null, null, addr.as_mut_ptr(), status.as_mut_ptr()) };
+        csk.iter_mut().for_each(|b| *b = 0);
+        if rc != 0 { return Err(last_error()); }
+        hd_status("hd_address", status[0])?;
+        Ok(addr)
+    }
+    /// The 20-byte Ethereum address of the key at the non-hardened `path` below a public node: what a watcher holding an xpub derives.
+    pub fn hd_address_pub(&self, pk: &AffinePoint, chain: &[u8; 32], path: &str) -> Result<[u8; 20], HipError> {
+        let idx = parse_path(path)?;
+        let (mut par, mut cpk, mut addr, mut status) = ([0u8; 64], [0u8; 64], [0u8; 20], [0u8; 1]);
+        put_point(&mut par, pk);
+        let rc = unsafe { plume_hd_derive_pub_batch(self.0, 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, par.as_ptr(), chain.as_ptr(), idx.as_ptr(), idx.len(), cpk.as_mut_ptr(),
+                                                    std::ptr::null_mut(), addr.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        hd_status("hd_address_pub", status[0])?;
+        Ok(addr)
     }
     /// The public key and the address of the sender of one raw signed transaction (`plume_eth_tx_sender_batch`), with the EIP-2 low-`s` rule.  An error when there is no
     /// sender: the framing is broken or the signature recovers no key.

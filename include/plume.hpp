@@ -27,6 +27,7 @@
 // A single sign / verify is a batch of one (a kernel launch per call: use the batch twins for throughput).
 #ifndef PLUME_HPP
 #define PLUME_HPP
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstdlib>
@@ -440,6 +441,149 @@ inline std::vector<uint8_t> sign_tx(const SecretKey& sk, const uint8_t* unsigned
     if (st) throw SignatureError();
     out.resize(out_len);
     return out;
+}
+// ---- BIP-32 (plume_hip.h, library 0.17): the single-item forms.  A node is (key, chain code); every derivation runs on the GPU.
+struct HdNode { SecretKey sk; Bytes32 chain; };
+struct HdPubNode { AffinePoint pk; Bytes32 chain; };
+// The indices of "m/44'/60'/0'/0/3" or, relative to a node, "0/3": decimal components below 2^31, a trailing ' or h adds 2^31 (hardened); 1 .. PLUME_HD_MAX_DEPTH of them.
+// std::invalid_argument for "m", "m/", an empty component, anything else that is no index, too many components.
+inline std::vector<uint32_t> parse_path(const std::string& path) {
+    std::vector<uint32_t> out;
+    size_t pos = 0;
+    if (path == "m" || path.empty()) throw std::invalid_argument("parse_path: no component");
+    if (path.compare(0, 2, "m/") == 0) pos = 2;
+    for (;;) {
+        const size_t end = std::min(path.find('/', pos), path.size());
+        std::string c = path.substr(pos, end - pos);
+        const bool hard = !c.empty() && (c.back() == '\'' || c.back() == 'h');
+        if (hard) c.pop_back();
+        if (c.empty() || c.size() > 10 || c.find_first_not_of("0123456789") != std::string::npos) throw std::invalid_argument("parse_path: bad component");
+        const unsigned long long v = std::stoull(c);
+        if (v >= 0x80000000ull) throw std::invalid_argument("parse_path: index not below 2^31");
+        out.push_back((uint32_t)v + (hard ? 0x80000000u : 0u));
+        if (out.size() > PLUME_HD_MAX_DEPTH) throw std::invalid_argument("parse_path: too deep");
+        if (end == path.size()) break;
+        pos = end + 1;
+    }
+    return out;
+}
+inline void hd_check_status(uint8_t st) {
+    if (st) throw SignatureError();      // 2: an invalid parent; PLUME_STATUS_HD_NO_KEY: the path has no key; PLUME_STATUS_HD_HARDENED: a public key has no hardened children
+}
+// HMAC-SHA512("Bitcoin seed", seed), 16 <= len <= 64
+inline HdNode hd_master(const uint8_t* seed, size_t len, Engine& eng = Engine::shared()) {
+    Bytes32 sk{}, chain{};
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_hd_master_batch(eng.ctx(), 1, seed, len, sk.data(), chain.data(), &st), "plume_hd_master_batch");
+    hd_check_status(st);
+    return {*SecretKey::from_bytes(sk), chain};
+}
+inline HdNode hd_derive(const SecretKey& sk, const Bytes32& chain, const std::string& path, Engine& eng = Engine::shared()) {
+    const std::vector<uint32_t> idx = parse_path(path);
+    Bytes32 csk{}, cchain{};
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_hd_derive_priv_batch(eng.ctx(), 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, sk.to_bytes().data(), chain.data(), idx.data(), idx.size(), csk.data(),
+                                                cchain.data(), nullptr, nullptr, &st),
+                     "plume_hd_derive_priv_batch");
+    hd_check_status(st);
+    return {*SecretKey::from_bytes(csk), cchain};
+}
+// non-hardened indices only ("0/3"): what a watcher holding an xpub derives
+inline HdPubNode hd_derive_pub(const AffinePoint& pk, const Bytes32& chain, const std::string& path, Engine& eng = Engine::shared()) {
+    const std::vector<uint32_t> idx = parse_path(path);
+    uint8_t cpk[64], st = 0xFF;
+    Bytes32 cchain{};
+    plume_hip::check(plume_hd_derive_pub_batch(eng.ctx(), 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, pk.xy.data(), chain.data(), idx.data(), idx.size(), cpk, cchain.data(),
+                                               nullptr, &st),
+                     "plume_hd_derive_pub_batch");
+    hd_check_status(st);
+    return {AffinePoint::from_bytes64(cpk), cchain};
+}
+// the 20-byte Ethereum address of the key at `path` below a private node, or (non-hardened path) below a public one
+inline std::array<uint8_t, 20> hd_address(const SecretKey& sk, const Bytes32& chain, const std::string& path, Engine& eng = Engine::shared()) {
+    const std::vector<uint32_t> idx = parse_path(path);
+    Bytes32 csk{};
+    std::array<uint8_t, 20> addr{};
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_hd_derive_priv_batch(eng.ctx(), 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, sk.to_bytes().data(), chain.data(), idx.data(), idx.size(), csk.data(),
+                                                nullptr, nullptr, addr.data(), &st),
+                     "plume_hd_derive_priv_batch");
+    csk.fill(0);
+    hd_check_status(st);
+    return addr;
+}
+inline std::array<uint8_t, 20> hd_address(const AffinePoint& pk, const Bytes32& chain, const std::string& path, Engine& eng = Engine::shared()) {
+    const std::vector<uint32_t> idx = parse_path(path);
+    uint8_t cpk[64], st = 0xFF;
+    std::array<uint8_t, 20> addr{};
+    plume_hip::check(plume_hd_derive_pub_batch(eng.ctx(), 0, PLUME_ETH_PK_AFFINE64, PLUME_ETH_ADDR_RAW20, 1, pk.xy.data(), chain.data(), idx.data(), idx.size(), cpk, nullptr,
+                                               addr.data(), &st),
+                     "plume_hd_derive_pub_batch");
+    hd_check_status(st);
+    return addr;
+}
+// An extended key "xprv..." / "xpub..." (mainnet), base58check DECODE only: depth, child number, chain code and the key -- 32 bytes of sk in key[1 .. 33) behind a zero
+// byte, or the 33 SEC1 bytes of pk.  std::invalid_argument for a bad digit, length, checksum or version.
+struct ExtendedKey { uint8_t depth; uint32_t child_number; Bytes32 chain; std::array<uint8_t, 33> key; };
+namespace hd_detail {
+inline void sha256(const uint8_t* msg, size_t len, uint8_t out[32]) {          // host-side, for the four checksum bytes only
+    static const uint32_t K[64] = {
+        0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74,
+        0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d,
+        0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e,
+        0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5,
+        0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+    uint32_t h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+    std::vector<uint8_t> m(msg, msg + len);
+    m.push_back(0x80);
+    while (m.size() % 64 != 56) m.push_back(0);
+    for (int b = 7; b >= 0; b--) m.push_back((uint8_t)(((uint64_t)len * 8) >> (8 * b)));
+    auto rotr = [](uint32_t x, int n) { return (x >> n) | (x << (32 - n)); };
+    for (size_t blk = 0; blk < m.size(); blk += 64) {
+        uint32_t w[64];
+        for (int i = 0; i < 16; i++) w[i] = ((uint32_t)m[blk + 4 * i] << 24) | ((uint32_t)m[blk + 4 * i + 1] << 16) | ((uint32_t)m[blk + 4 * i + 2] << 8) | m[blk + 4 * i + 3];
+        for (int i = 16; i < 64; i++) w[i] = w[i - 16] + (rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3)) + w[i - 7] + (rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10));
+        uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
+        for (int i = 0; i < 64; i++) {
+            const uint32_t t1 = hh + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + K[i] + w[i];
+            const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
+            hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+        }
+        h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+    }
+    for (int i = 0; i < 8; i++) for (int b = 0; b < 4; b++) out[4 * i + b] = (uint8_t)(h[i] >> (24 - 8 * b));
+}
+inline ExtendedKey parse_xkey(const std::string& s, uint32_t version) {
+    static const char* digits = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz";
+    uint8_t raw[82] = {0};
+    for (char ch : s) {
+        const char* d = ch ? std::strchr(digits, ch) : nullptr;
+        if (!d) throw std::invalid_argument("extended key: not a base58 digit");
+        uint32_t carry = (uint32_t)(d - digits);
+        for (int i = 81; i >= 0; i--) { carry += 58u * raw[i]; raw[i] = (uint8_t)carry; carry >>= 8; }
+        if (carry) throw std::invalid_argument("extended key: longer than 82 bytes");
+    }
+    uint8_t h1[32], h2[32];
+    sha256(raw, 78, h1); sha256(h1, 32, h2);
+    if (std::memcmp(h2, raw + 78, 4) != 0) throw std::invalid_argument("extended key: checksum");
+    if ((((uint32_t)raw[0] << 24) | ((uint32_t)raw[1] << 16) | ((uint32_t)raw[2] << 8) | raw[3]) != version) throw std::invalid_argument("extended key: version bytes");
+    ExtendedKey k;
+    k.depth = raw[4];
+    k.child_number = ((uint32_t)raw[9] << 24) | ((uint32_t)raw[10] << 16) | ((uint32_t)raw[11] << 8) | raw[12];
+    std::memcpy(k.chain.data(), raw + 13, 32);
+    std::memcpy(k.key.data(), raw + 45, 33);
+    return k;
+}
+}  // namespace hd_detail
+inline ExtendedKey parse_xprv(const std::string& s) {
+    const ExtendedKey k = hd_detail::parse_xkey(s, 0x0488ADE4u);
+    if (k.key[0] != 0) throw std::invalid_argument("parse_xprv: the key is not 00 || 32 bytes");
+    return k;
+}
+inline ExtendedKey parse_xpub(const std::string& s) {
+    const ExtendedKey k = hd_detail::parse_xkey(s, 0x0488B21Eu);
+    if (k.key[0] != 2 && k.key[0] != 3) throw std::invalid_argument("parse_xpub: the key is not a compressed point");
+    return k;
 }
 inline std::pair<AffinePoint, std::array<uint8_t, 20>> tx_sender(const uint8_t* raw, size_t len, Engine& eng = Engine::shared(), bool low_s = true) {
     const uint64_t off[2] = {0, (uint64_t)len};

@@ -48,6 +48,9 @@ typedef struct plume_ctx plume_ctx;
                                            every output record of the item is all zero */
 #define PLUME_STATUS_BAD_TX 16         /* plume_eth_tx_sign_batch* only: the unsigned transaction breaks a framing rule, its offsets are rejected or its slot reaches past \
                                           out_bytes; reported alone, whatever the key is */
+#define PLUME_STATUS_HD_NO_KEY 32      /* plume_hd_*_batch* only: BIP-32's outcomes that "have no key": IL >= n, child scalar 0 or child point = identity at some level \
+                                          (master: IL = 0 or IL >= n) */
+#define PLUME_STATUS_HD_HARDENED 64    /* plume_hd_derive_pub_batch* only: public derivation asked for an index >= 2^31 */
 
 /* Create a context bound to HIP device `device_id` (>= 0): streams, events and a small scratch area; about 1.5 ms.  The generator's fixed tables are built by the first call
  * that needs them, ONCE per device and process -- (1..2^23)*G for the verifier's 24-bit windows (1 GiB, first verify / verify_non_zk call) and the signer's doubling-free
@@ -680,6 +683,46 @@ int plume_eth_tx_sign_batch(plume_ctx* ctx, int flags, size_t n, const uint8_t* 
 int plume_eth_tx_sign_batch_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, const uint8_t* sk, const uint8_t* aux,
                                    uint8_t* out, size_t out_bytes, uint32_t* out_len, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
                                    uint8_t* tx_type, uint8_t* status, void* stream);
+
+/* ---- BIP-32 child keys, public keys and addresses  (library 0.17) ------------------------------------------------
+ * Wallets, custodians and test networks hold one seed or one account node, not an array of raw keys.  These calls derive the keys where the signers use them:
+ * the child_sk of the device form is the sk pointer plume_ecdsa_sign_batch_device, plume_eth_tx_sign_batch_device and plume_sign_batch*_device take, and the address
+ * records are what plume_nullset_* and plume_merkle_leaf_batch take.
+ *   I = HMAC-SHA512(key = c_par, data), IL = I[0:32], IR = I[32:64], the index i as four big-endian bytes, serP the 33-byte SEC1 compressed form:
+ *   private   data = 00 || ser256(k_par) || i when i >= 2^31 (hardened), serP(k_par G) || i otherwise;  k_i = IL + k_par mod n, c_i = IR
+ *   public    non-hardened only: data = serP(K_par) || i;  K_i = IL G + K_par, c_i = IR
+ *   master    I = HMAC-SHA512(key = "Bitcoin seed", seed), 16 <= seed_len <= 64, the same for all items;  k = IL, c = IR
+ * Item i walks `depth` levels (1 .. PLUME_HD_MAX_DEPTH): the indices path[i][0 .. depth), uint32_t in host order, row-major.  flags: PLUME_HD_SHARED_PARENT -- the parent
+ * arrays hold ONE record, used for every item; PLUME_HD_SHARED_PATH -- path holds ONE row.  pk_format / addr_format are PLUME_ETH_PK_* / PLUME_ETH_ADDR_*: parent_pk
+ * and child_pk are in pk_format, address in addr_format.  child_chain32, child_pk (private form) and address may be NULL.
+ *   status    (required) 0: derived.  PLUME_STATUS_BAD_SCALAR: parent sk outside [1, n - 1], or parent pk not a non-identity curve point in the given format.
+ *             PLUME_STATUS_HD_NO_KEY, PLUME_STATUS_HD_HARDENED: above.  The first level that fails decides.  An item with any non-zero status has every output record
+ *             all zero; a zero sk fed on into a signer reports PLUME_STATUS_BAD_SCALAR there.
+ * Argument errors return PLUME_ERR_ARG with nothing written: depth outside 1 .. PLUME_HD_MAX_DEPTH, unknown flag bits, seed_len outside 16 .. 64, an unknown format, a
+ * null required array.  n = 0 is a successful no-op.  Arrays may sit at any byte offset.
+ * Device side, one lane per item: the private form runs, for every level and once more at the end, k G by the signer's comb at the context's uniform level
+ * (plume_set_sign_uniform) and the batched conversion to affine -- for EVERY item, hardened or not, so no lane's work depends on its path --, then the HMAC and the tweak;
+ * the hardened or the public preimage is chosen by select on the index bit, and the range check, the reduction, zero detection and the zeroing of a failed item are
+ * selects too.  The public form hashes serP(K), multiplies IL (public) by the comb and adds K.  k, the chain codes and the images of k G between the levels live in
+ * staging the context owns and are wiped on the call's stream behind the last kernel, on failure paths too.  There is no self-check for derivation.  With stage timing on
+ * the stages are "hd_master"; "hd_priv_load", "hd_gmul", "to_affine", "hd_priv_step", "hd_finish"; "hd_pub_load", "hd_pub_step".  The device forms need a single-device
+ * context and n <= the chunk size, wait for and leave the workspace event (master: no workspace), build the signer's table on first use and do not synchronise.  The host
+ * forms are serial calls: pieces of at most plume_set_chunk items, the shards of a plume_init_multi context; sk, chain codes and seeds -- going in and coming out -- are
+ * wiped from the staging behind their use or their download; a shared parent or path is uploaded once per piece or once per call. */
+#define PLUME_HD_MAX_DEPTH 8
+#define PLUME_HD_SHARED_PARENT 1 /* flags bit 0: the parent arrays hold ONE record, used for every item */
+#define PLUME_HD_SHARED_PATH 2   /* flags bit 1: path holds ONE row of `depth` indices, used for every item */
+int plume_hd_master_batch(plume_ctx* ctx, size_t n, const uint8_t* seed, size_t seed_len, uint8_t* sk32, uint8_t* chain32, uint8_t* status);
+int plume_hd_master_batch_device(plume_ctx* ctx, size_t n, const uint8_t* seed, size_t seed_len, uint8_t* sk32, uint8_t* chain32, uint8_t* status, void* stream);
+int plume_hd_derive_priv_batch(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* parent_sk32, const uint8_t* parent_chain32,
+                               const uint32_t* path, size_t depth, uint8_t* child_sk32, uint8_t* child_chain32, uint8_t* child_pk, uint8_t* address, uint8_t* status);
+int plume_hd_derive_priv_batch_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* parent_sk32, const uint8_t* parent_chain32,
+                                      const uint32_t* path, size_t depth, uint8_t* child_sk32, uint8_t* child_chain32, uint8_t* child_pk, uint8_t* address,
+                                      uint8_t* status, void* stream);
+int plume_hd_derive_pub_batch(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* parent_pk, const uint8_t* parent_chain32,
+                              const uint32_t* path, size_t depth, uint8_t* child_pk, uint8_t* child_chain32, uint8_t* address, uint8_t* status);
+int plume_hd_derive_pub_batch_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* parent_pk, const uint8_t* parent_chain32,
+                                     const uint32_t* path, size_t depth, uint8_t* child_pk, uint8_t* child_chain32, uint8_t* address, uint8_t* status, void* stream);
 
 /* ---- Keccak Merkle allow-lists of addresses  (library 0.15) -------------------------------------------------------
  * An application that gates on a list of accounts usually publishes ONE 32-byte root and lets every claimant bring a proof.  These calls build that tree, hand out proofs

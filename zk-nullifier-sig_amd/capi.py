@@ -183,6 +183,13 @@ def _load():
     fn = getattr(lib, "plume_eth_tx_sign_out_bytes", None)
     if fn is not None:
         fn.argtypes, fn.restype = [sz, C.c_uint64], C.c_void_p                     # (a size_t)
+    # BIP-32 key derivation (library 0.17; Engine.hd_* raise PlumeHipError on an older build)
+    for name, args in (("plume_hd_master_batch", [vp, sz, vp, sz, vp, vp, vp]), ("plume_hd_master_batch_device", [vp, sz, vp, sz, vp, vp, vp, vp]),
+                       ("plume_hd_derive_priv_batch", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 5), ("plume_hd_derive_priv_batch_device", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 6),
+                       ("plume_hd_derive_pub_batch", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 4), ("plume_hd_derive_pub_batch_device", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 5)):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
     _lib = lib
     # (the 0.13 entry points are told by their symbols: plume_version() still begins "plume_hip 0.12")
     if (_version(lib) < (0, 12) or getattr(lib, "plume_ecdsa_sign_batch", None) is None) and not os.environ.get("PLUME_HIP_LIB"):
@@ -207,7 +214,9 @@ def exported_symbols():
             "plume_eth_tx_parse_batch", "plume_eth_tx_parse_batch_device", "plume_eth_tx_sender_batch", "plume_eth_tx_sender_batch_device",
             "plume_merkle_max_proof_len", "plume_merkle_leaf_batch", "plume_merkle_leaf_batch_device", "plume_merkle_tree_build", "plume_merkle_tree_build_device",
             "plume_merkle_proof_batch", "plume_merkle_proof_batch_device", "plume_merkle_verify_batch", "plume_merkle_verify_batch_device",
-            "plume_eth_tx_sign_out_bytes", "plume_eth_tx_sign_batch", "plume_eth_tx_sign_batch_device"]
+            "plume_eth_tx_sign_out_bytes", "plume_eth_tx_sign_batch", "plume_eth_tx_sign_batch_device",
+            "plume_hd_master_batch", "plume_hd_master_batch_device", "plume_hd_derive_priv_batch", "plume_hd_derive_priv_batch_device",
+            "plume_hd_derive_pub_batch", "plume_hd_derive_pub_batch_device"]
 
 
 def pack_messages(msgs):
@@ -250,6 +259,11 @@ ETH_TX_OK, ETH_TX_INVALID = 1, 3
 # plume_eth_tx_sign_batch (include/plume_hip.h): the status bit it adds to the signer's (0, 2, 4, 8) and the bytes a slot has beyond its unsigned item
 STATUS_BAD_TX = 16
 ETH_TX_SIGN_GROWTH = 68
+# plume_hd_*_batch (include/plume_hip.h): the deepest path, the flag bits, the status bits they add to PLUME_STATUS_BAD_SCALAR (2), the first hardened index
+HD_MAX_DEPTH = 8
+HD_SHARED_PARENT, HD_SHARED_PATH = 1, 2
+STATUS_HD_NO_KEY, STATUS_HD_HARDENED = 32, 64
+HD_HARDENED = 2**31
 # plume_merkle_* (include/plume_hip.h): leaf formats -> (PLUME_MERKLE_LEAF_*), the sort flag, the status of an item, the proof length of a refused index
 MERKLE_LEAF_FORMATS = {"hash32": 0, "address": 1, "address_uint256": 2}
 MERKLE_SORT_LEAVES = 1
@@ -698,6 +712,113 @@ class Engine:
             return raw, res["status"], {k: res[k] for k in ("hash", "r", "s", "v", "chain_id", "tx_type")}
         return raw, res["status"]
 
+    def _hd_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no key derivation: {name} came with library 0.17 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    def hd_master_batch(self, seed, seed_len=None):
+        """BIP-32 master nodes (plume_hd_master_batch).  seed: n x seed_len bytes (a 2-D array, or flat with seed_len given), 16 <= seed_len <= 64.  Returns
+        (sk, chain, status): n x 32 bytes each and n status bytes -- 0, or STATUS_HD_NO_KEY (32) with both records all zero."""
+        fn = self._hd_fn("plume_hd_master_batch")
+        seed = np.ascontiguousarray(seed, dtype=np.uint8)
+        if seed_len is None:
+            if seed.ndim != 2:
+                raise ValueError("seed: give an n x seed_len array, or seed_len")
+            seed_len = seed.shape[1]
+        if seed_len <= 0 or seed.size % int(seed_len):
+            raise ValueError("seed: not a whole number of seed_len-byte records")
+        n = seed.size // int(seed_len)
+        sk, chain, status = np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        self._chk(fn(self._ctx, n, _ptr(seed), int(seed_len), _ptr(sk), _ptr(chain), _ptr(status)), "plume_hd_master_batch")
+        return sk, chain, status
+
+    @staticmethod
+    def _hd_shape(parent, width, chain, path, name):
+        """(flags, n, depth, parent, chain, path) of a derive call: a parent of ONE record or a path of ONE row is shared by every item"""
+        path = np.ascontiguousarray(path, dtype=np.uint32)
+        if path.ndim == 1:
+            path = path.reshape(1, -1)
+        parent, chain = np.ascontiguousarray(parent, dtype=np.uint8).reshape(-1, width), np.ascontiguousarray(chain, dtype=np.uint8).reshape(-1, 32)
+        if len(parent) != len(chain):
+            raise ValueError(f"{name}: {len(parent)} parent keys and {len(chain)} chain codes")
+        n = max(len(parent), len(path))
+        flags = (HD_SHARED_PARENT if len(parent) == 1 and n > 1 else 0) | (HD_SHARED_PATH if len(path) == 1 and n > 1 else 0)
+        if len(parent) not in (1, n) or len(path) not in (1, n):
+            raise ValueError(f"{name}: {len(parent)} parents and {len(path)} paths")
+        return flags, n, path.shape[1], parent, chain, path
+
+    def hd_derive_priv_batch(self, parent_sk, parent_chain, path, pk_format="affine64", addr_format="raw20", want=("chain", "pk", "address"), device=False):
+        """BIP-32 private derivation (plume_hd_derive_priv_batch).  parent_sk, parent_chain: n x 32 bytes, or ONE record shared by every item; path: n x depth uint32
+        indices (>= 2^31: hardened), or ONE row shared by every item.  Returns a dict: sk (n x 32), status (n: 0, 2, 32) and the records named in `want` -- chain,
+        pk (pk_format), address (addr_format).  An item with a status has all-zero records.  device=True: everything stays on the GPU -- the inputs may be torch
+        tensors on the engine's device, the dict holds torch uint8 tensors, and sk goes into ecdsa_sign_batch_device / eth_tx_sign_batch_device as it is (synchronises
+        only as torch does)."""
+        if device:
+            return self._hd_derive_torch(False, parent_sk, parent_chain, path, pk_format, addr_format, want)
+        fn = self._hd_fn("plume_hd_derive_priv_batch")
+        flags, n, depth, parent_sk, parent_chain, path = self._hd_shape(parent_sk, 32, parent_chain, path, "hd_derive_priv_batch")
+        res = {"sk": np.zeros((n, 32), np.uint8), "status": np.zeros(n, np.uint8)}
+        shape = {"chain": 32, "pk": ETH_PK_FORMATS[pk_format][1], "address": ETH_ADDR_FORMATS[addr_format][1]}
+        for k in want:
+            res[k] = np.zeros((n, shape[k]), np.uint8)
+        self._chk(fn(self._ctx, flags, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], n, _ptr(parent_sk), _ptr(parent_chain), _ptr(path), depth,
+                     _ptr(res["sk"]), _ptr(res.get("chain")), _ptr(res.get("pk")), _ptr(res.get("address")), _ptr(res["status"])), "plume_hd_derive_priv_batch")
+        return res
+
+    def hd_derive_pub_batch(self, parent_pk, parent_chain, path, pk_format="affine64", addr_format="raw20", want=("chain", "address"), device=False):
+        """BIP-32 public derivation (plume_hd_derive_pub_batch): non-hardened indices only.  parent_pk in pk_format; the rest as hd_derive_priv_batch.  Returns a dict: pk
+        (pk_format), status (n: 0, 2, 32, 64) and the records named in `want` -- chain, address."""
+        if device:
+            return self._hd_derive_torch(True, parent_pk, parent_chain, path, pk_format, addr_format, want)
+        fn = self._hd_fn("plume_hd_derive_pub_batch")
+        flags, n, depth, parent_pk, parent_chain, path = self._hd_shape(parent_pk, ETH_PK_FORMATS[pk_format][1], parent_chain, path, "hd_derive_pub_batch")
+        res = {"pk": np.zeros((n, ETH_PK_FORMATS[pk_format][1]), np.uint8), "status": np.zeros(n, np.uint8)}
+        shape = {"chain": 32, "address": ETH_ADDR_FORMATS[addr_format][1]}
+        for k in want:
+            res[k] = np.zeros((n, shape[k]), np.uint8)
+        self._chk(fn(self._ctx, flags, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], n, _ptr(parent_pk), _ptr(parent_chain), _ptr(path), depth,
+                     _ptr(res["pk"]), _ptr(res.get("chain")), _ptr(res.get("address")), _ptr(res["status"])), "plume_hd_derive_pub_batch")
+        return res
+
+    def _hd_derive_torch(self, pub, parent, parent_chain, path, pk_format, addr_format, want):
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        width = ETH_PK_FORMATS[pk_format][1] if pub else 32
+
+        def rows(a, w, dtype):
+            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32 if dtype is torch.int32 else np.uint8).view(np.int32 if dtype is torch.int32 else np.uint8))
+            t = t.to(dev).contiguous()
+            return t.reshape(1, -1) if t.ndim == 1 and w is None else (t if w is None else t.reshape(-1, w))
+        parent, parent_chain, path = rows(parent, width, torch.uint8), rows(parent_chain, 32, torch.uint8), rows(path, None, torch.int32)
+        if path.element_size() != 4:
+            raise ValueError("path: a tensor of 4-byte indices")
+        if len(parent) != len(parent_chain):
+            raise ValueError(f"{len(parent)} parent keys and {len(parent_chain)} chain codes")
+        n = max(len(parent), len(path))
+        if len(parent) not in (1, n) or len(path) not in (1, n):
+            raise ValueError(f"{len(parent)} parents and {len(path)} paths")
+        flags = (HD_SHARED_PARENT if len(parent) == 1 and n > 1 else 0) | (HD_SHARED_PATH if len(path) == 1 and n > 1 else 0)
+        z = lambda w: torch.zeros((n, w), dtype=torch.uint8, device=dev)  # noqa: E731
+        res = {"status": torch.zeros(n, dtype=torch.uint8, device=dev)}
+        if not pub:
+            res["sk"] = z(32)
+        shape = {"chain": 32, "pk": ETH_PK_FORMATS[pk_format][1], "address": ETH_ADDR_FORMATS[addr_format][1]}
+        for k in tuple(want) + (("pk",) if pub else ()):
+            res[k] = z(shape[k])
+        # on a stream of its own between two waits: torch's default stream is the null stream, which the library takes to mean the context's stream -- and that one
+        # is not ordered against the fills above or the caller's next use of the tensors
+        cur = torch.cuda.current_stream(dev)
+        st = torch.cuda.Stream(dev)
+        st.wait_stream(cur)
+        self.hd_derive_batch_device(pub, flags, n, parent, parent_chain, path, path.shape[1], res.get("sk"), res.get("chain"), res.get("pk"), res.get("address"),
+                                    res["status"], pk_format, addr_format, stream=st)
+        cur.wait_stream(st)
+        for t in (parent, parent_chain, path, *res.values()):
+            t.record_stream(st)
+        return res
+
     def _merkle_fn(self, name):
         fn = getattr(self._lib, name, None)
         if fn is None:
@@ -1021,6 +1142,29 @@ class Engine:
         d = self._dp
         self._chk(fn(self._ctx, 0, int(n), d(txs), d(tx_off), int(txs_bytes), d(sk), d(aux), d(out), int(out_bytes), d(out_len), d(hash32), d(r), d(s), d(v), d(chain_id),
                      d(tx_type), d(status), C.c_void_p(st)), "plume_eth_tx_sign_batch_device")
+
+    def hd_master_batch_device(self, n, seed, seed_len, sk, chain, status, stream=None):
+        """the device form of hd_master_batch on torch tensors; one kernel on `stream` (None = current stream); does not synchronise"""
+        import torch
+        fn = self._hd_fn("plume_hd_master_batch_device")
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        self._chk(fn(self._ctx, int(n), d(seed), int(seed_len), d(sk), d(chain), d(status), C.c_void_p(st)), "plume_hd_master_batch_device")
+
+    def hd_derive_batch_device(self, pub, flags, n, parent, parent_chain, path, depth, child_sk, child_chain, child_pk, address, status, pk_format="affine64",
+                               addr_format="raw20", stream=None):
+        """the device forms of hd_derive_priv_batch (pub False: parent is sk, child_sk required) and hd_derive_pub_batch (pub True: parent is pk, child_sk ignored, child_pk
+        required) on torch tensors; path: n x depth 4-byte indices (one row with HD_SHARED_PATH); the optional records may be None; enqueues on `stream` (None = current
+        stream); does not synchronise.  child_sk is what ecdsa_sign_batch_device and eth_tx_sign_batch_device take as sk."""
+        import torch
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        d = self._dp
+        head = (self._ctx, int(flags), ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(parent), d(parent_chain), d(path), int(depth))
+        if pub:
+            self._chk(self._hd_fn("plume_hd_derive_pub_batch_device")(*head, d(child_pk), d(child_chain), d(address), d(status), C.c_void_p(st)), "plume_hd_derive_pub_batch_device")
+        else:
+            self._chk(self._hd_fn("plume_hd_derive_priv_batch_device")(*head, d(child_sk), d(child_chain), d(child_pk), d(address), d(status), C.c_void_p(st)),
+                      "plume_hd_derive_priv_batch_device")
 
     def merkle_leaf_batch_device(self, n, items, amounts, leaf32, status, leaf_format="address", addr_format="raw20", stream=None):
         """the device form of merkle_leaf_batch on torch tensors; amounts (n x 32 big-endian bytes) and status may be None; one kernel on `stream` (None = current

@@ -1,4 +1,4 @@
-// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_eth_hash_capi.hip, plume_ecdsa_capi.hip, plume_ecdsa_sign_capi.hip, plume_eth_tx_capi.hip, plume_eth_tx_sign_capi.hip, plume_merkle_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
+// The few services of plume_capi.hip that other translation units of the library use (plume_nullset_capi.hip, plume_nonce_capi.hip, plume_selfcheck_capi.hip, plume_recover_capi.hip, plume_eth_capi.hip, plume_eth_hash_capi.hip, plume_ecdsa_capi.hip, plume_ecdsa_sign_capi.hip, plume_eth_tx_capi.hip, plume_eth_tx_sign_capi.hip, plume_merkle_capi.hip, plume_hd_capi.hip).  Internal: not part of the ABI, hidden in the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -178,5 +178,33 @@ __attribute__((visibility("hidden"))) int capi_eth_tx_sign_device(plume_ctx* ctx
                                                                   const uint8_t* sk, const uint8_t* aux, uint8_t* out, size_t out_bytes, uint32_t* out_len, uint8_t* hash32,
                                                                   uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream,
                                                                   const EthTxSignLaunch* fn);
+
+// The key derivation (plume_hd_master_batch*, plume_hd_derive_priv_batch*, plume_hd_derive_pub_batch*).  master is one kernel on the caller's arrays.  The two derive calls
+// keep k, the chain code and the status of every item in staging the context owns (65 B / item) and the points in the signer's result array: load, then per level the comb
+// (private form: at the context's uniform level), the conversion to affine and the step kernel, then finish into the caller's arrays.  The staging and the Jacobian images
+// are wiped on the call's stream behind finish, and on failure paths too.  Tables, the workspace chain, the chunk limit and routing are the ECDSA signer's; the launchers come
+// in as a hook struct.  The host-pointer forms are serial calls (serial_host_call_any): sk, chain codes and seeds staged as secrets -- inputs and outputs --, a shared
+// parent or path as whole-call inputs.
+struct HdArgs;
+struct HdLaunch {
+    void (*master)(const HdArgs& a, hipStream_t st);
+    void (*priv_load)(const HdArgs& a, hipStream_t st);
+    void (*pub_load)(const HdArgs& a, hipStream_t st);
+    void (*gmul)(const HdArgs& a, hipStream_t st);
+    void (*priv_step)(const HdArgs& a, hipStream_t st);
+    void (*pub_step)(const HdArgs& a, hipStream_t st);
+    void (*finish)(const HdArgs& a, hipStream_t st);
+};
+__attribute__((visibility("hidden"))) int capi_hd_master(plume_ctx* ctx, size_t n, const uint8_t* seed, size_t seed_len, uint8_t* sk, uint8_t* chain, uint8_t* status,
+                                                         const HdLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_hd_master_device(plume_ctx* ctx, size_t n, const uint8_t* seed, size_t seed_len, uint8_t* sk, uint8_t* chain, uint8_t* status,
+                                                                void* stream, const HdLaunch* fn);
+// pub = false: parent is sk, child_sk is required.  pub = true: parent is pk in pk_format, child_sk is NULL and child_pk required
+__attribute__((visibility("hidden"))) int capi_hd_derive(plume_ctx* ctx, bool pub, int flags, int pk_format, int addr_format, size_t n, const uint8_t* parent,
+                                                         const uint8_t* parent_chain, const uint32_t* path, size_t depth, uint8_t* child_sk, uint8_t* child_chain,
+                                                         uint8_t* child_pk, uint8_t* address, uint8_t* status, const HdLaunch* fn);
+__attribute__((visibility("hidden"))) int capi_hd_derive_device(plume_ctx* ctx, bool pub, int flags, int pk_format, int addr_format, size_t n, const uint8_t* parent,
+                                                                const uint8_t* parent_chain, const uint32_t* path, size_t depth, uint8_t* child_sk, uint8_t* child_chain,
+                                                                uint8_t* child_pk, uint8_t* address, uint8_t* status, void* stream, const HdLaunch* fn);
 
 }  // namespace plume

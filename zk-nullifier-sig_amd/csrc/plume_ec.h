@@ -98,8 +98,14 @@ PLUME_HD void jac_dbl_neg(jac& p) {
 // cold path of the additions (P == Q).  Takes and returns BY VALUE through a local copy at the call site: passing the
 // accumulator by reference would make its address escape and pin it in scratch memory for the whole hot loop
 // (measured: ~900 scratch stores per lane and 21 GB of write traffic per 2^20 batch before this change).
+// PLUME_COLD_DBL_INLINE (plume_hd_kernels.hip): the doubling inlined at the call site instead -- no call, so no copy in scratch at all; for kernels whose hot loop is short
+// enough to carry the extra code.
 PLUME_HD_NOINLINE void jac_dbl_cold_impl(jac* p) { jac_dbl(*p); }
+#if defined(PLUME_COLD_DBL_INLINE)
+PLUME_HD void jac_dbl_cold(jac& p) { jac_dbl(p); }
+#else
 PLUME_HD void jac_dbl_cold(jac& p) { jac tmp = p; jac_dbl_cold_impl(&tmp); p = tmp; }
+#endif
 
 // p += (qx, qy) affine, q != infinity; qx tight, qy tight or an unreduced negation (limbs <= 2p).  8M + 3S, no carry pass (round 3: the three subtractions ride in their products' folds).
 // CHECKED = true handles every exceptional case (p infinite, p == q, p == -q).

@@ -21,7 +21,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .capi import ECDSA_INVALID, ETH_INVALID, ETH_MATCH, ETH_TX_OK, MERKLE_MATCH, RECOVER_INVALID, RECOVER_MATCH, STATUS_BAD_TX, Engine, default_engine, pack_messages
+from .capi import (ECDSA_INVALID, ETH_INVALID, ETH_MATCH, ETH_TX_OK, HD_HARDENED, HD_MAX_DEPTH, MERKLE_MATCH, RECOVER_INVALID, RECOVER_MATCH, STATUS_BAD_TX, STATUS_HD_HARDENED,
+                   STATUS_HD_NO_KEY, Engine, default_engine, pack_messages)
 
 DST = b"QUUX-V01-CS02-with-secp256k1_XMD:SHA-256_SSWU_RO_"  # rust-k256/src/lib.rs:61
 _P = 2**256 - 2**32 - 977
@@ -410,6 +411,131 @@ def sign_tx(sk, unsigned: bytes, aux: Optional[bytes] = None, engine: Optional[E
     if st:
         raise SignatureError(f"sign_tx: no signature (status {st}: {'sk outside [1, n - 1]' if st == 2 else 'a degenerate outcome'})")
     return raw[0]
+
+
+# ------------------------------------------------------------------------------------------------ BIP-32 (library 0.17)
+def parse_path(path: str):
+    """The indices of a BIP-32 path: "m/44'/60'/0'/0/3" or, relative to a node, "0/3".  A component is a decimal number below 2^31; a trailing ' or h makes it
+    hardened (+ 2^31).  At most 8 components (PLUME_HD_MAX_DEPTH); "m" alone, "m/" and an empty component are errors (ValueError)."""
+    parts = str(path).split("/")
+    if parts[0] == "m":
+        parts = parts[1:]
+    if not 1 <= len(parts) <= HD_MAX_DEPTH:
+        raise ValueError(f"parse_path: {path!r} has {len(parts)} components; 1 .. {HD_MAX_DEPTH} are derived")
+    out = []
+    for c in parts:
+        hard = c[-1:] in ("'", "h")
+        num = c[:-1] if hard else c
+        if not num.isascii() or not num.isdigit() or int(num) >= HD_HARDENED:
+            raise ValueError(f"parse_path: component {c!r} of {path!r} is not an index below 2^31")
+        out.append(int(num) + (HD_HARDENED if hard else 0))
+    return out
+
+
+def _hd_status(what: str, st: int):
+    if st == STATUS_HD_HARDENED:
+        raise SignatureError(f"{what}: a public key has no hardened children")
+    if st == STATUS_HD_NO_KEY:
+        raise SignatureError(f"{what}: the path has no key (BIP-32: IL >= n or a zero child; take the next index)")
+    if st:
+        raise SignatureError(f"{what}: the parent key is not valid (status {st})")
+
+
+def _hd_path(path):
+    return np.array([parse_path(path) if isinstance(path, str) else [int(i) for i in path]], dtype=np.uint32)
+
+
+def hd_master(seed: bytes, engine: Optional[Engine] = None) -> Tuple[bytes, bytes]:
+    """The BIP-32 master node (sk, chain) of a seed of 16 .. 64 bytes, made on the GPU (include/plume_hip.h, plume_hd_master_batch): HMAC-SHA512("Bitcoin seed", seed).
+    The seed of a BIP-39 mnemonic is hashlib.pbkdf2_hmac("sha512", mnemonic, b"mnemonic" + passphrase, 2048)."""
+    seed = bytes(seed)
+    if not 16 <= len(seed) <= 64:
+        raise ValueError("hd_master: a seed is 16 .. 64 bytes")
+    sk, chain, status = (engine or default_engine()).hd_master_batch(np.frombuffer(seed, dtype=np.uint8).reshape(1, -1))
+    _hd_status("hd_master", int(status[0]))
+    return sk[0].tobytes(), chain[0].tobytes()
+
+
+def hd_derive(sk, chain: bytes, path, engine: Optional[Engine] = None) -> Tuple[bytes, bytes]:
+    """The node (sk, chain) at `path` below the node (sk, chain): BIP-32's CKDpriv along "m/44'/60'/0'/0/3" (or a list of indices), on the GPU
+    (plume_hd_derive_priv_batch).  sk: a SecretKey or 32 big-endian bytes.  Raises SignatureError for a parent outside [1, n - 1] and for a path that has no key."""
+    sk32 = _b32("hd_derive", "sk", sk.to_bytes() if isinstance(sk, SecretKey) else sk)
+    a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
+    res = (engine or default_engine()).hd_derive_priv_batch(a(sk32), a(_b32("hd_derive", "chain", chain)), _hd_path(path), want=("chain",))
+    _hd_status("hd_derive", int(res["status"][0]))
+    return res["sk"][0].tobytes(), res["chain"][0].tobytes()
+
+
+def hd_derive_pub(pk, chain: bytes, path, engine: Optional[Engine] = None) -> Tuple[AffinePoint, bytes]:
+    """The public node (pk, chain) at the non-hardened `path` ("0/3") below the public node (pk, chain): BIP-32's CKDpub on the GPU (plume_hd_derive_pub_batch) --
+    what a watcher holding an xpub derives.  pk: an AffinePoint, 64 bytes x || y or 33 SEC1 bytes.  Raises SignatureError for a hardened index, an invalid key, no key."""
+    pk = pk.to_bytes64() if isinstance(pk, AffinePoint) else bytes(pk)
+    if len(pk) not in (33, 64):
+        raise ValueError("hd_derive_pub: pk is 64 bytes x || y or 33 SEC1 bytes")
+    a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
+    eng = engine or default_engine()
+    if len(pk) == 33:                                                        # SEC1 in, 64 bytes out: two calls would do it; one, with the address call's decoder, is enough
+        res = eng.hd_derive_pub_batch(a(pk), a(_b32("hd_derive_pub", "chain", chain)), _hd_path(path), pk_format="sec1", want=("chain",))
+        _hd_status("hd_derive_pub", int(res["status"][0]))
+        x = int.from_bytes(res["pk"][0, 1:].tobytes(), "big")
+        y = pow((x * x * x + 7) % _P, (_P + 1) // 4, _P)
+        return AffinePoint(x, y if (y & 1) == (int(res["pk"][0, 0]) & 1) else _P - y), res["chain"][0].tobytes()
+    res = eng.hd_derive_pub_batch(a(pk), a(_b32("hd_derive_pub", "chain", chain)), _hd_path(path), want=("chain",))
+    _hd_status("hd_derive_pub", int(res["status"][0]))
+    return AffinePoint.from_bytes64(res["pk"][0].tobytes()), res["chain"][0].tobytes()
+
+
+def hd_address(key, chain: bytes, path, engine: Optional[Engine] = None) -> bytes:
+    """The 20-byte Ethereum address of the key at `path`: below a private node (key: a SecretKey or 32 bytes; any path) or below a public one (key: an AffinePoint, 64 or
+    33 bytes; non-hardened indices only).  hd_address(*hd_master(seed), "m/44'/60'/0'/0/0") is a wallet's first account."""
+    a = lambda b: np.frombuffer(b, dtype=np.uint8)  # noqa: E731
+    eng = engine or default_engine()
+    if isinstance(key, SecretKey) or (not isinstance(key, AffinePoint) and len(bytes(key)) == 32):
+        sk32 = _b32("hd_address", "sk", key.to_bytes() if isinstance(key, SecretKey) else key)
+        res = eng.hd_derive_priv_batch(a(sk32), a(_b32("hd_address", "chain", chain)), _hd_path(path), want=("address",))
+    else:
+        pk = key.to_bytes64() if isinstance(key, AffinePoint) else bytes(key)
+        if len(pk) not in (33, 64):
+            raise ValueError("hd_address: key is a 32-byte sk, or a pk of 64 bytes x || y or 33 SEC1 bytes")
+        res = eng.hd_derive_pub_batch(a(pk), a(_b32("hd_address", "chain", chain)), _hd_path(path), pk_format="sec1" if len(pk) == 33 else "affine64", want=("address",))
+    _hd_status("hd_address", int(res["status"][0]))
+    return res["address"][0].tobytes()
+
+
+_B58 = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"
+
+
+def _xkey(what: str, s: str, version: bytes) -> bytes:
+    import hashlib
+    v = 0
+    for ch in str(s):
+        d = _B58.find(ch)
+        if d < 0:
+            raise ValueError(f"{what}: {ch!r} is not a base58 digit")
+        v = v * 58 + d
+    raw = v.to_bytes(82, "big") if v < 1 << (8 * 82) else b""
+    if len(raw) != 82 or hashlib.sha256(hashlib.sha256(raw[:78]).digest()).digest()[:4] != raw[78:]:
+        raise ValueError(f"{what}: not 78 bytes with a valid base58check checksum")
+    if raw[:4] != version:
+        raise ValueError(f"{what}: version bytes {raw[:4].hex()}, expected {version.hex()}")
+    return raw[:78]
+
+
+def parse_xprv(s: str) -> Tuple[int, int, bytes, bytes]:
+    """(depth, child_number, chain, sk) of a mainnet extended private key "xprv..." -- base58check DECODE only: hd_derive(sk, chain, path) takes it from there.
+    ValueError for a bad digit, length, checksum, version or key byte."""
+    b = _xkey("parse_xprv", s, bytes.fromhex("0488ade4"))
+    if b[45] != 0:
+        raise ValueError("parse_xprv: the key is not 00 || 32 bytes")
+    return b[4], int.from_bytes(b[9:13], "big"), b[13:45], b[46:78]
+
+
+def parse_xpub(s: str) -> Tuple[int, int, bytes, bytes]:
+    """(depth, child_number, chain, pk33) of a mainnet extended public key "xpub...": hd_derive_pub(pk33, chain, path) takes it from there"""
+    b = _xkey("parse_xpub", s, bytes.fromhex("0488b21e"))
+    if b[45] not in (2, 3):
+        raise ValueError("parse_xpub: the key is not a compressed point")
+    return b[4], int.from_bytes(b[9:13], "big"), b[13:45], b[45:78]
 
 
 def _tx_sender(what: str, want, raw: bytes, engine: Optional[Engine], low_s: bool):

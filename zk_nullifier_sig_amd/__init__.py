@@ -4,7 +4,7 @@ from pathlib import Path as _Path
 
 __path__.append(str(_Path(__file__).resolve().parent.parent / "zk-nullifier-sig_amd"))
 
-from .capi import ECDSA_INVALID, ECDSA_LOW_S, ECDSA_MATCH, ECDSA_MISMATCH, ECDSA_SIGN_V27, ETH_HASH_MODES, ETH_INVALID, ETH_MATCH, ETH_MISMATCH, ETH_TX_INVALID, ETH_TX_OK, ETH_TX_SIGN_GROWTH, MERKLE_BAD_PROOF, MERKLE_INVALID, MERKLE_MATCH, MERKLE_MISMATCH, Engine, MerkleTree, NullifierSet, PlumeHipError, STATUS_BAD_TX, default_engine, library_path  # noqa: E402,F401
+from .capi import ECDSA_INVALID, ECDSA_LOW_S, ECDSA_MATCH, ECDSA_MISMATCH, ECDSA_SIGN_V27, ETH_HASH_MODES, ETH_INVALID, ETH_MATCH, ETH_MISMATCH, ETH_TX_INVALID, ETH_TX_OK, ETH_TX_SIGN_GROWTH, HD_HARDENED, HD_MAX_DEPTH, HD_SHARED_PARENT, HD_SHARED_PATH, MERKLE_BAD_PROOF, MERKLE_INVALID, MERKLE_MATCH, MERKLE_MISMATCH, Engine, MerkleTree, NullifierSet, PlumeHipError, STATUS_BAD_TX, STATUS_HD_HARDENED, STATUS_HD_NO_KEY, default_engine, library_path  # noqa: E402,F401
 from .plume import (  # noqa: E402,F401
     DST,
     AffinePoint,
@@ -33,6 +33,13 @@ from .plume import (  # noqa: E402,F401
     sign,
     sign_with_r,
     sign_tx,
+    hd_address,
+    hd_derive,
+    hd_derive_pub,
+    hd_master,
+    parse_path,
+    parse_xprv,
+    parse_xpub,
     tx_sender,
     tx_sender_address,
     tx_signing_hash,
