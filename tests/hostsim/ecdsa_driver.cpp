@@ -1,5 +1,4 @@
-// TEST INFRASTRUCTURE ONLY.  plume_ecdsa_recover_batch* on the library's host side (capi_ecdsa_recover / capi_ecdsa_recover_device in csrc/plume_capi.hip +
-// csrc/plume_ecdsa_capi.hip) on the mock HIP runtime, under the sanitizers (tests/test_ecdsa_hostsim.py).
+// TEST INFRASTRUCTURE ONLY.  plume_ecdsa_recover_batch* on the library's host side (csrc/plume_ecdsa_capi.hip) on the mock HIP runtime, under the sanitizers (tests/test_ecdsa_hostsim.py).
 // usage: ecdsa_driver VECTORS SEED.  VECTORS is written by the test from the Python restatement (tests/_ecdsa.py): u32 n, then n hashes, n r, n s (32 bytes each), n v
 // (1 byte), n status bytes (1 recovered / 3 invalid), n keys of 64 bytes, n raw addresses, n EIP-55 records of 42 bytes (zeros for an invalid item).  Every call must
 // reproduce those bytes: the host form with chunks of 1, 64 and n, pageable and page-locked arrays, expect absent / matching / wrong, each output NULL, the device form on

@@ -1,5 +1,4 @@
-// TEST INFRASTRUCTURE ONLY.  plume_ecdsa_sign_batch* and plume_eth_message_hash_batch* on the library's host side (capi_ecdsa_sign*, capi_eth_message_hash* in
-// csrc/plume_capi.hip + csrc/plume_ecdsa_sign_capi.hip, csrc/plume_eth_hash_capi.hip) on the mock HIP runtime, under the sanitizers (tests/test_ecdsa_sign_hostsim.py).
+// TEST INFRASTRUCTURE ONLY.  plume_ecdsa_sign_batch* and plume_eth_message_hash_batch* on the library's host side (csrc/plume_ecdsa_sign_capi.hip, csrc/plume_eth_hash_capi.hip) on the mock HIP runtime, under the sanitizers (tests/test_ecdsa_sign_hostsim.py).
 // usage: ecdsa_sign_driver VECTORS SEED.  VECTORS is written by the test from the Python restatement (tests/_ecdsa_sign.py): u32 n, n hashes, n sk, n aux (32 bytes each),
 // then what the call gives without aux and with it -- n r, n s (32 bytes), n v in {0, 1}, n status bytes, twice; then u32 m, m + 1 u64 message offsets, the message bytes,
 // m digests of mode 0 and m of mode 1.  Every call must reproduce those bytes: the host form with chunks smaller than n, pageable and page-locked arrays, the device form

@@ -1,5 +1,4 @@
-// TEST INFRASTRUCTURE ONLY.  plume_eth_address_batch* on the library's host side (capi_eth_address / capi_eth_address_device in csrc/plume_capi.hip +
-// csrc/plume_eth_capi.hip) on the mock HIP runtime, under the sanitizers (tests/test_eth_hostsim.py).
+// TEST INFRASTRUCTURE ONLY.  plume_eth_address_batch* on the library's host side (csrc/plume_eth_capi.hip) on the mock HIP runtime, under the sanitizers (tests/test_eth_hostsim.py).
 // usage: eth_driver VECTORS SEED.  VECTORS is written by the test from the Python restatement (tests/_keccak.py), for each key format (64-byte, then SEC1): u32 n, the n
 // keys, n status bytes (1 valid / 3 no key), n raw addresses (zeros for an invalid key), n EIP-55 records (42 bytes, zeros likewise).  Every call must reproduce those
 // bytes: the host form with chunks smaller than n, pageable and page-locked arrays, expect absent / matching / wrong, NULL address / NULL status, the device form on a

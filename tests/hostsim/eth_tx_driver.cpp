@@ -1,5 +1,4 @@
-// TEST INFRASTRUCTURE ONLY.  plume_eth_tx_parse_batch* and plume_eth_tx_sender_batch* on the library's host side (capi_eth_tx_* in csrc/plume_capi.hip +
-// csrc/plume_eth_tx_capi.hip) on the mock HIP runtime, under the sanitizers (tests/test_eth_tx_hostsim.py).
+// TEST INFRASTRUCTURE ONLY.  plume_eth_tx_parse_batch* and plume_eth_tx_sender_batch* on the library's host side (csrc/plume_eth_tx_capi.hip) on the mock HIP runtime, under the sanitizers (tests/test_eth_tx_hostsim.py).
 // usage: eth_tx_driver VECTORS SEED.  VECTORS is written by the test from the Python restatement (tests/_eth_tx.py, tests/_ecdsa.py) over the committed fixture: u32 n,
 // n + 1 u64 offsets, the bytes, then what the parse writes (hash, r, s 32 n each; v, tx_type, status n each; chain_id 8 n) and what the sender writes under
 // PLUME_ECDSA_LOW_S in the 64-byte / raw formats (pk 64 n, address 20 n, status n).  Every call on a range of the items must reproduce those bytes: the host form with

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE ONLY.  plume_eth_tx_sign_batch* on the library's host side (capi_eth_tx_sign* in csrc/plume_capi.hip + csrc/plume_eth_tx_sign_capi.hip) on the mock
+// TEST INFRASTRUCTURE ONLY.  plume_eth_tx_sign_batch* on the library's host side (csrc/plume_eth_tx_sign_capi.hip) on the mock
 // HIP runtime, under the sanitizers (tests/test_eth_tx_sign_hostsim.py).
 // usage: eth_tx_sign_driver VECTORS SEED.  VECTORS is written by the test from the Python restatement (tests/_eth_tx_sign.py): u32 n, n + 1 u64 offsets, the bytes, n sk, n
 // aux (32 bytes each), then what the call gives without aux and with it -- out (bytes + 68 n), out_len (4 n), status (n), hash, r, s (32 n each), v (n), chain_id (8 n),

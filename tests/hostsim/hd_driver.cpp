@@ -1,5 +1,4 @@
-// TEST INFRASTRUCTURE ONLY.  plume_hd_master_batch*, plume_hd_derive_priv_batch* and plume_hd_derive_pub_batch* on the library's host side (capi_hd_* in csrc/plume_capi.hip +
-// csrc/plume_hd_capi.hip) on the mock HIP runtime, under the sanitizers (tests/test_hd_hostsim.py).
+// TEST INFRASTRUCTURE ONLY.  plume_hd_master_batch*, plume_hd_derive_priv_batch* and plume_hd_derive_pub_batch* on the library's host side (csrc/plume_hd_capi.hip) on the mock HIP runtime, under the sanitizers (tests/test_hd_hostsim.py).
 // usage: hd_driver VECTORS SEED.  VECTORS is written by the test from the Python restatement (tests/_hd.py): u32 n, u32 depth, u32 seed_len; n parent sk, n chain codes (32
 // bytes each), n x depth u32 indices, n parent pk (64 bytes), n x depth u32 indices of the public form, n seeds; then what the calls give, each as its arrays in ABI
 // order: private (sk, chain, pk, address, status), public (pk, chain, address, status), private with PLUME_HD_SHARED_PARENT (record 0), private with PLUME_HD_SHARED_PATH

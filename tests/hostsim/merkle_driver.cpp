@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE ONLY.  plume_merkle_* on the library's host side (capi_merkle_* in csrc/plume_capi.hip + csrc/plume_merkle_capi.hip) on the mock HIP runtime, under
+// TEST INFRASTRUCTURE ONLY.  plume_merkle_* on the library's host side (csrc/plume_merkle_capi.hip) on the mock HIP runtime, under
 // the sanitizers (tests/test_merkle_hostsim.py).
 // usage: merkle_driver VECTORS SEED.  VECTORS is written by the test from the Python restatement (tests/_merkle.py): u32 count, then per tree u32 leaf_format, addr_format,
 // sort, n, depth; the items, the amounts (format 2), the leaves, n leaf status bytes, the tree, leaf_pos, the proofs of the input items in depth slots, n proof lengths.

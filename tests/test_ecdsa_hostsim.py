@@ -1,4 +1,4 @@
-"""plume_ecdsa_recover_batch* on the host side (capi_ecdsa_recover / capi_ecdsa_recover_device in csrc/plume_capi.hip, csrc/plume_ecdsa_capi.hip) under the sanitizers, on
+"""plume_ecdsa_recover_batch* on the host side (csrc/plume_ecdsa_capi.hip) under the sanitizers, on
 the CPU: the unchanged objects of the existing host-side harness (tests/hostsim/Makefile: plume_capi.hip against the mock HIP runtime, the other kernels as host loops, the
 C oracle) linked with the ABI's translation unit, the three kernels as host loops (tests/hostsim/ecdsa_launch.cpp) and a driver (tests/hostsim/ecdsa_driver.cpp) that
 pins every output to vectors this test writes from the Python restatement (tests/_ecdsa.py) over the OpenSSL and crafted items of

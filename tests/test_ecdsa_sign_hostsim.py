@@ -1,5 +1,4 @@
-"""plume_ecdsa_sign_batch* and plume_eth_message_hash_batch* on the host side (capi_ecdsa_sign*, capi_eth_message_hash* in csrc/plume_capi.hip,
-csrc/plume_ecdsa_sign_capi.hip, csrc/plume_eth_hash_capi.hip) under the sanitizers, on the CPU: the unchanged objects of the existing host-side harness
+"""plume_ecdsa_sign_batch* and plume_eth_message_hash_batch* on the host side (csrc/plume_ecdsa_sign_capi.hip, csrc/plume_eth_hash_capi.hip) under the sanitizers, on the CPU: the unchanged objects of the existing host-side harness
 (tests/hostsim/Makefile: plume_capi.hip against the mock HIP runtime, the other kernels as host loops, the C oracle) linked with the two ABI translation units, the self-check's switch
 (csrc/plume_selfcheck_capi.hip, tests/hostsim/selfcheck_launch.cpp), the recover stages' launchers (tests/hostsim/ecdsa_launch.cpp: the self-check runs them), the new kernels as host loops (tests/hostsim/ecdsa_sign_launch.cpp) and a driver
 (tests/hostsim/ecdsa_sign_driver.cpp) that pins every output to vectors this test writes from the restatement (tests/_ecdsa_sign.py) over the whole fixture: the host form
@@ -34,7 +33,7 @@ def _build(out, san, launch_defs=()):
     subprocess.run(["make", "-C", str(HOSTSIM), f"OUT={out}", f"SAN={san}", "-j2", str(out / "capi.o"), str(out / "launch.o"), str(out / "oracle.o")],
                    check=True, capture_output=True, text=True, timeout=1200)
     flags = FLAGS + _san_flags(san)
-    units = [(["-x", "c++", "-O1", "-Werror"], CSRC / "plume_ecdsa_sign_capi.hip", "scapi.o"), (["-x", "c++", "-O1", "-Werror"], CSRC / "plume_eth_hash_capi.hip", "hcapi.o"),
+    units = [(["-x", "c++", "-O1", "-Werror"], CSRC / "plume_ecdsa_sign_capi.hip", "scapi.o"), (["-x", "c++", "-O1", "-Werror"], CSRC / "plume_ecdsa_capi.hip", "kcapi.o"), (["-x", "c++", "-O1", "-Werror"], CSRC / "plume_eth_hash_capi.hip", "hcapi.o"),
              (["-x", "c++", "-O1", "-Werror"], CSRC / "plume_selfcheck_capi.hip", "ccapi.o"), (["-O2", "-Werror"], HOSTSIM / "selfcheck_launch.cpp", "claunch.o"),
              (["-O2", "-Werror"], HOSTSIM / "ecdsa_launch.cpp", "rlaunch.o"), (["-O2", "-Werror", *launch_defs], HOSTSIM / "ecdsa_sign_launch.cpp", "slaunch.o"),
              (["-O1", "-Werror"], HOSTSIM / "ecdsa_sign_driver.cpp", "sdriver.o")]
@@ -43,7 +42,7 @@ def _build(out, san, launch_defs=()):
         _, err = p.communicate(timeout=900)
         assert p.returncode == 0, (src.name, err[-4000:])
     exe = out / "ecdsa_sign_driver"
-    subprocess.run(["g++", *_san_flags(san), "-o", str(exe), *[str(out / o) for o in ("capi.o", "launch.o", "oracle.o", "scapi.o", "hcapi.o", "ccapi.o", "claunch.o", "rlaunch.o", "slaunch.o", "sdriver.o")],
+    subprocess.run(["g++", *_san_flags(san), "-o", str(exe), *[str(out / o) for o in ("capi.o", "launch.o", "oracle.o", "scapi.o", "kcapi.o", "hcapi.o", "ccapi.o", "claunch.o", "rlaunch.o", "slaunch.o", "sdriver.o")],
                     "-lpthread"], check=True, capture_output=True, text=True, timeout=600)
     return exe
 

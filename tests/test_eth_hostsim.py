@@ -1,4 +1,4 @@
-"""plume_eth_address_batch* on the host side (capi_eth_address / capi_eth_address_device in csrc/plume_capi.hip, csrc/plume_eth_capi.hip) under the sanitizers, on the
+"""plume_eth_address_batch* on the host side (csrc/plume_eth_capi.hip) under the sanitizers, on the
 CPU: the unchanged objects of the existing host-side harness (tests/hostsim/Makefile: plume_capi.hip against the mock HIP runtime, the other kernels as host loops, the C
 oracle) linked with the ABI's translation unit, k_eth_address as a host loop (tests/hostsim/eth_launch.cpp) and a driver (tests/hostsim/eth_driver.cpp) that pins every
 output to vectors this test writes from the Python restatement (tests/_keccak.py): the host form with chunks smaller than n, plume_init_multi contexts over three and

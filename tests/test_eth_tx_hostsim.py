@@ -1,4 +1,4 @@
-"""plume_eth_tx_parse_batch* and plume_eth_tx_sender_batch* on the host side (capi_eth_tx_* in csrc/plume_capi.hip, csrc/plume_eth_tx_capi.hip) under the sanitizers, on
+"""plume_eth_tx_parse_batch* and plume_eth_tx_sender_batch* on the host side (csrc/plume_eth_tx_capi.hip) under the sanitizers, on
 the CPU: the unchanged objects of the existing host-side harness (tests/hostsim/Makefile: plume_capi.hip against the mock HIP runtime, the other kernels as host loops, the C
 oracle) linked with the ABI's translation unit, the recover stages' launchers (tests/hostsim/ecdsa_launch.cpp), k_eth_tx_parse as a host loop
 (tests/hostsim/eth_tx_launch.cpp) and a driver (tests/hostsim/eth_tx_driver.cpp) that pins every output to vectors this test writes from the restatements
@@ -34,14 +34,14 @@ def _build(out, san, launch_defs=()):
     subprocess.run(["make", "-C", str(HOSTSIM), f"OUT={out}", f"SAN={san}", "-j2", str(out / "capi.o"), str(out / "launch.o"), str(out / "oracle.o")],
                    check=True, capture_output=True, text=True, timeout=1200)
     flags = FLAGS + _san_flags(san)
-    units = [(["-x", "c++", "-O1", "-Werror"], CSRC / "plume_eth_tx_capi.hip", "tcapi.o"), (["-O2", "-Werror"], HOSTSIM / "ecdsa_launch.cpp", "rlaunch.o"),
+    units = [(["-x", "c++", "-O1", "-Werror"], CSRC / "plume_eth_tx_capi.hip", "tcapi.o"), (["-x", "c++", "-O1", "-Werror"], CSRC / "plume_ecdsa_capi.hip", "kcapi.o"), (["-O2", "-Werror"], HOSTSIM / "ecdsa_launch.cpp", "rlaunch.o"),
              (["-O2", "-Werror", *launch_defs], HOSTSIM / "eth_tx_launch.cpp", "tlaunch.o"), (["-O1", "-Werror"], HOSTSIM / "eth_tx_driver.cpp", "tdriver.o")]
     procs = [subprocess.Popen(["g++", *extra, *flags, "-c", str(src), "-o", str(out / obj)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for extra, src, obj in units]
     for p, (_, src, _) in zip(procs, units):
         _, err = p.communicate(timeout=900)
         assert p.returncode == 0, (src.name, err[-4000:])
     exe = out / "eth_tx_driver"
-    subprocess.run(["g++", *_san_flags(san), "-o", str(exe), *[str(out / o) for o in ("capi.o", "launch.o", "oracle.o", "tcapi.o", "rlaunch.o", "tlaunch.o", "tdriver.o")], "-lpthread"],
+    subprocess.run(["g++", *_san_flags(san), "-o", str(exe), *[str(out / o) for o in ("capi.o", "launch.o", "oracle.o", "tcapi.o", "kcapi.o", "rlaunch.o", "tlaunch.o", "tdriver.o")], "-lpthread"],
                    check=True, capture_output=True, text=True, timeout=600)
     return exe
 

@@ -1,4 +1,4 @@
-"""plume_eth_tx_sign_batch* on the host side (capi_eth_tx_sign* in csrc/plume_capi.hip, csrc/plume_eth_tx_sign_capi.hip) under the sanitizers, on the CPU: the unchanged
+"""plume_eth_tx_sign_batch* on the host side (csrc/plume_eth_tx_sign_capi.hip) under the sanitizers, on the CPU: the unchanged
 objects of the existing host-side harness (tests/hostsim/Makefile: plume_capi.hip against the mock HIP runtime, the other kernels as host loops, the C oracle) linked with
 the ABI's translation unit, the self-check's switch (csrc/plume_selfcheck_capi.hip, tests/hostsim/selfcheck_launch.cpp), the launchers of the sign and recover stages (tests/hostsim/ecdsa_sign_launch.cpp,
 ecdsa_launch.cpp), the two new kernels as host loops
@@ -37,7 +37,7 @@ def _build(out, san, launch_defs=()):
     subprocess.run(["make", "-C", str(HOSTSIM), f"OUT={out}", f"SAN={san}", "-j2", str(out / "capi.o"), str(out / "launch.o"), str(out / "oracle.o")],
                    check=True, capture_output=True, text=True, timeout=1200)
     flags = FLAGS + _san_flags(san)
-    units = [(["-x", "c++", "-O1", "-Werror"], CSRC / "plume_eth_tx_sign_capi.hip", "xcapi.o"), (["-O2", "-Werror"], HOSTSIM / "ecdsa_launch.cpp", "rlaunch.o"),
+    units = [(["-x", "c++", "-O1", "-Werror"], CSRC / "plume_eth_tx_sign_capi.hip", "xcapi.o"), (["-x", "c++", "-O1", "-Werror"], CSRC / "plume_ecdsa_sign_capi.hip", "scapi.o"), (["-x", "c++", "-O1", "-Werror"], CSRC / "plume_ecdsa_capi.hip", "kcapi.o"), (["-O2", "-Werror"], HOSTSIM / "ecdsa_launch.cpp", "rlaunch.o"),
              (["-O2", "-Werror"], HOSTSIM / "ecdsa_sign_launch.cpp", "slaunch.o"), (["-O2", "-Werror", *launch_defs], HOSTSIM / "eth_tx_sign_launch.cpp", "xlaunch.o"),
              (["-x", "c++", "-O1", "-Werror"], CSRC / "plume_selfcheck_capi.hip", "ccapi.o"), (["-O2", "-Werror"], HOSTSIM / "selfcheck_launch.cpp", "claunch.o"),
              (["-O1", "-Werror"], HOSTSIM / "eth_tx_sign_driver.cpp", "xdriver.o")]
@@ -46,7 +46,7 @@ def _build(out, san, launch_defs=()):
         _, err = p.communicate(timeout=900)
         assert p.returncode == 0, (src.name, err[-4000:])
     exe = out / "eth_tx_sign_driver"
-    subprocess.run(["g++", *_san_flags(san), "-o", str(exe), *[str(out / o) for o in ("capi.o", "launch.o", "oracle.o", "xcapi.o", "ccapi.o", "claunch.o", "rlaunch.o", "slaunch.o", "xlaunch.o", "xdriver.o")],
+    subprocess.run(["g++", *_san_flags(san), "-o", str(exe), *[str(out / o) for o in ("capi.o", "launch.o", "oracle.o", "xcapi.o", "scapi.o", "kcapi.o", "ccapi.o", "claunch.o", "rlaunch.o", "slaunch.o", "xlaunch.o", "xdriver.o")],
                     "-lpthread"], check=True, capture_output=True, text=True, timeout=600)
     return exe
 

@@ -1,4 +1,4 @@
-"""plume_hd_*_batch* on the host side (capi_hd_* in csrc/plume_capi.hip, csrc/plume_hd_capi.hip) under the sanitizers, on the CPU: the unchanged objects of the existing
+"""plume_hd_*_batch* on the host side (csrc/plume_hd_capi.hip) under the sanitizers, on the CPU: the unchanged objects of the existing
 host-side harness (tests/hostsim/Makefile: plume_capi.hip against the mock HIP runtime, the other kernels as host loops, the C oracle) linked with the ABI's translation
 unit, the new kernels as host loops (tests/hostsim/hd_launch.cpp) and a driver (tests/hostsim/hd_driver.cpp) that pins every output to vectors this test writes from the
 restatement (tests/_hd.py): the host form with chunks that cut the batch into 1, 2 and many pieces and on sub-ranges; both SHARED flags -- a whole-call input that was

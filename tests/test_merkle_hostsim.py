@@ -1,4 +1,4 @@
-"""plume_merkle_* on the host side (capi_merkle_* in csrc/plume_capi.hip, csrc/plume_merkle_capi.hip) under the sanitizers, on the CPU: the unchanged objects of the
+"""plume_merkle_* on the host side (csrc/plume_merkle_capi.hip) under the sanitizers, on the CPU: the unchanged objects of the
 existing host-side harness (tests/hostsim/Makefile: plume_capi.hip against the mock HIP runtime, the other kernels as host loops, the C oracle) linked with the ABI's
 translation unit, the Merkle kernels as host loops (tests/hostsim/merkle_launch.cpp) and a driver (tests/hostsim/merkle_driver.cpp) that pins every output to vectors this
 test writes from the restatement (tests/_merkle.py): the committed fixture's trees and one of 2 100 leaves (a stage of the sort in the workspace, per-depth launches under

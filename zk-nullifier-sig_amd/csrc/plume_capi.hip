@@ -27,16 +27,10 @@
 
 #include "../../include/plume_hip.h"
 #include "plume_agg_launch.h"
+#include "plume_capi_ctx.h"
 #include "plume_capi_internal.h"
-#include "plume_ecdsa.h"
-#include "plume_ecdsa_sign.h"
-#include "plume_eth_tx.h"
-#include "plume_eth_tx_sign.h"
-#include "plume_hd.h"
 #include "plume_host_logic.h"
-#include "plume_keccak.h"
 #include "plume_launch.h"
-#include "plume_merkle.h"
 #include "plume_nonce.h"
 #include "plume_recover.h"
 #include "plume_selfcheck.h"
@@ -44,74 +38,9 @@
 using namespace plume;
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e__ = (expr);                                                                                  \
-        if (e__ != hipSuccess) return fail(PLUME_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));    \
-    } while (0)
+int plume::fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 constexpr int kMaxSubBatches = 64;
-
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return fail(PLUME_ERR_HIP, std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e)); }
-        cap = want;
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() const { return (T*)p; }
-};
-
-// page-locked host scratch (hipHostMalloc): the source of uploads the library itself prepares.  A pageable source would make the runtime stage the copy and move it with a
-// blit KERNEL, which then queues behind the saturating multi-scalar kernel and stalls the upload stream (seen in the round-4 pipeline trace: tests/gpu_debug/e2e_trace.py)
-struct PinnedBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) { p = nullptr; return fail(PLUME_ERR_HIP, std::string("hipHostMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e)); }
-        cap = want;
-        return 0;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
-
-struct StageTimer {
-    std::vector<const char*> names;
-    std::vector<hipEvent_t> ev;   // ev[0] start, ev[i+1] after stage i
-    size_t used = 0;
-    uint64_t runs = 0;            // calls that started a timeline here, i.e. put work on this context (Route)
-    bool on = false;              // plume_set_stage_timing: a timing event between two kernels of a stream costs ~6 us of idle GPU (rocprofv3 trace of 2^16-item calls, round 5:
-                                  // kernels without an event between them follow each other within 0.2 us), five or six per call -- 2 % of a 2^16-item verify, so only on request
-    void begin(hipStream_t st) { runs++; names.clear(); used = 0; if (on) mark(st); }
-    void mark(hipStream_t st) {
-        if (used == ev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; ev.push_back(e); }
-        (void)hipEventRecord(ev[used++], st);
-    }
-    void stage(const char* name, hipStream_t st) { if (!on) return; names.push_back(name); mark(st); }
-    void destroy() { for (auto e : ev) (void)hipEventDestroy(e); ev.clear(); }
-};
-
-// staging for one piece of a host-pointer call
-struct HostSlot {
-    DevBuf msgs, off, in[6], out[8];
-    DevBuf ragged;                                                    // the ragged output of a serial call that has one (HostCall::ragged)
-    PinnedBuf relbuf;                                                 // piece-relative message offsets (source of an upload: lives until the slot is reused), page-locked
-    uint64_t* rel = nullptr;
-    hipEvent_t ready = nullptr, computed = nullptr, drained = nullptr;   // uploads landed / kernels finished / downloads landed
-    bool in_flight = false;
-};
 
 // one worker thread per shard of a multi-device context: it binds the shard's device once and then runs the jobs handed to it
 struct Worker {
@@ -125,84 +54,8 @@ struct Worker {
     std::string err;
 };
 
-// The generator's fixed tables (the verifier's 2^23-row window table, 1 GiB; the signer's comb, 252 MiB; 18 ms to build both) depend on nothing but G: every context of a
-// process on the same device shares ONE read-only copy, freed with the last context (a second batch in flight -- a second context -- then costs its workspace only).
-// Round 4: each table is built by the first call that needs it (need_gtab: verify, verify_non_zk; need_gcomb: sign, SEC1-DER export, the aggregate check), so a
-// verify-only process never holds the comb, a sign-only one never the 1 GiB window table, and plume_init itself allocates neither.
-struct FixedTables {
-    std::mutex m;                 // the tables of ONE device: their build (18 ms, synchronous) holds this lock, not the process-wide one -- the shards of a multi-device context
-                                  // build theirs side by side (the CPU pipeline harness showed eight shards' first call queueing behind one lock: tests/hostsim)
-    DevBuf gtab, gcomb, gscan;
-    int refs = 0;                 // under g_fixed_mutex
-    bool gtab_built = false, gcomb_built = false, gscan_built = false;
-};
 static std::mutex g_fixed_mutex;                 // the map and the reference counts.  Lock order: g_fixed_mutex, then a device's FixedTables::m
 static std::map<int, FixedTables> g_fixed;
-
-struct plume_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr, up = nullptr, down = nullptr;   // kernels / host->HBM / HBM->host
-    hipStream_t side = nullptr;                                   // aggregate check: the generator term and the upper windows' reduction run beside the main stream
-    hipStream_t pre = nullptr;                                    // overlapped verify / sign: the stages BEFORE the multi-scalar kernel of sub-batch k+1 run here, beside that kernel of sub-batch k
-    hipEvent_t pre_begin = nullptr;                               // ... the caller's stream has reached the call (inputs are there, the workspace is free)
-    std::vector<hipEvent_t> pre_ready;                            // ... sub-batch k's window tables are built
-    const char* last_msm_kernel = nullptr;                         // the multi-scalar kernel the last verify call on this context launched (plume_last_msm_kernel)
-    bool last_msm_sampled = false;                                 // ... and whether that launch sampled its clocks (plume_last_msm_clock: stage timing was on for the call)
-    std::vector<size_t> redo_counters;                            // word offsets (in `redo`) of the last verify call's redo counters, one per sub-batch (plume_last_redo_tasks)
-    int sub_batches = 1;                                          // device-resident verify / sign: number of sub-batches; 1 = strictly serial launch order (the default: measured on the MI355X, r03, kernels of two
-                                                                  // streams sharing the CUs cost MORE than the table kernel's idle issue slots give back -- 21.85 ms serial vs 22.1-22.4 ms for 2..16 sub-batches, LABNOTES.md §6)
-    size_t overlap_min = (size_t)1 << 17;                         // ... batches below this many items always run serial (a sub-batch must still fill the chip)
-    hipEvent_t agg_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // terms ready / upper bucket sums ready / generator term ready / upper windows reduced
-    hipEvent_t ws_free = nullptr;     // recorded behind the last kernel of every device-resident call: the next call's stream waits on it before it
-    bool ws_used = false;             // touches the per-context workspace, so calls on DIFFERENT streams of one context cannot race on that scratch
-    hipStream_t ws_stream = nullptr;  // the stream ws_free was last recorded on
-    size_t chunk = (size_t)1 << 20;
-    size_t host_piece = (size_t)1 << 19;                            // host-pointer calls: largest pipelined piece
-    size_t host_first_piece = (size_t)1 << 16;                      // ... the first piece (its upload is the only one no kernel hides); pieces then grow 3x per step
-    size_t host_tail_piece = (size_t)1 << 16;                       // ... the last piece of calls with large outputs (its download is the only one no kernel hides)
-    size_t host_register_min = 0;                                   // host-pointer calls: page-lock caller arrays of at least this many bytes for the call (0 = never)
-    // multi-device parent (plume_init_multi): the shards are complete single-device contexts, one worker thread each; a parent owns no GPU state
-    std::vector<plume_ctx*> shards;
-    std::vector<Worker*> workers;
-    HostSlot slot[4];                                              // host-pointer calls: staging slots (two for the one-lane pipeline, four when two lanes take the pieces in turn)
-    plume_ctx* host_lane = nullptr;                                // ... the second lane of the host-pointer pipeline: a complete single-device context (workspace, streams), created on first use
-    size_t msm_pair_max = (size_t)1 << 14;                          // verify calls (slices) of at most this many items run k_verify_msm_pair (env PLUME_MSM_PAIR_MAX; 0: never)
-    bool split_scalars = true;                                      // ... and the scalar stage in that kernel's idle role (env PLUME_SPLIT_SCALARS=0: a launch of its own, A/B)
-    size_t ingest_split_max = (size_t)1 << 16;                     // verify calls (slices) of at most this many items run the ingest stage with two lanes per item (latency-bound there)
-    int sign_uniform = 1;                                          // plume_set_sign_uniform: the signer's schedule (level 0, 1, 2).  Default 1 since round 5: no branch on a digit of sk or r
-                                                                   // (k256's multiplication is constant-time, rust-k256/src/randomizedsigner.rs:51-70; measured price +2.5 % per signature)
-    int host_lanes = 2;                                            // ... 1 = every piece on the context itself (rounds 1-3), 2 = pieces alternate between the context and host_lane
-    int host_sign_lanes = 2;                                       // ... the signer's host-pointer call: lanes it may use (env PLUME_HOST_SIGN_LANES).  2 since round 6, with uniform 2^16-item pieces (plume_host_logic.h)
-    bool host_lane_failed = false;                                 // ... the second lane could not be created once (out of memory): do not retry on every call
-    int jobs_per_lane = kTableJobsPerLane;
-    bool jobs_per_lane_forced = false;
-    FixedTables* fixed = nullptr;                                 // this device's shared generator tables (g_fixed)
-    // batches in flight (plume_set_in_flight): device-resident calls are dealt out in turn to this context and to `lanes`, complete single-device contexts of their own
-    // (workspace, streams, events; the fixed tables are shared), so that calls the caller issues on DIFFERENT streams run side by side instead of queueing for one workspace
-    std::vector<plume_ctx*> lanes;
-    size_t lane_next = 0;
-    size_t in_flight_min = 0;                                      // verify / sign calls of fewer items are not dealt out to the lanes (env PLUME_IN_FLIGHT_MIN; 0, the default: every call is)
-    plume_ctx* lane_last = nullptr;                               // the lane the last device-resident call went to (plume_last_stage_times, plume_last_redo_tasks)
-    DevBuf bases, jobflags, itemflags, tab, tabscr, res, resinf, res2, res2inf, pkaff, sink, redo, digs, eq1fall, eq1k, clk;
-    int sign_selfcheck = 0;                                        // plume_set_sign_selfcheck: 1 = every sign call stages its outputs here, verifies them and releases what verifies (sign_device)
-    DevBuf scstage;                                                // ... the staging: six records in the 64-byte form, the signer's status and the check's verdict, 322 B / item; wiped after the release
-    DevBuf txstage;                                                // plume_eth_tx_sender_batch: what k_eth_tx_parse hands the recover stages -- hash, r, s, v, 97 B / item (public data: not wiped)
-    DevBuf txsign;                                                 // plume_eth_tx_sign_batch: the framing (chain id, packed frame word), the signing hash and what the sign stages make of it -- 114 B / item; r, s, v and status wiped behind the assemble
-    DevBuf hdws;                                                   // plume_hd_derive_*_batch: k, the chain code and the status of every item between the levels, 65 B / item; wiped behind finish
-    DevBuf mrksort;                                                // plume_merkle_tree_build: the sort's records, nine word arrays of npad words, 36 B / padded leaf (public data: not wiped)
-    DevBuf nonce;                                                  // the derived-nonce signer: r of the call in flight, 32 B / item, wiped on the call's stream after sign_final
-    int eq1_short = 1;                                             // verify calls that give R: equation 1 in its short form (plume_eis.h).  0 = long form always (A/B), 2 = test: every item takes the fallback
-    size_t eq1_short_min = (size_t)1 << 16;                        // ... for calls of at least this many items.  Round 6 sweep on one box, interleaved (profiles/r06_eq1_threshold.txt), now that the
-                                                                   // scalar stage -- half-GCD included -- of calls up to 2^16 runs in role B of the two-role ingest kernel: 2^16 items 1.385 -> 1.343 ms
-                                                                   // (-3.0 %), 2^17 -4.4 %, 2^18 -4.1 %; 2^15 +6.3 % (0.928 -> 0.987: one wavefront per SIMD, the chain's latency is the
-                                                                   // kernel's time and equation 2's chain is the long one either way), <= 2^14 +35 % (the half chains of k_verify_msm_pair
-                                                                   // need the long form).  Round 5's threshold, before the scalar stage moved: 2^17
-    DevBuf dec[4], preflags;
-    DevBuf agg[15];      // aggregate check (plume_aggregate.h): haff, scal, flags, gs, hash_ok, counters, count, sort tiles, sorted, bsum, bsuminf, red, redinf, ssum, perm + its histogram
-    DevBuf agg_record;   // the running record of a host-pointer aggregate call (pieces of one batch)
-    DevBuf dslots, dminid, dmyslot, dcount, dblockcnt;   // nullifier-set post-processing (plume_dedup.h)   // SEC1 ingest: decompressed 64-byte records + per-item reject flags
-    StageTimer timer;
-};
 
 // Every per-context tunable a derived context (an in-flight lane, the host pipeline's second lane, a shard) has to share with the context it serves: ONE place, so that a new
 // knob cannot reach some derived contexts and miss others (round 4's host lane did not inherit sign_uniform: VERDICT r4).
@@ -221,44 +74,15 @@ static void propagate_tunables(plume_ctx* ctx) {
     if (ctx->host_lane) { inherit_tunables(ctx->host_lane, ctx); ctx->host_lane->sub_batches = 1; }   // the pieces of a host-pointer call are never cut again
 }
 
-static int bind(plume_ctx* ctx) {
+int plume::bind(plume_ctx* ctx) {
     if (!ctx) return fail(PLUME_ERR_ARG, "null context");
     if (!ctx->shards.empty()) return fail(PLUME_ERR_ARG, "device-resident entry points need a single-device context (plume_init): device pointers belong to one GPU");
     HIPCHK(hipSetDevice(ctx->device));
     return 0;
 }
-// The lane a device-resident call runs on -- the context itself, or one of its in-flight lanes in turn -- and the stream it runs on.  The stream is resolved against the
-// context the CALLER holds before the call is dealt out: NULL means "that context's own stream" whichever lane serves the call, so successive NULL-stream calls stay
-// ordered against each other (a sign followed by a verify of its outputs) exactly as they are without lanes.  (Round 3 resolved NULL after routing, i.e. to the lane's
-// private stream, which changes from call to call: ADVICE r3.)  A lane's workspace is guarded by its ws_free event, so running it on a stream it does not own is safe.
-struct Route {
-    plume_ctx* held;           // the context the caller holds
-    plume_ctx* lane;           // the lane that serves this call
-    hipStream_t st;
-    size_t next0 = 0;
-    plume_ctx* last0 = nullptr;
-    uint64_t epoch0 = 0;
-    Route(plume_ctx* ctx, void* stream, size_t n = (size_t)-1) : held(ctx), lane(ctx) {
-        st = stream ? (hipStream_t)stream : (ctx ? ctx->stream : nullptr);
-        if (!ctx) return;
-        next0 = ctx->lane_next; last0 = ctx->lane_last;
-        if (!ctx->lanes.empty() && n >= ctx->in_flight_min) {                 // (a small call stays on the first lane: plume_set_in_flight)
-            const size_t k = ctx->lanes.size() + 1, i = ctx->lane_next++ % k;
-            lane = i == 0 ? ctx : ctx->lanes[i - 1];
-        }
-        ctx->lane_last = lane;
-        epoch0 = lane->timer.runs;
-    }
-    Route(const Route&) = delete;
-    Route& operator=(const Route&) = delete;
-    // A call that is refused before it starts its lane's stage timeline (an argument check, n above the chunk size, an empty batch) never happened as far as the lanes are concerned:
-    // it neither takes a turn nor becomes "the last device-resident call" that plume_last_stage_times / plume_last_redo_tasks report.  (Found by the CPU pipeline harness,
-    // tests/hostsim: a refused call moved lane_last to a lane that had run nothing, and the stage times read afterwards -- and the wait they imply -- were another call's.)
-    ~Route() { if (held && lane->timer.runs == epoch0) { held->lane_next = next0; held->lane_last = last0; } }
-};
 // Workspace ordering for the device-resident entry points: every call leaves ws_free behind its last kernel, and the next call's stream
 // waits on it first.  Calls on one stream are ordered anyway; this makes calls on DIFFERENT streams of one context safe too.
-static int ws_acquire(plume_ctx* ctx, hipStream_t st) {
+int plume::ws_acquire(plume_ctx* ctx, hipStream_t st) {
     // (the previous call on the SAME stream is ordered by the stream itself: no wait packet between two calls of a stream of small calls -- each one is a few us of idle GPU)
     // The comparison is of stream HANDLES: a caller who destroys a stream and gets the same handle value back for a new one while this context's last call on the old
     // one is still running would skip a wait it needs.  The header therefore asks that a caller-provided stream stay alive until the context's last call on it has
@@ -272,25 +96,7 @@ static int ws_release(plume_ctx* ctx, hipStream_t st) {
     ctx->ws_stream = st;
     return 0;
 }
-// Holds the workspace from a successful ws_acquire to the end of the call.  A call that fails half way (an allocation, a launch) must still leave ws_free behind
-// whatever it has already enqueued -- on the caller's stream and on the context's side stream -- or the next call, on another stream, would run into it.
-struct WsHold {
-    plume_ctx* ctx;
-    hipStream_t st;
-    bool released = false;
-    WsHold(plume_ctx* c, hipStream_t s) : ctx(c), st(s) {}
-    WsHold(const WsHold&) = delete;
-    WsHold& operator=(const WsHold&) = delete;
-    int release() { released = true; return ws_release(ctx, st); }
-    ~WsHold() {
-        if (released) return;
-        if (ctx->side) (void)hipStreamSynchronize(ctx->side);      // failure path only: side-stream work the caller's stream never joined
-        if (ctx->pre) (void)hipStreamSynchronize(ctx->pre);
-        (void)hipEventRecord(ctx->ws_free, st);
-        ctx->ws_used = true;
-        ctx->ws_stream = st;
-    }
-};
+int WsHold::release() { released = true; return ws_release(ctx, st); }
 
 extern "C" const char* plume_last_error(void) { return g_err.c_str(); }
 #ifndef PLUME_BUILD_ID
@@ -418,9 +224,9 @@ static int need_fixed(plume_ctx* ctx, bool gtab, bool gcomb, bool gscan = false)
     return 0;
 }
 static int need_gtab(plume_ctx* ctx) { return need_fixed(ctx, true, false); }
-static int need_gcomb(plume_ctx* ctx) { return need_fixed(ctx, false, true); }
+int plume::need_gcomb(plume_ctx* ctx) { return need_fixed(ctx, false, true); }
 // the signer's (and the SEC1-DER export's) table of G: the comb, or at level 2 of the uniform schedule the small scanned table
-static int need_sign_tables(plume_ctx* ctx) { return ctx->sign_uniform == 2 ? need_fixed(ctx, false, false, true) : need_gcomb(ctx); }
+int plume::need_sign_tables(plume_ctx* ctx) { return ctx->sign_uniform == 2 ? need_fixed(ctx, false, false, true) : need_gcomb(ctx); }
 
 static int check_device(int device_id) {
     if (device_id < 0) return fail(PLUME_ERR_ARG, "negative device id");
@@ -763,8 +569,8 @@ static int pick_jobs_per_lane(const plume_ctx* ctx, size_t njobs, bool kinds_of_
 
 // nthrees: how many of the jobs, from the front, come as (pk, H, nullifier) triples (the verifier: 3 per item; its short first equation appends one more job per item behind
 // them; the signer: 0): the jobs per lane are then a multiple of three, so that the kinds line up across a wavefront (affine and Jacobian bases take different paths).
-static size_t table_stage_scratch(const plume_ctx* ctx, size_t njobs, size_t nthrees) { return tables_scratch_bytes(njobs, pick_jobs_per_lane(ctx, njobs, nthrees != 0)); }
-static void table_stage(plume_ctx* ctx, uint32_t* tab, const uint32_t* bases, const uint8_t* jobflags, size_t njobs, size_t nthrees, hipStream_t st) {
+size_t plume::table_stage_scratch(const plume_ctx* ctx, size_t njobs, size_t nthrees) { return tables_scratch_bytes(njobs, pick_jobs_per_lane(ctx, njobs, nthrees != 0)); }
+void plume::table_stage(plume_ctx* ctx, uint32_t* tab, const uint32_t* bases, const uint8_t* jobflags, size_t njobs, size_t nthrees, hipStream_t st) {
     launch_tables(tab, bases, jobflags, njobs, pick_jobs_per_lane(ctx, njobs, nthrees != 0), ctx->tabscr.as<uint32_t>(), st);
 }
 
@@ -773,7 +579,7 @@ static void table_stage(plume_ctx* ctx, uint32_t* tab, const uint32_t* bases, co
 // k+1 run on ctx->pre beside the multi-scalar kernel of sub-batch k on the caller's stream.  The multi-scalar kernel saturates the vector ALUs but leaves HBM idle, the
 // table kernel is bound by the critical path of its workgroups and leaves half of the issue slots idle (LABNOTES.md §5): side by side they fill each other's gaps, one
 // after the other they cannot.  Slices are multiples of 1024 items (whole workgroups, aligned records).  One sub-batch = the strictly serial order.
-static std::vector<size_t> sub_batch_bounds(const plume_ctx* ctx, size_t n) { return plume_host::sub_batch_bounds(n, ctx->sub_batches, ctx->overlap_min); }
+std::vector<size_t> plume::sub_batch_bounds(const plume_ctx* ctx, size_t n) { return plume_host::sub_batch_bounds(n, ctx->sub_batches, ctx->overlap_min); }
 static int pre_events(plume_ctx* ctx, size_t k) {
     while (ctx->pre_ready.size() < k) {
         hipEvent_t e;
@@ -1490,35 +1296,6 @@ static int host_pipeline(plume_ctx* ctx, size_t n, bool out_heavy, Up up, Run ru
     return rc;
 }
 
-// One host-pointer call, stated once: the caller's arrays in the order of HostSlot::in[k] / out[k].  Registration, the page-lock check for two lanes, the copies and
-// the shard offsets are all read off this table, so they cannot disagree (round 4's page-lock check listed its arrays by hand and missed some: ADVICE r4).
-struct HostArray {
-    const void* p = nullptr;   // the caller's array; null: not given
-    size_t stride = 0;         // bytes per item; 0 = unused entry
-    bool secret = false;       // the staged copy is wiped once it has served: an input behind the kernels that read it, an output (serial calls only) behind its download
-    bool whole = false;        // serial calls only: `stride` bytes in all, not per item.  An input is given once for the call: uploaded in front of the first piece, not advanced by shard()
-};
-struct HostCall {
-    const uint8_t* msgs;       // may be null when the offsets give it no bytes
-    const uint64_t* msg_off;   // null (serial calls only): the call has no messages and stages none
-    HostArray in[6], out[8];
-    bool out_heavy = false, may_use_two_lanes = false;
-    const char *off_name = "msg_off", *msgs_name = "message";         // what the argument errors of the message staging call the two
-    // serial calls only: a ragged output tied to the messages.  Item i owns the ragged_growth i + (msg_off[i] - msg_off[0]) .. bytes of it, its message's length plus
-    // ragged_growth of them; a piece's share is contiguous, staged in HostSlot::ragged and downloaded in one copy behind the fixed-stride outputs
-    void* ragged = nullptr;
-    size_t ragged_growth = 0;
-    size_t ragged_at(size_t i) const { return (size_t)(msg_off[i] - msg_off[0]) + ragged_growth * i; }
-    // items [lo, ...) of the same call: msg_off keeps the caller's absolute offsets into the same msgs buffer
-    HostCall shard(size_t lo) const {
-        HostCall c = *this;
-        if (c.ragged) c.ragged = (uint8_t*)c.ragged + ragged_at(lo);
-        if (c.msg_off) c.msg_off += lo;
-        for (HostArray& a : c.in) if (a.p && !a.whole) a.p = (const uint8_t*)a.p + a.stride * lo;
-        for (HostArray& a : c.out) if (a.p && !a.whole) a.p = (const uint8_t*)a.p + a.stride * lo;
-        return c;
-    }
-};
 // the messages of items [i0, i0 + cnt): their offsets rebased to the piece (page-locked, sl.rel) and the piece's bytes, uploaded through the slot on `st`.  sl.rel[cnt]: the bytes
 static int stage_msgs(const HostCall& call, HostSlot& sl, size_t i0, size_t cnt, hipStream_t st) {
     if (sl.relbuf.ensure((cnt + 1) * 8)) return PLUME_ERR_HIP;
@@ -1670,6 +1447,11 @@ static int serial_host_call_any(plume_ctx* ctx, size_t n, const HostCall& call, 
     if (ctx->shards.empty()) return serial_host_call(ctx, n, call, run);
     return for_shards(ctx, n, [&](plume_ctx* sh, size_t lo, size_t hi) -> int { return serial_host_call(sh, hi - lo, call.shard(lo), run); });
 }
+// the same four for the call families' own files (plume_capi_ctx.h)
+int plume::host_call_any(plume_ctx* ctx, size_t n, const HostCall& call, HostRun run) { return ::host_call_any(ctx, n, call, run); }
+int plume::serial_host_piece(plume_ctx* ctx, const HostCall& call, size_t i0, size_t cnt, HostRun run) { return ::serial_host_piece(ctx, call, i0, cnt, run); }
+int plume::serial_host_call(plume_ctx* ctx, size_t n, const HostCall& call, HostRun run) { return ::serial_host_call(ctx, n, call, run); }
+int plume::serial_host_call_any(plume_ctx* ctx, size_t n, const HostCall& call, HostRun run) { return ::serial_host_call_any(ctx, n, call, run); }
 
 // the first-occurrence flags over host arrays: one piece whatever the chunk size is (every record has to be resident to be compared)
 extern "C" int plume_nullifier_first_occurrence(plume_ctx* ctx, size_t n, const uint8_t* nullifier, const uint8_t* live, const uint64_t* ids, uint8_t* first,
@@ -1888,695 +1670,6 @@ extern "C" int plume_scalars_to_sec1_der_batch(plume_ctx* ctx, size_t n, const u
     const HostCall call{nullptr, nullptr, {{scalars, 32, true}}, {{der109, PLUME_DER_LEN, true}, {status, 1}}};
     return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
         return der_device(on, cnt, sl.in[0].as<uint8_t>(), sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), on->stream);
-    });
-}
-// The Ethereum-address call (plume_capi_internal.h): the ABI and the launcher live in plume_eth_capi.hip.  No table is needed and no workspace is touched -- the kernel
-// reads and writes the caller's arrays only -- so the call neither builds anything nor joins the ws_free chain.
-static int eth_args_ok(int pk_format, int addr_format, size_t n, const void* pk, const void* address, const void* status, EthLaunch fn) {
-    if (pk_format != PLUME_ETHK_PK_AFFINE64 && pk_format != PLUME_ETHK_PK_SEC1) return fail(PLUME_ERR_ARG, "pk_format must be 0 or 1");
-    if (addr_format != PLUME_ETHK_ADDR_RAW20 && addr_format != PLUME_ETHK_ADDR_RECORD64 && addr_format != PLUME_ETHK_ADDR_EIP55) return fail(PLUME_ERR_ARG, "addr_format must be 0, 1 or 2");
-    if (!fn) return fail(PLUME_ERR_ARG, "the address kernel is not part of this build");
-    if (n && !pk) return fail(PLUME_ERR_ARG, "null array");
-    if (n && !address && !status) return fail(PLUME_ERR_ARG, "no output array");
-    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
-    return 0;
-}
-static int eth_device(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status, hipStream_t st,
-                      EthLaunch fn) {
-    if (n == 0) return 0;
-    EthArgs a; a.pk_format = pk_format; a.addr_format = addr_format; a.n = (uint32_t)n; a.pk = pk; a.expect = expect; a.address = address; a.status = status;
-    ctx->timer.begin(st);
-    fn(a, st); ctx->timer.stage("eth_address", st);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int plume::capi_eth_address_device(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status,
-                                   void* stream, EthLaunch eth_fn) {
-    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = eth_args_ok(pk_format, addr_format, n, pk, address, status, eth_fn)) return rc;
-    return eth_device(ctx, pk_format, addr_format, n, pk, expect, address, status, st_, eth_fn);
-}
-int plume::capi_eth_address(plume_ctx* ctx, int pk_format, int addr_format, size_t n, const uint8_t* pk, const uint8_t* expect, uint8_t* address, uint8_t* status,
-                            EthLaunch eth_fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = eth_args_ok(pk_format, addr_format, n, pk, address, status, eth_fn)) return rc;
-    const HostCall call{nullptr, nullptr, {{pk, eth_pk_width(pk_format)}, {expect, 20}}, {{address, eth_address_width(addr_format)}, {status, 1}}};
-    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return eth_device(on, pk_format, addr_format, cnt, sl.in[0].as<uint8_t>(), expect ? sl.in[1].as<uint8_t>() : nullptr, address ? sl.out[0].as<uint8_t>() : nullptr,
-                          status ? sl.out[1].as<uint8_t>() : nullptr, on->stream, eth_fn);
-    });
-}
-// The ECDSA recovery (plume_capi_internal.h): the ABI and the launchers live in plume_ecdsa_capi.hip.  The comb of G is the only fixed table (never the 1 GiB window table);
-// the workspace is the verifier's own buffers, one table job per item, so the device form joins the ws_free chain.  plume_set_sub_batches cuts the call as it cuts a verify
-// call (sub_batch_bounds); the slices follow one another on the caller's stream.
-static int ecdsa_args_ok(int flags, int pk_format, int addr_format, size_t n, const void* hash, const void* r, const void* s, const void* v, const void* pk, const void* address,
-                         const void* status, const EcdsaLaunch* fn) {
-    if (flags & ~PLUME_ECDSAK_LOW_S) return fail(PLUME_ERR_ARG, "unknown flag bits");
-    if (pk_format != PLUME_ETHK_PK_AFFINE64 && pk_format != PLUME_ETHK_PK_SEC1) return fail(PLUME_ERR_ARG, "pk_format must be 0 or 1");
-    if (addr_format != PLUME_ETHK_ADDR_RAW20 && addr_format != PLUME_ETHK_ADDR_RECORD64 && addr_format != PLUME_ETHK_ADDR_EIP55) return fail(PLUME_ERR_ARG, "addr_format must be 0, 1 or 2");
-    if (!fn || !fn->prepare || !fn->mul || !fn->finalize) return fail(PLUME_ERR_ARG, "the ECDSA recovery kernels are not part of this build");
-    if (n && (!hash || !r || !s || !v)) return fail(PLUME_ERR_ARG, "null array");
-    if (n && !pk && !address && !status) return fail(PLUME_ERR_ARG, "no output array");
-    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
-    return 0;
-}
-static int ecdsa_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s, const uint8_t* v,
-                        const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, hipStream_t st, const EcdsaLaunch* fn, bool continue_timer = false) {
-    if (n == 0) return 0;
-    if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
-    if (int rc = need_gcomb(ctx)) return rc;
-    if (!continue_timer) { if (int rc = ws_acquire(ctx, st)) return rc; }     // continue_timer: the caller (the ECDSA signer's self-check) holds the workspace already
-    std::unique_ptr<WsHold> hold(continue_timer ? nullptr : new WsHold(ctx, st));
-    const std::vector<size_t> cut = sub_batch_bounds(ctx, n);
-    const size_t nsub = cut.size() - 1;
-    size_t scr_bytes = 0;
-    for (size_t k = 0; k < nsub; k++) scr_bytes = std::max(scr_bytes, table_stage_scratch(ctx, cut[k + 1] - cut[k], 0));
-    if (ctx->bases.ensure((size_t)PLUME_BASE_WORDS * 4 * n) || ctx->jobflags.ensure(n) || ctx->itemflags.ensure(n) || ctx->tab.ensure((size_t)PLUME_TAB_WORDS * 4 * n) ||
-        ctx->tabscr.ensure(scr_bytes) || ctx->res.ensure((size_t)PLUME_JAC_WORDS * 4 * n) || ctx->resinf.ensure(n) || ctx->redo.ensure((n + nsub) * 4) ||
-        ctx->digs.ensure((size_t)PLUME_NPOS * n) || ctx->eq1k.ensure(32 * n))
-        return PLUME_ERR_HIP;
-    const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
-    StageTimer& t = ctx->timer;
-    if (!continue_timer) t.begin(st);
-    for (size_t k = 0; k < nsub; k++) {
-        const size_t lo = cut[k], cnt = cut[k + 1] - cut[k];
-        EcdsaArgs a;                                                          // the slice [lo, lo + cnt) as a batch of its own: every array and every scratch region starts at the slice
-        memset(&a, 0, sizeof a);
-        a.flags = flags; a.pk_format = pk_format; a.addr_format = addr_format; a.n = (uint32_t)cnt;
-        a.hash = hash + 32 * lo; a.r = r + 32 * lo; a.s = s + 32 * lo; a.v = v + lo; a.expect = expect ? expect + 20 * lo : nullptr;
-        a.pk = pk ? pk + P * lo : nullptr; a.address = address ? address + W * lo : nullptr; a.status = status ? status + lo : nullptr;
-        a.bases = ctx->bases.as<uint32_t>() + (size_t)PLUME_BASE_WORDS * lo; a.jobflags = ctx->jobflags.as<uint8_t>() + lo; a.itemflags = ctx->itemflags.as<uint8_t>() + lo;
-        a.tab = ctx->tab.as<uint32_t>() + (size_t)PLUME_TAB_WORDS * lo; a.digs = ctx->digs.as<int8_t>() + (size_t)PLUME_NPOS * lo; a.u1 = ctx->eq1k.as<uint32_t>() + 8 * lo;
-        a.res = ctx->res.as<uint32_t>() + (size_t)PLUME_JAC_WORDS * lo; a.resinf = ctx->resinf.as<uint8_t>() + lo;
-        a.redo = ctx->redo.as<uint32_t>() + lo + k;                          // the slice's redo list: counter + up to cnt items
-        a.gcomb = ctx->fixed->gcomb.as<uint32_t>();
-        fn->prepare(a, st); t.stage("ecdsa_prepare", st);
-        table_stage(ctx, a.tab, a.bases, a.jobflags, cnt, 0, st); t.stage("tables", st);
-        fn->mul(a, st); t.stage("ecdsa_mul", st);
-        launch_normalize(a.res, a.resinf, cnt, st); t.stage("to_affine", st);
-        fn->finalize(a, st); t.stage("ecdsa_finalize", st);
-    }
-    HIPCHK(hipGetLastError());
-    return hold ? hold->release() : 0;
-}
-int plume::capi_ecdsa_recover_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s,
-                                     const uint8_t* v, const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, void* stream, const EcdsaLaunch* fn) {
-    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = ecdsa_args_ok(flags, pk_format, addr_format, n, hash, r, s, v, pk, address, status, fn)) return rc;
-    return ecdsa_device(ctx, flags, pk_format, addr_format, n, hash, r, s, v, expect, pk, address, status, st_, fn);
-}
-int plume::capi_ecdsa_recover(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* hash, const uint8_t* r, const uint8_t* s, const uint8_t* v,
-                              const uint8_t* expect, uint8_t* pk, uint8_t* address, uint8_t* status, const EcdsaLaunch* fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = ecdsa_args_ok(flags, pk_format, addr_format, n, hash, r, s, v, pk, address, status, fn)) return rc;
-    const HostCall call{nullptr, nullptr, {{hash, 32}, {r, 32}, {s, 32}, {v, 1}, {expect, 20}}, {{pk, eth_pk_width(pk_format)}, {address, eth_address_width(addr_format)}, {status, 1}}};
-    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return ecdsa_device(on, flags, pk_format, addr_format, cnt, sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(), sl.in[2].as<uint8_t>(), sl.in[3].as<uint8_t>(),
-                            expect ? sl.in[4].as<uint8_t>() : nullptr, pk ? sl.out[0].as<uint8_t>() : nullptr, address ? sl.out[1].as<uint8_t>() : nullptr,
-                            status ? sl.out[2].as<uint8_t>() : nullptr, on->stream, fn);
-    });
-}
-// The message-hash call (plume_capi_internal.h): the ABI lives in plume_eth_hash_capi.hip, the launcher beside the address kernel's.  Like the address call it needs no table and touches no workspace.
-static int eth_hash_args_ok(int mode, size_t n, const void* off, const void* hash, EthHashLaunch fn) {
-    if (mode != PLUME_ETHK_HASH_KECCAK256 && mode != PLUME_ETHK_HASH_EIP191) return fail(PLUME_ERR_ARG, "mode must be 0 or 1");
-    if (!fn) return fail(PLUME_ERR_ARG, "the message-hash kernel is not part of this build");
-    if (n && (!off || !hash)) return fail(PLUME_ERR_ARG, "null array");
-    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
-    return 0;
-}
-static int eth_hash_device(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, uint8_t* hash, hipStream_t st, EthHashLaunch fn) {
-    if (n == 0) return 0;
-    if (!msgs && msgs_bytes) return fail(PLUME_ERR_ARG, "null message buffer");
-    EthHashArgs a; a.mode = mode; a.n = (uint32_t)n; a.msgs = msgs; a.msg_off = msg_off; a.msgs_bytes = msgs ? msgs_bytes : 0; a.hash = hash;
-    ctx->timer.begin(st);
-    fn(a, st); ctx->timer.stage("eth_message_hash", st);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int plume::capi_eth_message_hash_device(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, size_t msgs_bytes, uint8_t* hash32, void* stream,
-                                        EthHashLaunch hash_fn) {
-    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = eth_hash_args_ok(mode, n, msg_off, hash32, hash_fn)) return rc;
-    return eth_hash_device(ctx, mode, n, msgs, msg_off, msgs_bytes, hash32, st_, hash_fn);
-}
-int plume::capi_eth_message_hash(plume_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint64_t* msg_off, uint8_t* hash32, EthHashLaunch hash_fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = eth_hash_args_ok(mode, n, msg_off, hash32, hash_fn)) return rc;
-    const HostCall call{msgs, msg_off, {}, {{hash32, 32}}};
-    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return eth_hash_device(on, mode, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.out[0].as<uint8_t>(), on->stream, hash_fn);
-    });
-}
-// The transaction calls (plume_capi_internal.h): the ABI and the launcher live in plume_eth_tx_capi.hip.  parse is the message-hash call with more outputs: no table, no
-// workspace.  sender runs the same kernel into ctx->txstage and the recover stages (ecdsa_device, on this workspace and this stream) on what it staged, so it holds the
-// workspace from in front of the parse to behind finalize.
-static int eth_tx_parse_args_ok(size_t n, const void* off, const void* hash, const void* r, const void* s, const void* v, EthTxLaunch fn) {
-    if (!fn) return fail(PLUME_ERR_ARG, "the transaction kernel is not part of this build");
-    if (n && (!off || !hash || !r || !s || !v)) return fail(PLUME_ERR_ARG, "null array");
-    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
-    return 0;
-}
-static EthTxArgs eth_tx_args(size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, uint8_t* hash, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
-                             uint8_t* tx_type, uint8_t* status) {
-    EthTxArgs a; a.n = (uint32_t)n; a.txs = txs; a.tx_off = tx_off; a.txs_bytes = txs ? txs_bytes : 0; a.hash = hash; a.r = r; a.s = s; a.v = v; a.chain_id = chain_id;
-    a.tx_type = tx_type; a.status = status;
-    return a;
-}
-static int eth_tx_parse_device(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, uint8_t* hash, uint8_t* r, uint8_t* s, uint8_t* v,
-                               uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, hipStream_t st, EthTxLaunch fn) {
-    if (n == 0) return 0;
-    if (!txs && txs_bytes) return fail(PLUME_ERR_ARG, "null transaction buffer");
-    ctx->timer.begin(st);
-    fn(eth_tx_args(n, txs, tx_off, txs_bytes, hash, r, s, v, chain_id, tx_type, status), st); ctx->timer.stage("eth_tx_parse", st);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int plume::capi_eth_tx_parse_device(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v,
-                                    uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream, EthTxLaunch tx_fn) {
-    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = eth_tx_parse_args_ok(n, tx_off, hash32, r, s, v, tx_fn)) return rc;
-    return eth_tx_parse_device(ctx, n, txs, tx_off, txs_bytes, hash32, r, s, v, chain_id, tx_type, status, st_, tx_fn);
-}
-// the host-pointer forms stage their bytes as a message-hash call does; the argument errors speak of transactions
-static HostCall eth_tx_call(const HostCall& call) { HostCall c = call; c.off_name = "tx_off"; c.msgs_name = "transaction"; return c; }
-int plume::capi_eth_tx_parse(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
-                             uint8_t* tx_type, uint8_t* status, EthTxLaunch tx_fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = eth_tx_parse_args_ok(n, tx_off, hash32, r, s, v, tx_fn)) return rc;
-    const HostCall call = eth_tx_call({txs, tx_off, {}, {{hash32, 32}, {r, 32}, {s, 32}, {v, 1}, {chain_id, 8}, {tx_type, 1}, {status, 1}}});
-    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return eth_tx_parse_device(on, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(),
-                                   sl.out[3].as<uint8_t>(), chain_id ? sl.out[4].as<uint64_t>() : nullptr, tx_type ? sl.out[5].as<uint8_t>() : nullptr,
-                                   status ? sl.out[6].as<uint8_t>() : nullptr, on->stream, tx_fn);
-    });
-}
-static int eth_tx_sender_args_ok(int flags, int pk_format, int addr_format, size_t n, const void* off, const void* pk, const void* address, const void* status,
-                                 EthTxLaunch tx_fn, const EcdsaLaunch* fn) {
-    if (!tx_fn) return fail(PLUME_ERR_ARG, "the transaction kernel is not part of this build");
-    if (n && !off) return fail(PLUME_ERR_ARG, "null array");
-    const uint8_t one = 0;                                                      // (hash, r, s, v are the staging's: any non-null pointer passes the recovery's own check)
-    return ecdsa_args_ok(flags, pk_format, addr_format, n, &one, &one, &one, &one, pk, address, status, fn);
-}
-static int eth_tx_sender_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes,
-                                const uint8_t* expect, uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, hipStream_t st, EthTxLaunch tx_fn,
-                                const EcdsaLaunch* fn) {
-    if (n == 0) return 0;
-    if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
-    if (!txs && txs_bytes) return fail(PLUME_ERR_ARG, "null transaction buffer");
-    if (int rc = need_gcomb(ctx)) return rc;                                    // the recover stages' table, built before anything is queued
-    if (int rc = ws_acquire(ctx, st)) return rc;
-    WsHold hold(ctx, st);
-    if (ctx->txstage.ensure(97 * n)) return PLUME_ERR_HIP;
-    uint8_t* const stg = ctx->txstage.as<uint8_t>();
-    uint8_t *const g_hash = stg, *const g_r = stg + 32 * n, *const g_s = stg + 64 * n, *const g_v = stg + 96 * n;
-    ctx->timer.begin(st);
-    tx_fn(eth_tx_args(n, txs, tx_off, txs_bytes, g_hash, g_r, g_s, g_v, chain_id, tx_type, nullptr), st); ctx->timer.stage("eth_tx_parse", st);
-    HIPCHK(hipGetLastError());
-    if (int rc = ecdsa_device(ctx, flags, pk_format, addr_format, n, g_hash, g_r, g_s, g_v, expect, pk, address, status, st, fn, true)) return rc;
-    return hold.release();
-}
-int plume::capi_eth_tx_sender_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes,
-                                     const uint8_t* expect, uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, void* stream,
-                                     EthTxLaunch tx_fn, const EcdsaLaunch* fn) {
-    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = eth_tx_sender_args_ok(flags, pk_format, addr_format, n, tx_off, pk, address, status, tx_fn, fn)) return rc;
-    return eth_tx_sender_device(ctx, flags, pk_format, addr_format, n, txs, tx_off, txs_bytes, expect, pk, address, chain_id, tx_type, status, st_, tx_fn, fn);
-}
-int plume::capi_eth_tx_sender(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* txs, const uint64_t* tx_off, const uint8_t* expect,
-                              uint8_t* pk, uint8_t* address, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status, EthTxLaunch tx_fn, const EcdsaLaunch* fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = eth_tx_sender_args_ok(flags, pk_format, addr_format, n, tx_off, pk, address, status, tx_fn, fn)) return rc;
-    const HostCall call = eth_tx_call({txs, tx_off, {{expect, 20}},
-                                       {{pk, eth_pk_width(pk_format)}, {address, eth_address_width(addr_format)}, {status, 1}, {chain_id, 8}, {tx_type, 1}}});
-    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return eth_tx_sender_device(on, flags, pk_format, addr_format, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], expect ? sl.in[0].as<uint8_t>() : nullptr,
-                                    pk ? sl.out[0].as<uint8_t>() : nullptr, address ? sl.out[1].as<uint8_t>() : nullptr, chain_id ? sl.out[3].as<uint64_t>() : nullptr,
-                                    tx_type ? sl.out[4].as<uint8_t>() : nullptr, status ? sl.out[2].as<uint8_t>() : nullptr, on->stream, tx_fn, fn);
-    });
-}
-// The Merkle calls (plume_capi_internal.h): the ABI and the launchers live in plume_merkle_capi.hip.  leaf and verify are the address call over again: per-item kernels
-// on the caller's arrays, no table, no workspace.  build and proof work on one tree, so their host-pointer forms never split: a plume_init_multi context runs them on its
-// first shard, the whole tree staged in that context's first slot.  build's sort keeps its records in ctx->mrksort, so the device form holds the workspace like the
-// transaction sender does.
-static int merkle_formats_ok(int leaf_format, int addr_format, const MerkleLaunch* fn) {
-    if (!fn || !fn->leaf || !fn->sort || !fn->place || !fn->level || !fn->top || !fn->proof || !fn->verify) return fail(PLUME_ERR_ARG, "the Merkle kernels are not part of this build");
-    if (leaf_format != PLUME_MRK_LEAF_HASH32 && leaf_format != PLUME_MRK_LEAF_ADDRESS && leaf_format != PLUME_MRK_LEAF_ADDRESS_UINT256)
-        return fail(PLUME_ERR_ARG, "leaf_format must be 0, 1 or 2");
-    if (addr_format != PLUME_ETHK_ADDR_RAW20 && addr_format != PLUME_ETHK_ADDR_RECORD64) return fail(PLUME_ERR_ARG, "addr_format must be 0 or 1: a leaf is made of address bytes, not of EIP-55 text");
-    return 0;
-}
-static int merkle_leaf_args_ok(int leaf_format, int addr_format, size_t n, const void* in, const void* amount, const void* leaf, const MerkleLaunch* fn) {
-    if (int rc = merkle_formats_ok(leaf_format, addr_format, fn)) return rc;
-    if (n && (!in || !leaf || (leaf_format == PLUME_MRK_LEAF_ADDRESS_UINT256 && !amount))) return fail(PLUME_ERR_ARG, "null array");
-    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
-    return 0;
-}
-static int merkle_leaf_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* in, const uint8_t* amount, uint8_t* leaf, uint8_t* status,
-                              hipStream_t st, const MerkleLaunch* fn) {
-    if (n == 0) return 0;
-    MerkleLeafArgs a; a.leaf_format = leaf_format; a.addr_format = addr_format; a.n = (uint32_t)n; a.in = in; a.amount = amount; a.leaf = leaf; a.status = status;
-    ctx->timer.begin(st);
-    fn->leaf(a, st); ctx->timer.stage("merkle_leaf", st);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int plume::capi_merkle_leaf_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* address, const uint8_t* amount, uint8_t* leaf32, uint8_t* status,
-                                   void* stream, const MerkleLaunch* fn) {
-    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = merkle_leaf_args_ok(leaf_format, addr_format, n, address, amount, leaf32, fn)) return rc;
-    return merkle_leaf_device(ctx, leaf_format, addr_format, n, address, amount, leaf32, status, st_, fn);
-}
-int plume::capi_merkle_leaf(plume_ctx* ctx, int leaf_format, int addr_format, size_t n, const uint8_t* address, const uint8_t* amount, uint8_t* leaf32, uint8_t* status,
-                            const MerkleLaunch* fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = merkle_leaf_args_ok(leaf_format, addr_format, n, address, amount, leaf32, fn)) return rc;
-    if (leaf_format != PLUME_MRK_LEAF_ADDRESS_UINT256) amount = nullptr;
-    const HostCall call{nullptr, nullptr, {{address, mrk_item_width(leaf_format, addr_format)}, {amount, 32}}, {{leaf32, 32}, {status, 1}}};
-    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return merkle_leaf_device(on, leaf_format, addr_format, cnt, sl.in[0].as<uint8_t>(), amount ? sl.in[1].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(),
-                                  status ? sl.out[1].as<uint8_t>() : nullptr, on->stream, fn);
-    });
-}
-static int merkle_build_args_ok(int flags, size_t n, const void* leaf, const void* tree, const MerkleLaunch* fn) {
-    if (int rc = merkle_formats_ok(PLUME_MRK_LEAF_HASH32, PLUME_ETHK_ADDR_RAW20, fn)) return rc;
-    if (flags & ~PLUME_MRK_SORT_LEAVES) return fail(PLUME_ERR_ARG, "unknown flag bits");
-    if (n == 0 || n > PLUME_MRK_MAX_N) return fail(PLUME_ERR_ARG, "a tree has between 1 and 2^26 leaves");
-    if (!leaf || !tree) return fail(PLUME_ERR_ARG, "null array");
-    return 0;
-}
-static int merkle_build_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf, uint8_t* tree, uint32_t* leaf_pos, hipStream_t st, const MerkleLaunch* fn) {
-    const bool sorted = (flags & PLUME_MRK_SORT_LEAVES) && n > 1;
-    const uint32_t npad = mrk_next_pow2((uint32_t)n);
-    if (int rc = ws_acquire(ctx, st)) return rc;
-    WsHold hold(ctx, st);
-    if (sorted && ctx->mrksort.ensure((size_t)PLUME_MRK_REC_WORDS * 4 * npad)) return PLUME_ERR_HIP;
-    ctx->timer.begin(st);
-    if (sorted) {
-        MerkleSortArgs sa; sa.n = (uint32_t)n; sa.npad = npad; sa.tile = npad < PLUME_MRK_TILE ? npad : PLUME_MRK_TILE; sa.leaf = leaf; sa.ws = ctx->mrksort.as<uint32_t>();
-        fn->sort(sa, st); ctx->timer.stage("merkle_sort", st);
-    }
-    MerkleTreeArgs ta; ta.n = (uint32_t)n; ta.npad = npad; ta.leaf = leaf; ta.ws = sorted ? ctx->mrksort.as<uint32_t>() : nullptr; ta.tree = tree; ta.leaf_pos = leaf_pos;
-    fn->place(ta, st); ctx->timer.stage("merkle_place", st);
-    if (n >= 2) {
-        const char* e = std::getenv("PLUME_MERKLE_FUSED_TOP");                           // A/B knob (tests/gpu_debug/merkle_timing.py): 0 = one launch per depth all the way up
-        const bool fused = !(e && std::atoi(e) == 0);
-        uint32_t d = mrk_parent_depth((uint32_t)n) + 1u;
-        const uint32_t stop = fused ? PLUME_MRK_TOP_DEPTH + 1u : 0u;
-        if (d > stop) {
-            while (d-- > stop) fn->level(tree, (uint32_t)n, d, st);
-            d = stop;
-            ctx->timer.stage("merkle_levels", st);
-        }
-        if (fused) { fn->top(tree, (uint32_t)n, d - 1u, st); ctx->timer.stage("merkle_top", st); }
-    }
-    HIPCHK(hipGetLastError());
-    return hold.release();
-}
-int plume::capi_merkle_tree_build_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf32, uint8_t* tree, uint32_t* leaf_pos, void* stream, const MerkleLaunch* fn) {
-    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = merkle_build_args_ok(flags, n, leaf32, tree, fn)) return rc;
-    return merkle_build_device(ctx, flags, n, leaf32, tree, leaf_pos, st_, fn);
-}
-// one piece whatever the chunk size is: the tree is built where all of its leaves are
-int plume::capi_merkle_tree_build(plume_ctx* ctx, int flags, size_t n, const uint8_t* leaf32, uint8_t* tree, uint32_t* leaf_pos, const MerkleLaunch* fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = merkle_build_args_ok(flags, n, leaf32, tree, fn)) return rc;
-    if (!ctx->shards.empty()) ctx = ctx->shards[0];                             // one tree: one device holds all of it
-    HIPCHK(hipSetDevice(ctx->device));
-    const HostCall call{nullptr, nullptr, {{leaf32, 32}}, {{tree, 32 * (2 * n - 1), false, true}, {leaf_pos, 4}}};
-    return serial_host_piece(ctx, call, 0, n, [&](HostSlot& sl, size_t, plume_ctx* on) -> int {
-        return merkle_build_device(on, flags, n, sl.in[0].as<uint8_t>(), sl.out[0].as<uint8_t>(), leaf_pos ? sl.out[1].as<uint32_t>() : nullptr, on->stream, fn);
-    });
-}
-static int merkle_proof_args_ok(size_t n, const void* tree, size_t m, const void* pos, size_t depth, const void* proof, const void* proof_len, const MerkleLaunch* fn) {
-    if (int rc = merkle_formats_ok(PLUME_MRK_LEAF_HASH32, PLUME_ETHK_ADDR_RAW20, fn)) return rc;
-    if (n == 0 || n > PLUME_MRK_MAX_N) return fail(PLUME_ERR_ARG, "a tree has between 1 and 2^26 leaves");
-    if (depth > PLUME_MRK_MAX_DEPTH) return fail(PLUME_ERR_ARG, "depth above 64");
-    if (m > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "m too large");
-    if (m && (!tree || !pos || !proof_len || (depth && !proof))) return fail(PLUME_ERR_ARG, "null array");
-    return 0;
-}
-static int merkle_proof_device(plume_ctx* ctx, size_t n, const uint8_t* tree, size_t m, const uint32_t* pos, size_t depth, uint8_t* proof, uint8_t* proof_len, hipStream_t st,
-                               const MerkleLaunch* fn) {
-    if (m == 0) return 0;
-    MerkleProofArgs a; a.n = (uint32_t)n; a.m = (uint32_t)m; a.depth = (uint32_t)depth; a.tree = tree; a.pos = pos; a.proof = proof; a.proof_len = proof_len;
-    ctx->timer.begin(st);
-    fn->proof(a, st); ctx->timer.stage("merkle_proof", st);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int plume::capi_merkle_proof_device(plume_ctx* ctx, size_t n, const uint8_t* tree, size_t m, const uint32_t* pos, size_t depth, uint8_t* proof, uint8_t* proof_len,
-                                    void* stream, const MerkleLaunch* fn) {
-    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = merkle_proof_args_ok(n, tree, m, pos, depth, proof, proof_len, fn)) return rc;
-    return merkle_proof_device(ctx, n, tree, m, pos, depth, proof, proof_len, st_, fn);
-}
-int plume::capi_merkle_proof(plume_ctx* ctx, size_t n, const uint8_t* tree, size_t m, const uint32_t* pos, size_t depth, uint8_t* proof, uint8_t* proof_len,
-                             const MerkleLaunch* fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = merkle_proof_args_ok(n, tree, m, pos, depth, proof, proof_len, fn)) return rc;
-    if (m == 0) return 0;
-    if (!ctx->shards.empty()) ctx = ctx->shards[0];                             // the tree is staged once: one device answers every index
-    const size_t pb = 32 * depth;
-    const HostCall call{nullptr, nullptr, {{tree, 32 * (2 * n - 1), false, true}, {pos, 4}}, {{pb ? proof : nullptr, pb}, {proof_len, 1}}};
-    return serial_host_call(ctx, m, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return merkle_proof_device(on, n, sl.in[0].as<uint8_t>(), cnt, sl.in[1].as<uint32_t>(), depth, pb ? sl.out[0].as<uint8_t>() : nullptr, sl.out[1].as<uint8_t>(), on->stream, fn);
-    });
-}
-static int merkle_verify_args_ok(int leaf_format, int addr_format, size_t m, const void* in, const void* amount, size_t depth, const void* proof, const void* proof_len,
-                                 const void* root, const void* status, const MerkleLaunch* fn) {
-    if (int rc = merkle_formats_ok(leaf_format, addr_format, fn)) return rc;
-    if (depth > PLUME_MRK_MAX_DEPTH) return fail(PLUME_ERR_ARG, "depth above 64");
-    if (m > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "m too large");
-    if (m && (!in || !proof_len || !root || !status || (depth && !proof) || (leaf_format == PLUME_MRK_LEAF_ADDRESS_UINT256 && !amount))) return fail(PLUME_ERR_ARG, "null array");
-    return 0;
-}
-static int merkle_verify_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* in, const uint8_t* amount, size_t depth, const uint8_t* proof,
-                                const uint8_t* proof_len, const uint8_t* root, uint8_t* status, hipStream_t st, const MerkleLaunch* fn) {
-    if (m == 0) return 0;
-    MerkleVerifyArgs a; a.leaf_format = leaf_format; a.addr_format = addr_format; a.m = (uint32_t)m; a.depth = (uint32_t)depth; a.in = in; a.amount = amount; a.proof = proof;
-    a.proof_len = proof_len; a.root = root; a.status = status;
-    ctx->timer.begin(st);
-    fn->verify(a, st); ctx->timer.stage("merkle_verify", st);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int plume::capi_merkle_verify_device(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* address_or_leaf, const uint8_t* amount, size_t depth,
-                                     const uint8_t* proof, const uint8_t* proof_len, const uint8_t* root32, uint8_t* status, void* stream, const MerkleLaunch* fn) {
-    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = merkle_verify_args_ok(leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, fn)) return rc;
-    return merkle_verify_device(ctx, leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, st_, fn);
-}
-int plume::capi_merkle_verify(plume_ctx* ctx, int leaf_format, int addr_format, size_t m, const uint8_t* address_or_leaf, const uint8_t* amount, size_t depth,
-                              const uint8_t* proof, const uint8_t* proof_len, const uint8_t* root32, uint8_t* status, const MerkleLaunch* fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = merkle_verify_args_ok(leaf_format, addr_format, m, address_or_leaf, amount, depth, proof, proof_len, root32, status, fn)) return rc;
-    if (leaf_format != PLUME_MRK_LEAF_ADDRESS_UINT256) amount = nullptr;
-    const size_t pb = 32 * depth;
-    const HostCall call{nullptr, nullptr, {{address_or_leaf, mrk_item_width(leaf_format, addr_format)}, {amount, 32}, {pb ? proof : nullptr, pb}, {proof_len, 1}, {root32, 32, false, true}},
-                        {{status, 1}}};
-    return serial_host_call_any(ctx, m, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return merkle_verify_device(on, leaf_format, addr_format, cnt, sl.in[0].as<uint8_t>(), amount ? sl.in[1].as<uint8_t>() : nullptr, depth,
-                                    pb ? sl.in[2].as<uint8_t>() : nullptr, sl.in[3].as<uint8_t>(), sl.in[4].as<uint8_t>(), sl.out[0].as<uint8_t>(), on->stream, fn);
-    });
-}
-// The ECDSA signer (plume_capi_internal.h): the ABI and the launchers live in plume_ecdsa_sign_capi.hip.  The table of G is the signer's -- the comb, or at level 2 the
-// scanned table -- and the workspace is the signer's too: the nonce buffer, one Jacobian result per item (two with the self-check: sk G), the item flags; the call joins the
-// ws_free chain.  plume_set_sub_batches cuts the call as it cuts an ECDSA recovery (sub_batch_bounds); there is no stage in front of a long multiplication to overlap, so
-// the slices follow one another on the caller's stream.  With plume_set_sign_selfcheck on, finalize writes ctx->scstage, the recover stages (ecdsa_device, on this
-// workspace and this stream) recover a key from the staged (hash, r, s, v), the release kernel writes the caller's arrays and the staging is wiped.
-static int ecdsa_sign_args_ok(int flags, size_t n, const void* hash, const void* sk, const void* r, const void* s, const void* v, const void* status, const EcdsaSignLaunch* fn) {
-    if (flags & ~PLUME_ECDSAK_SIGN_V27) return fail(PLUME_ERR_ARG, "unknown flag bits");
-    if (!fn || !fn->nonce || !fn->gmul || !fn->finalize || !fn->release || !fn->recover) return fail(PLUME_ERR_ARG, "the ECDSA signing kernels are not part of this build");
-    if (n && (!hash || !sk || !r || !s || !v || !status)) return fail(PLUME_ERR_ARG, "null array");
-    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
-    return 0;
-}
-static int ecdsa_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v, uint8_t* status,
-                             hipStream_t st, const EcdsaSignLaunch* fn, bool continue_timer = false) {
-    if (n == 0) return 0;
-    if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
-    if (int rc = need_sign_tables(ctx)) return rc;
-    const bool selfcheck = ctx->sign_selfcheck != 0;
-    if (selfcheck) { if (int rc = need_gcomb(ctx)) return rc; }                  // the recover stages' table, built before anything is queued
-    if (!continue_timer) { if (int rc = ws_acquire(ctx, st)) return rc; }       // continue_timer: the caller (the transaction signer) holds the workspace already and has begun the timeline
-    std::unique_ptr<WsHold> hold(continue_timer ? nullptr : new WsHold(ctx, st));
-    const std::vector<size_t> cut = sub_batch_bounds(ctx, n);
-    const size_t nsub = cut.size() - 1;
-    const size_t T = selfcheck ? 2 : 1;                                         // points per item
-    constexpr size_t kEcdsaStageBytes = 2 * 32 + 2 * 64 + 3;                         // per item: r, s | sk G, the recovered key | v, status, the recover stages' status -- in that order, the records 16-byte aligned
-    if (ctx->nonce.ensure(32 * n) || ctx->itemflags.ensure(n) || ctx->res.ensure((size_t)PLUME_JAC_WORDS * 4 * T * n) || ctx->resinf.ensure(T * n) ||
-        (selfcheck && ctx->scstage.ensure(kEcdsaStageBytes * n)))
-        return PLUME_ERR_HIP;
-    uint8_t* const stg = ctx->scstage.as<uint8_t>();
-    uint8_t *const g_r = stg, *const g_s = stg + 32 * n, *const g_pk = stg + 64 * n, *const g_rec = stg + 128 * n, *const g_v = stg + 192 * n, *const g_status = stg + 193 * n,
-            *const g_recst = stg + 194 * n;
-    struct StageWipe {                                                          // failure paths only: a call that fails behind finalize still wipes what it staged, in front of ws_free (~WsHold)
-        plume_ctx* ctx; size_t bytes; hipStream_t st;
-        ~StageWipe() { if (bytes) (void)hipMemsetAsync(ctx->scstage.p, 0, bytes, st); }
-    } stage_wipe{ctx, selfcheck ? kEcdsaStageBytes * n : 0, st};
-    StageTimer& t = ctx->timer;
-    if (!continue_timer) t.begin(st);
-    for (size_t k = 0; k < nsub; k++) {
-        const size_t lo = cut[k], cnt = cut[k + 1] - cut[k];
-        EcdsaSignArgs a;                                                        // the slice [lo, lo + cnt) as a batch of its own
-        memset(&a, 0, sizeof a);
-        a.flags = flags; a.uniform = ctx->sign_uniform; a.n = (uint32_t)cnt; a.ntask = (uint32_t)T;
-        a.hash = hash + 32 * lo; a.sk = sk + 32 * lo; a.aux = aux ? aux + 32 * lo : nullptr;
-        a.r = (selfcheck ? g_r : r) + 32 * lo; a.s = (selfcheck ? g_s : s) + 32 * lo; a.v = (selfcheck ? g_v : v) + lo; a.status = (selfcheck ? g_status : status) + lo;
-        a.pkstage = selfcheck ? g_pk + 64 * lo : nullptr;
-        a.k = ctx->nonce.as<uint8_t>() + 32 * lo; a.itemflags = ctx->itemflags.as<uint8_t>() + lo;
-        a.res = ctx->res.as<uint32_t>() + (size_t)PLUME_JAC_WORDS * T * lo; a.resinf = ctx->resinf.as<uint8_t>() + T * lo;
-        a.gcomb = ctx->fixed->gcomb.as<uint32_t>(); a.gscan = ctx->fixed->gscan.as<uint32_t>();
-        fn->nonce(a, st); t.stage("ecdsa_sign_nonce", st);
-        fn->gmul(a, st); t.stage("ecdsa_sign_gmul", st);
-        launch_normalize(a.res, a.resinf, T * cnt, st); t.stage("to_affine", st);
-        fn->finalize(a, st); t.stage("ecdsa_sign_finalize", st);
-    }
-    // the nonces never leave the device; wipe them and the images of k G behind the last kernel that reads them
-    HIPCHK(hipMemsetAsync(ctx->nonce.p, 0, 32 * n, st));
-    HIPCHK(hipMemsetAsync(ctx->res.p, 0, (size_t)PLUME_JAC_WORDS * 4 * T * n, st));
-    HIPCHK(hipGetLastError());
-    if (selfcheck) {
-        if (int rc = ecdsa_device(ctx, PLUME_ECDSAK_LOW_S, PLUME_ETHK_PK_AFFINE64, PLUME_ETHK_ADDR_RAW20, n, hash, g_r, g_s, g_v, nullptr, g_rec, nullptr, g_recst, st, fn->recover, true))
-            return rc;
-        EcdsaSignReleaseArgs ra;
-        ra.n = (uint32_t)n; ra.stage_r = g_r; ra.stage_s = g_s; ra.stage_v = g_v; ra.stage_status = g_status; ra.stage_pk = g_pk; ra.rec_pk = g_rec; ra.rec_status = g_recst;
-        ra.r = r; ra.s = s; ra.v = v; ra.status = status;
-        fn->release(ra, st); t.stage("ecdsa_sign_release", st);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemsetAsync(ctx->scstage.p, 0, kEcdsaStageBytes * n, st));        // a withheld s is precisely the value that must not linger
-        stage_wipe.bytes = 0;
-    }
-    return hold ? hold->release() : 0;
-}
-int plume::capi_ecdsa_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v,
-                                  uint8_t* status, void* stream, const EcdsaSignLaunch* fn) {
-    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = ecdsa_sign_args_ok(flags, n, hash, sk, r, s, v, status, fn)) return rc;
-    return ecdsa_sign_device(ctx, flags, n, hash, sk, aux, r, s, v, status, st_, fn);
-}
-// the host-pointer form: the signer's pipeline (host_call_any: pieces, two lanes, shards; sk and aux staged as secrets and wiped), with no messages to stage
-int plume::capi_ecdsa_sign(plume_ctx* ctx, int flags, size_t n, const uint8_t* hash, const uint8_t* sk, const uint8_t* aux, uint8_t* r, uint8_t* s, uint8_t* v, uint8_t* status,
-                           const EcdsaSignLaunch* fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = ecdsa_sign_args_ok(flags, n, hash, sk, r, s, v, status, fn)) return rc;
-    if (n == 0) return 0;
-    static const uint8_t no_msgs[16] = {0};
-    const std::vector<uint64_t> no_off(n + 1, 0);                               // every item's message is empty
-    const HostCall call{no_msgs, no_off.data(), {{hash, 32}, {sk, 32, true}, {aux, 32, true}}, {{r, 32}, {s, 32}, {v, 1}, {status, 1}}, false, ctx->host_sign_lanes > 1};
-    return host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return ecdsa_sign_device(on, flags, cnt, sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(), aux ? sl.in[2].as<uint8_t>() : nullptr, sl.out[0].as<uint8_t>(),
-                                 sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(), sl.out[3].as<uint8_t>(), on->stream, fn);
-    });
-}
-// The transaction signer (plume_capi_internal.h): the ABI and the launchers live in plume_eth_tx_sign_capi.hip.  k_eth_tx_sign_frame stages the framing and the signing
-// hash in ctx->txsign, the ECDSA signer's stages (ecdsa_sign_device, on this workspace and this stream, self-check included) sign the staged hash into the same staging,
-// k_eth_tx_sign_assemble writes the caller's slots and records; the staged r, s, v and status are wiped behind it (an item the framing rejected was signed over the zero hash: that
-// signature is never released).  The call holds the workspace from in front of the frame to behind the wipe.
-static int eth_tx_sign_args_ok(int flags, size_t n, const void* off, const void* sk, const void* out, const void* out_len, const void* status, const EthTxSignLaunch* fn) {
-    if (flags) return fail(PLUME_ERR_ARG, "unknown flag bits");
-    if (!fn || !fn->frame || !fn->assemble || !fn->sign) return fail(PLUME_ERR_ARG, "the transaction signing kernels are not part of this build");
-    if (n && (!off || !sk || !out || !out_len || !status)) return fail(PLUME_ERR_ARG, "null array");
-    if (n > 0xFFFFFFF0u) return fail(PLUME_ERR_ARG, "n too large");
-    const uint8_t one = 0;                                                      // (hash, r, s, v are the staging's: any non-null pointer passes the signer's own check)
-    return ecdsa_sign_args_ok(0, n, &one, sk ? sk : &one, &one, &one, &one, &one, fn->sign);
-}
-static int eth_tx_sign_device(plume_ctx* ctx, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, const uint8_t* sk, const uint8_t* aux, uint8_t* out,
-                              size_t out_bytes, uint32_t* out_len, uint8_t* hash, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status,
-                              hipStream_t st, const EthTxSignLaunch* fn) {
-    if (n == 0) return 0;
-    if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
-    if (!txs && txs_bytes) return fail(PLUME_ERR_ARG, "null transaction buffer");
-    if (int rc = need_sign_tables(ctx)) return rc;                              // the signer's tables, built before anything is queued
-    if (ctx->sign_selfcheck) { if (int rc = need_gcomb(ctx)) return rc; }
-    if (int rc = ws_acquire(ctx, st)) return rc;
-    WsHold hold(ctx, st);
-    if (ctx->txsign.ensure((size_t)PLUME_ETHTXK_SIGN_STAGE * n)) return PLUME_ERR_HIP;
-    uint8_t* const stg = ctx->txsign.as<uint8_t>();
-    uint8_t *const g_hash = stg + 16 * n, *const g_r = stg + 48 * n, *const g_s = stg + 80 * n, *const g_v = stg + 112 * n, *const g_status = stg + 113 * n;
-    struct StageWipe {                                                          // failure paths only: whatever fails behind the sign stages, the staged signatures do not linger (queued in front of ws_free: ~WsHold runs later)
-        uint8_t* p; size_t bytes; hipStream_t st;
-        ~StageWipe() { if (bytes) (void)hipMemsetAsync(p, 0, bytes, st); }
-    } stage_wipe{g_r, 66 * n, st};
-    EthTxSignArgs a;
-    memset(&a, 0, sizeof a);
-    a.n = (uint32_t)n; a.txs = txs; a.tx_off = tx_off; a.txs_bytes = txs ? txs_bytes : 0;
-    a.st_chain = (uint64_t*)stg; a.st_frame = (uint64_t*)(stg + 8 * n); a.st_hash = g_hash; a.st_r = g_r; a.st_s = g_s; a.st_v = g_v; a.st_status = g_status;
-    a.out = out; a.out_bytes = out_bytes; a.out_len = out_len; a.hash = hash; a.r = r; a.s = s; a.v = v; a.chain_id = chain_id; a.tx_type = tx_type; a.status = status;
-    ctx->timer.begin(st);
-    fn->frame(a, st); ctx->timer.stage("eth_tx_sign_frame", st);
-    HIPCHK(hipGetLastError());
-    if (int rc = ecdsa_sign_device(ctx, 0, n, g_hash, sk, aux, g_r, g_s, g_v, g_status, st, fn->sign, true)) return rc;
-    fn->assemble(a, st); ctx->timer.stage("eth_tx_sign_assemble", st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(g_r, 0, 66 * n, st));                                  // r, s, v, status: contiguous in the staging
-    stage_wipe.bytes = 0;
-    return hold.release();
-}
-int plume::capi_eth_tx_sign_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* txs, const uint64_t* tx_off, size_t txs_bytes, const uint8_t* sk, const uint8_t* aux,
-                                   uint8_t* out, size_t out_bytes, uint32_t* out_len, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id,
-                                   uint8_t* tx_type, uint8_t* status, void* stream, const EthTxSignLaunch* fn) {
-    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = eth_tx_sign_args_ok(flags, n, tx_off, sk, out, out_len, status, fn)) return rc;
-    return eth_tx_sign_device(ctx, n, txs, tx_off, txs_bytes, sk, aux, out, out_bytes, out_len, hash32, r, s, v, chain_id, tx_type, status, st_, fn);
-}
-// the host-pointer form: a serial call with the transactions as its messages, sk and aux staged as secrets, and `out` as the call's ragged output
-int plume::capi_eth_tx_sign(plume_ctx* ctx, int flags, size_t n, const uint8_t* txs, const uint64_t* tx_off, const uint8_t* sk, const uint8_t* aux, uint8_t* out,
-                            uint32_t* out_len, uint8_t* hash32, uint8_t* r, uint8_t* s, uint8_t* v, uint64_t* chain_id, uint8_t* tx_type, uint8_t* status,
-                            const EthTxSignLaunch* fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = eth_tx_sign_args_ok(flags, n, tx_off, sk, out, out_len, status, fn)) return rc;
-    HostCall call = eth_tx_call({txs, tx_off, {{sk, 32, true}, {aux, 32, true}},
-                                 {{out_len, 4}, {status, 1}, {hash32, 32}, {r, 32}, {s, 32}, {v, 1}, {chain_id, 8}, {tx_type, 1}}});
-    call.ragged = out; call.ragged_growth = PLUME_ETHTXK_SIGN_GROWTH;
-    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        const size_t out_bytes = (size_t)sl.rel[cnt] + (size_t)PLUME_ETHTXK_SIGN_GROWTH * cnt;
-        return eth_tx_sign_device(on, cnt, sl.msgs.as<uint8_t>(), sl.off.as<uint64_t>(), (size_t)sl.rel[cnt], sl.in[0].as<uint8_t>(), aux ? sl.in[1].as<uint8_t>() : nullptr,
-                                  sl.ragged.as<uint8_t>(), out_bytes, sl.out[0].as<uint32_t>(), hash32 ? sl.out[2].as<uint8_t>() : nullptr,
-                                  r ? sl.out[3].as<uint8_t>() : nullptr, s ? sl.out[4].as<uint8_t>() : nullptr, v ? sl.out[5].as<uint8_t>() : nullptr,
-                                  chain_id ? sl.out[6].as<uint64_t>() : nullptr, tx_type ? sl.out[7].as<uint8_t>() : nullptr, sl.out[1].as<uint8_t>(), on->stream, fn);
-    });
-}
-// The key derivation (plume_capi_internal.h): the ABI and the launchers live in plume_hd_capi.hip.  master is one kernel on the caller's arrays: no table, no workspace.
-// The derive calls use the signer's table of G (the public form: the comb) and its result array, and ctx->hdws for k, the chain code and the status between the levels;
-// they join the ws_free chain and are cut by plume_set_sub_batches as an ECDSA signing call is.  Behind the last finish the staging and the Jacobian images are wiped on the
-// call's stream; a call that fails half way wipes them too (StageWipe), in front of ws_free.
-static int hd_master_args_ok(size_t n, const void* seed, size_t seed_len, const void* sk, const void* chain, const void* status, const HdLaunch* fn) {
-    if (!fn || !fn->master) return fail(PLUME_ERR_ARG, "the key derivation kernels are not part of this build");
-    if (seed_len < 16 || seed_len > 64) return fail(PLUME_ERR_ARG, "seed_len must be 16 .. 64");
-    if (n && (!seed || !sk || !chain || !status)) return fail(PLUME_ERR_ARG, "null array");
-    if (n > 0xFFFFFFF0u / 64) return fail(PLUME_ERR_ARG, "n too large");
-    return 0;
-}
-static int hd_master_device(plume_ctx* ctx, size_t n, const uint8_t* seed, size_t seed_len, uint8_t* sk, uint8_t* chain, uint8_t* status, hipStream_t st, const HdLaunch* fn) {
-    if (n == 0) return 0;
-    HdArgs a;
-    memset(&a, 0, sizeof a);
-    a.n = (uint32_t)n; a.seed_len = (uint32_t)seed_len; a.parent = seed; a.child_sk = sk; a.child_chain = chain; a.status = status;
-    ctx->timer.begin(st);
-    fn->master(a, st); ctx->timer.stage("hd_master", st);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int plume::capi_hd_master_device(plume_ctx* ctx, size_t n, const uint8_t* seed, size_t seed_len, uint8_t* sk, uint8_t* chain, uint8_t* status, void* stream, const HdLaunch* fn) {
-    Route rt_(ctx, stream); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = hd_master_args_ok(n, seed, seed_len, sk, chain, status, fn)) return rc;
-    return hd_master_device(ctx, n, seed, seed_len, sk, chain, status, st_, fn);
-}
-int plume::capi_hd_master(plume_ctx* ctx, size_t n, const uint8_t* seed, size_t seed_len, uint8_t* sk, uint8_t* chain, uint8_t* status, const HdLaunch* fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = hd_master_args_ok(n, seed, seed_len, sk, chain, status, fn)) return rc;
-    const HostCall call{nullptr, nullptr, {{seed, seed_len, true}}, {{sk, 32, true}, {chain, 32, true}, {status, 1}}};
-    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return hd_master_device(on, cnt, sl.in[0].as<uint8_t>(), seed_len, sl.out[0].as<uint8_t>(), sl.out[1].as<uint8_t>(), sl.out[2].as<uint8_t>(), on->stream, fn);
-    });
-}
-static int hd_derive_args_ok(bool pub, int flags, int pk_format, int addr_format, size_t n, const void* parent, const void* parent_chain, const void* path, size_t depth,
-                             const void* child_sk, const void* child_pk, const void* status, const HdLaunch* fn) {
-    if (flags & ~(PLUME_HDK_SHARED_PARENT | PLUME_HDK_SHARED_PATH)) return fail(PLUME_ERR_ARG, "unknown flag bits");
-    if (pk_format != PLUME_ETHK_PK_AFFINE64 && pk_format != PLUME_ETHK_PK_SEC1) return fail(PLUME_ERR_ARG, "pk_format must be 0 or 1");
-    if (addr_format != PLUME_ETHK_ADDR_RAW20 && addr_format != PLUME_ETHK_ADDR_RECORD64 && addr_format != PLUME_ETHK_ADDR_EIP55) return fail(PLUME_ERR_ARG, "addr_format must be 0, 1 or 2");
-    if (depth < 1 || depth > PLUME_HDK_MAX_DEPTH) return fail(PLUME_ERR_ARG, "depth must be 1 .. PLUME_HD_MAX_DEPTH");
-    if (!fn || !fn->priv_load || !fn->pub_load || !fn->gmul || !fn->priv_step || !fn->pub_step || !fn->finish)
-        return fail(PLUME_ERR_ARG, "the key derivation kernels are not part of this build");
-    if (n && (!parent || !parent_chain || !path || !status || (pub ? !child_pk : !child_sk))) return fail(PLUME_ERR_ARG, "null array");
-    if (n > 0xFFFFFFF0u / 64) return fail(PLUME_ERR_ARG, "n too large");
-    return 0;
-}
-static int hd_derive_device(plume_ctx* ctx, bool pub, int flags, int pk_format, int addr_format, size_t n, const uint8_t* parent, const uint8_t* parent_chain,
-                            const uint8_t* path, size_t depth, uint8_t* child_sk, uint8_t* child_chain, uint8_t* child_pk, uint8_t* address, uint8_t* status, hipStream_t st,
-                            const HdLaunch* fn) {
-    if (n == 0) return 0;
-    if (n > ctx->chunk) return fail(PLUME_ERR_ARG, "n exceeds the chunk size (plume_set_chunk)");
-    if (int rc = pub ? need_gcomb(ctx) : need_sign_tables(ctx)) return rc;      // built before anything is queued
-    if (int rc = ws_acquire(ctx, st)) return rc;
-    WsHold hold(ctx, st);
-    const std::vector<size_t> cut = sub_batch_bounds(ctx, n);
-    const size_t res_bytes = (size_t)PLUME_JAC_WORDS * 4 * n;
-    if (ctx->hdws.ensure((size_t)PLUME_HDK_WS_BYTES * n) || ctx->res.ensure(res_bytes) || ctx->resinf.ensure(n)) return PLUME_ERR_HIP;
-    struct StageWipe {                                                          // every path out of here, in front of ws_free (~WsHold runs later): k, the chain codes, the images of k G
-        plume_ctx* ctx; size_t ws, res; hipStream_t st;
-        ~StageWipe() { (void)hipMemsetAsync(ctx->hdws.p, 0, ws, st); (void)hipMemsetAsync(ctx->res.p, 0, res, st); }
-    };
-    uint8_t* const ws = ctx->hdws.as<uint8_t>();
-    const size_t pw = pub ? eth_pk_width(pk_format) : 32, kw = eth_pk_width(pk_format), aw = eth_address_width(addr_format);
-    const bool one_parent = (flags & PLUME_HDK_SHARED_PARENT) != 0, one_path = (flags & PLUME_HDK_SHARED_PATH) != 0;
-    StageTimer& t = ctx->timer;
-    t.begin(st);
-    {
-        StageWipe wipe{ctx, (size_t)PLUME_HDK_WS_BYTES * n, res_bytes, st};
-        for (size_t s = 0; s + 1 < cut.size(); s++) {
-            const size_t lo = cut[s], cnt = cut[s + 1] - cut[s];
-            HdArgs a;                                                           // the slice [lo, lo + cnt) as a batch of its own
-            memset(&a, 0, sizeof a);
-            a.flags = flags; a.pk_format = pk_format; a.addr_format = addr_format; a.uniform = ctx->sign_uniform; a.n = (uint32_t)cnt; a.depth = (uint32_t)depth;
-            a.parent = parent + (one_parent ? 0 : pw * lo); a.parent_chain = parent_chain + (one_parent ? 0 : 32 * lo); a.path = path + (one_path ? 0 : 4 * depth * lo);
-            a.child_sk = child_sk ? child_sk + 32 * lo : nullptr; a.child_chain = child_chain ? child_chain + 32 * lo : nullptr;
-            a.child_pk = child_pk ? child_pk + kw * lo : nullptr; a.address = address ? address + aw * lo : nullptr; a.status = status + lo;
-            a.k = ws + 32 * lo; a.chain = ws + 32 * n + 32 * lo; a.st = ws + 64 * n + lo;
-            a.res = ctx->res.as<uint32_t>() + (size_t)PLUME_JAC_WORDS * lo; a.resinf = ctx->resinf.as<uint8_t>() + lo;
-            a.gcomb = ctx->fixed->gcomb.as<uint32_t>(); a.gscan = ctx->fixed->gscan.as<uint32_t>();
-            if (pub) {
-                fn->pub_load(a, st); t.stage("hd_pub_load", st);
-                for (size_t j = 0; j < depth; j++) {
-                    a.level = (uint32_t)j;
-                    fn->pub_step(a, st); t.stage("hd_pub_step", st);
-                    launch_normalize(a.res, a.resinf, cnt, st); t.stage("to_affine", st);
-                }
-            } else {
-                fn->priv_load(a, st); t.stage("hd_priv_load", st);
-                for (size_t j = 0; j <= depth; j++) {
-                    fn->gmul(a, st); t.stage("hd_gmul", st);
-                    launch_normalize(a.res, a.resinf, cnt, st); t.stage("to_affine", st);
-                    if (j == depth) break;
-                    a.level = (uint32_t)j;
-                    fn->priv_step(a, st); t.stage("hd_priv_step", st);
-                }
-            }
-            fn->finish(a, st); t.stage("hd_finish", st);
-        }
-    }
-    HIPCHK(hipGetLastError());
-    return hold.release();
-}
-int plume::capi_hd_derive_device(plume_ctx* ctx, bool pub, int flags, int pk_format, int addr_format, size_t n, const uint8_t* parent, const uint8_t* parent_chain,
-                                 const uint32_t* path, size_t depth, uint8_t* child_sk, uint8_t* child_chain, uint8_t* child_pk, uint8_t* address, uint8_t* status,
-                                 void* stream, const HdLaunch* fn) {
-    Route rt_(ctx, stream, n); ctx = rt_.lane; const hipStream_t st_ = rt_.st;
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = hd_derive_args_ok(pub, flags, pk_format, addr_format, n, parent, parent_chain, path, depth, child_sk, child_pk, status, fn)) return rc;
-    return hd_derive_device(ctx, pub, flags, pk_format, addr_format, n, parent, parent_chain, (const uint8_t*)path, depth, pub ? nullptr : child_sk, child_chain, child_pk,
-                            address, status, st_, fn);
-}
-// the host-pointer form: a serial call; sk and the chain codes staged as secrets, going in and coming out; a shared parent or path is a whole-call input
-int plume::capi_hd_derive(plume_ctx* ctx, bool pub, int flags, int pk_format, int addr_format, size_t n, const uint8_t* parent, const uint8_t* parent_chain,
-                          const uint32_t* path, size_t depth, uint8_t* child_sk, uint8_t* child_chain, uint8_t* child_pk, uint8_t* address, uint8_t* status,
-                          const HdLaunch* fn) {
-    if (!ctx) return fail(PLUME_ERR_ARG, "null context");
-    if (int rc = hd_derive_args_ok(pub, flags, pk_format, addr_format, n, parent, parent_chain, path, depth, child_sk, child_pk, status, fn)) return rc;
-    if (pub) child_sk = nullptr;
-    const bool one_parent = (flags & PLUME_HDK_SHARED_PARENT) != 0, one_path = (flags & PLUME_HDK_SHARED_PATH) != 0;
-    const size_t pw = pub ? eth_pk_width(pk_format) : 32;
-    const HostCall call{nullptr, nullptr,
-                        {{parent, pw, !pub, one_parent}, {parent_chain, 32, true, one_parent}, {path, 4 * depth, false, one_path}},
-                        {{child_sk, 32, true}, {child_chain, 32, true}, {child_pk, eth_pk_width(pk_format)}, {address, eth_address_width(addr_format)}, {status, 1}}};
-    return serial_host_call_any(ctx, n, call, [&](HostSlot& sl, size_t cnt, plume_ctx* on) -> int {
-        return hd_derive_device(on, pub, flags, pk_format, addr_format, cnt, sl.in[0].as<uint8_t>(), sl.in[1].as<uint8_t>(), sl.in[2].as<uint8_t>(), depth,
-                                child_sk ? sl.out[0].as<uint8_t>() : nullptr, child_chain ? sl.out[1].as<uint8_t>() : nullptr, child_pk ? sl.out[2].as<uint8_t>() : nullptr,
-                                address ? sl.out[3].as<uint8_t>() : nullptr, sl.out[4].as<uint8_t>(), on->stream, fn);
     });
 }
 // The STRUCTURE half of SecretKey::from_sec1_der for the fixed 109-byte form above (what the wasm layer emits): ok[i] = 1 iff the record has that exact shape and
