@@ -5,29 +5,10 @@
 // a caller stream (which must not have run anything when the call returns, under the lazy scheduler) with and without sub-batches, a plume_init_multi context over eight
 // mock devices.  Then the argument errors, and every allocation of a host-form call failing in turn: an error code, the outputs of a repeated call right, nothing leaked.
 // A context that only ever did this builds the comb and no window table.
-#include <hip/hip_runtime.h>
+#define DRIVER_NAME "ecdsa_driver"
+#include "driver_prelude.h"
 
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <string>
-#include <vector>
-
-#include "../../include/plume_hip.h"
-
-static std::string g_what;
-#define REQUIRE(c)                                                                                                                        \
-    do {                                                                                                                                  \
-        if (!(c)) { std::fprintf(stderr, "ecdsa_driver: %s:%d: %s   [%s] (%s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-
-static std::mt19937_64 rng;
-constexpr uint8_t kFill = 0xAA;
 static const size_t kPk[2] = {64, 33}, kWidth[3] = {20, 64, 42};
-
-static bool all_of(const uint8_t* p, size_t bytes, uint8_t v) { for (size_t i = 0; i < bytes; i++) if (p[i] != v) return false; return true; }
 
 static size_t g_n = 0;
 static std::vector<uint8_t> g_hash, g_r, g_s, g_v, g_status, g_pk, g_raw, g_eip;
@@ -43,20 +24,6 @@ static void read_vectors(const char* path) {
             std::fread(g_status.data(), 1, n, f) == n && std::fread(g_pk.data(), 64, n, f) == n && std::fread(g_raw.data(), 20, n, f) == n && std::fread(g_eip.data(), 42, n, f) == n);
     std::fclose(f);
 }
-
-struct Arr {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    int kind;                                             // 0 pageable, 1 page-locked, 2 device
-    Arr(size_t b, int k, const void* src = nullptr) : bytes(b), kind(k) {
-        if (k == 2) REQUIRE(hipMalloc((void**)&p, b ? b : 1) == hipSuccess); else p = (uint8_t*)(k ? plume_host_alloc(b ? b : 1) : std::malloc(b ? b : 1));
-        REQUIRE(p);
-        if (src) std::memcpy(p, src, b); else std::memset(p, kFill, b);
-    }
-    ~Arr() { if (kind == 2) (void)hipFree(p); else if (kind) plume_host_free(p); else std::free(p); }
-    Arr(const Arr&) = delete;
-    Arr& operator=(const Arr&) = delete;
-};
 
 // items [lo, lo + n) of the vectors; expect_mode 0 absent, 1 matching, 2 every third item wrong in one bit of byte (i % 20); outs: bit 0 pk, bit 1 address, bit 2 status
 struct Call {
@@ -173,7 +140,7 @@ static void group_failing_allocations() {
     plume_ctx* keeper = nullptr;
     REQUIRE(plume_init(&keeper, 0) == 0);
     { Call c(0, 0, 0, 4, 0, 7, 0); g_what = "allocations: the comb"; REQUIRE(c.run(keeper, nullptr) == 0); c.check(); }
-    const long dev0 = mockhip::outstanding(0), host0 = mockhip::outstanding(1), str0 = mockhip::outstanding(2), ev0 = mockhip::outstanding(3);
+    const Outstanding before;
     plume_ctx* ctx = nullptr;
     REQUIRE(plume_init(&ctx, 0) == 0);
     (void)mockhip::fail_allocation(-1);
@@ -193,7 +160,7 @@ static void group_failing_allocations() {
         c.check();
         plume_destroy(ctx);
     }
-    REQUIRE(mockhip::outstanding(0) == dev0 && mockhip::outstanding(1) == host0 && mockhip::outstanding(2) == str0 && mockhip::outstanding(3) == ev0);
+    REQUIRE(Outstanding() == before);
     plume_destroy(keeper);
 }
 

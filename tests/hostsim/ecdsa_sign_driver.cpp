@@ -5,27 +5,8 @@
 // on a caller stream (which must not have run anything when the call returns, under the lazy scheduler), the three uniform levels, sub-batches, the self-check on (same
 // bytes, the stage list of the header), plume_init_multi contexts over three and eight mock devices, argument errors; then every allocation of a call fails in turn -- an
 // error code, a repeated call right, nothing leaked; and after every sign call no device allocation holds a nonce of the batch.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <string>
-#include <vector>
-
-#include "../../include/plume_hip.h"
-
-static std::string g_what;
-#define REQUIRE(c)                                                                                                                            \
-    do {                                                                                                                                      \
-        if (!(c)) { std::fprintf(stderr, "ecdsa_sign_driver: %s:%d: %s   [%s] (%s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-
-static std::mt19937_64 rng;
-constexpr uint8_t kFill = 0xAA;
-static bool all_of(const uint8_t* p, size_t bytes, uint8_t v) { for (size_t i = 0; i < bytes; i++) if (p[i] != v) return false; return true; }
+#define DRIVER_NAME "ecdsa_sign_driver"
+#include "driver_prelude.h"
 
 static size_t g_n = 0, g_m = 0;
 static std::vector<uint8_t> g_hash, g_sk, g_aux, g_r[2], g_s[2], g_v[2], g_st[2], g_msgs, g_dg[2];
@@ -51,20 +32,6 @@ static void read_vectors(const char* path) {
     for (int mode = 0; mode < 2; mode++) { g_dg[mode].resize(32 * g_m); REQUIRE(std::fread(g_dg[mode].data(), 32, m, f) == m); }
     std::fclose(f);
 }
-
-struct Arr {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    int kind;                                             // 0 pageable, 1 page-locked, 2 device
-    Arr(size_t b, int k, const void* src = nullptr) : bytes(b), kind(k) {
-        if (k == 2) REQUIRE(hipMalloc((void**)&p, b ? b : 1) == hipSuccess); else p = (uint8_t*)(k ? plume_host_alloc(b ? b : 1) : std::malloc(b ? b : 1));
-        REQUIRE(p);
-        if (src) std::memcpy(p, src, b); else std::memset(p, kFill, b);
-    }
-    ~Arr() { if (kind == 2) (void)hipFree(p); else if (kind) plume_host_free(p); else std::free(p); }
-    Arr(const Arr&) = delete;
-    Arr& operator=(const Arr&) = delete;
-};
 
 // items [lo, lo + n) signed with or without aux, v as 0 / 1 or 27 / 28
 struct SignCall {
@@ -140,12 +107,10 @@ static std::vector<std::string> stages_of_a_device_call(plume_ctx* ctx) {
     SignCall c(0, g_n, false, true, 2);
     REQUIRE(c.run(ctx, st) == 0 && hipStreamSynchronize(st) == hipSuccess);
     c.check();
-    const char* names[64]; float ms[64];
-    const int k = plume_last_stage_times(ctx, names, ms, 64);
-    REQUIRE(k > 0 && k <= 64);
+    const std::vector<std::string> names = last_stage_names(ctx);
     REQUIRE(plume_set_stage_timing(ctx, 0) == 0);
     REQUIRE(hipStreamDestroy(st) == hipSuccess);
-    return std::vector<std::string>(names, names + k);
+    return names;
 }
 
 static void group_arguments(plume_ctx* ctx) {
@@ -179,7 +144,7 @@ static void group_failing_allocations() {
     plume_ctx* keeper = nullptr;                                                     // keeps the device's shared tables alive: the counted calls build none
     REQUIRE(plume_init(&keeper, 0) == 0);
     { g_what = "allocations: tables"; SignCall c(0, 8, false, false, 0); REQUIRE(c.run(keeper, nullptr) == 0); c.check(); }
-    const long dev0 = mockhip::outstanding(0), host0 = mockhip::outstanding(1), str0 = mockhip::outstanding(2), ev0 = mockhip::outstanding(3);
+    const Outstanding before;
     for (int selfcheck = 0; selfcheck < 2; selfcheck++) {
         plume_ctx* ctx = nullptr;
         REQUIRE(plume_init(&ctx, 0) == 0 && plume_set_sign_selfcheck(ctx, selfcheck) == 0);
@@ -201,7 +166,7 @@ static void group_failing_allocations() {
             plume_destroy(ctx);
         }
     }
-    REQUIRE(mockhip::outstanding(0) == dev0 && mockhip::outstanding(1) == host0 && mockhip::outstanding(2) == str0 && mockhip::outstanding(3) == ev0);
+    REQUIRE(Outstanding() == before);
     plume_destroy(keeper);
 }
 

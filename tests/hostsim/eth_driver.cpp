@@ -4,29 +4,10 @@
 // bytes: the host form with chunks smaller than n, pageable and page-locked arrays, expect absent / matching / wrong, NULL address / NULL status, the device form on a
 // caller stream (which must not have run anything when the call returns, under the lazy scheduler), plume_init_multi contexts over three and eight mock devices.  Then every
 // allocation of a host-form call fails in turn: an error code, the outputs of a repeated call right, nothing leaked.  A context that only ever did this builds no table.
-#include <hip/hip_runtime.h>
+#define DRIVER_NAME "eth_driver"
+#include "driver_prelude.h"
 
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <string>
-#include <vector>
-
-#include "../../include/plume_hip.h"
-
-static std::string g_what;
-#define REQUIRE(c)                                                                                                                      \
-    do {                                                                                                                                \
-        if (!(c)) { std::fprintf(stderr, "eth_driver: %s:%d: %s   [%s] (%s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-
-static std::mt19937_64 rng;
-constexpr uint8_t kFill = 0xAA;
 static const size_t kPk[2] = {64, 33}, kWidth[3] = {20, 64, 42};
-
-static bool all_of(const uint8_t* p, size_t bytes, uint8_t v) { for (size_t i = 0; i < bytes; i++) if (p[i] != v) return false; return true; }
 
 struct Vectors {
     size_t n = 0;
@@ -47,20 +28,6 @@ static void read_vectors(const char* path) {
     }
     std::fclose(f);
 }
-
-struct Arr {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    int kind;                                             // 0 pageable, 1 page-locked, 2 device
-    Arr(size_t b, int k, const void* src = nullptr) : bytes(b), kind(k) {
-        if (k == 2) REQUIRE(hipMalloc((void**)&p, b ? b : 1) == hipSuccess); else p = (uint8_t*)(k ? plume_host_alloc(b ? b : 1) : std::malloc(b ? b : 1));
-        REQUIRE(p);
-        if (src) std::memcpy(p, src, b); else std::memset(p, kFill, b);
-    }
-    ~Arr() { if (kind == 2) (void)hipFree(p); else if (kind) plume_host_free(p); else std::free(p); }
-    Arr(const Arr&) = delete;
-    Arr& operator=(const Arr&) = delete;
-};
 
 // items [lo, lo + n) of a key format's vectors; expect_mode 0 absent, 1 matching, 2 every third valid item wrong in one bit of byte (i % 20)
 struct Call {
@@ -165,7 +132,7 @@ static void group_arguments(plume_ctx* ctx) {
 
 // every allocation of one host-form call fails in turn
 static void group_failing_allocations() {
-    const long dev0 = mockhip::outstanding(0), host0 = mockhip::outstanding(1), str0 = mockhip::outstanding(2), ev0 = mockhip::outstanding(3);
+    const Outstanding before;
     plume_ctx* ctx = nullptr;
     REQUIRE(plume_init(&ctx, 0) == 0);
     (void)mockhip::fail_allocation(-1);
@@ -185,7 +152,7 @@ static void group_failing_allocations() {
         c.check();
         plume_destroy(ctx);
     }
-    REQUIRE(mockhip::outstanding(0) == dev0 && mockhip::outstanding(1) == host0 && mockhip::outstanding(2) == str0 && mockhip::outstanding(3) == ev0);
+    REQUIRE(Outstanding() == before);
 }
 
 int main(int argc, char** argv) {

@@ -5,28 +5,8 @@
 // chunks of 1, 7 and n, pageable and page-locked arrays, optional outputs absent, the device form on a caller stream (which must not have run anything when the call
 // returns, under the lazy scheduler), plume_init_multi contexts over three and eight mock devices, empty items of a null buffer on one device and on several, argument errors, the stage lists, and every allocation of a call
 // failing in turn: an error code, untouched outputs, the outputs of a repeated call right, nothing leaked.  A context that only parses builds no table.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <string>
-#include <vector>
-
-#include "../../include/plume_hip.h"
-
-static std::string g_what;
-#define REQUIRE(c)                                                                                                                         \
-    do {                                                                                                                                   \
-        if (!(c)) { std::fprintf(stderr, "eth_tx_driver: %s:%d: %s   [%s] (%s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-
-static std::mt19937_64 rng;
-constexpr uint8_t kFill = 0xAA;
-
-static bool all_of(const uint8_t* p, size_t bytes, uint8_t v) { for (size_t i = 0; i < bytes; i++) if (p[i] != v) return false; return true; }
+#define DRIVER_NAME "eth_tx_driver"
+#include "driver_prelude.h"
 
 static size_t g_n;
 static std::vector<uint64_t> g_off;
@@ -46,23 +26,10 @@ static void read_vectors(const char* path) {
     std::fclose(f);
 }
 
-struct Arr {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    int kind;                                             // 0 pageable, 1 page-locked, 2 device
-    Arr(size_t b, int k, const void* src = nullptr) : bytes(b), kind(k) {
-        if (k == 2) REQUIRE(hipMalloc((void**)&p, b ? b : 1) == hipSuccess); else p = (uint8_t*)(k ? plume_host_alloc(b ? b : 1) : std::malloc(b ? b : 1));
-        REQUIRE(p);
-        if (src) std::memcpy(p, src, b); else std::memset(p, kFill, b);
-    }
-    ~Arr() { if (kind == 2) (void)hipFree(p); else if (kind) plume_host_free(p); else std::free(p); }
-    Arr(const Arr&) = delete;
-    Arr& operator=(const Arr&) = delete;
-    bool untouched() const { return all_of(p, bytes, kFill); }
-    void want(bool given, const std::vector<uint8_t>& ref, size_t width, size_t lo, size_t n) const {
-        if (given) REQUIRE(std::memcmp(p, ref.data() + width * lo, width * n) == 0); else REQUIRE(untouched());
-    }
-};
+// an output given to the call holds items [lo, lo + n) of ref; one not given is untouched
+static void want(const Arr& a, bool given, const std::vector<uint8_t>& ref, size_t width, size_t lo, size_t n) {
+    if (given) REQUIRE(std::memcmp(a.p, ref.data() + width * lo, width * n) == 0); else REQUIRE(a.untouched());
+}
 
 // items [lo, lo + n).  The host forms get the whole offsets array from `lo` on (absolute offsets into the whole buffer); the device forms a buffer and offsets of their own
 struct Call {
@@ -98,12 +65,12 @@ struct Call {
     }
     void check() const {                                  // (the mock's device memory is host memory)
         if (!sender) {
-            hash.want(true, g_hash, 32, lo, n); r.want(true, g_r, 32, lo, n); s.want(true, g_s, 32, lo, n); v.want(true, g_v, 1, lo, n);
-            chain.want(outs & 1, g_chain, 8, lo, n); type.want(outs & 2, g_type, 1, lo, n); status.want(outs & 4, g_status, 1, lo, n);
+            want(hash, true, g_hash, 32, lo, n); want(r, true, g_r, 32, lo, n); want(s, true, g_s, 32, lo, n); want(v, true, g_v, 1, lo, n);
+            want(chain, outs & 1, g_chain, 8, lo, n); want(type, outs & 2, g_type, 1, lo, n); want(status, outs & 4, g_status, 1, lo, n);
             REQUIRE(pk.untouched() && addr.untouched());
         } else {
-            pk.want(outs & 1, g_pk, 64, lo, n); addr.want(outs & 2, g_addr, 20, lo, n); status.want(outs & 4, g_sstatus, 1, lo, n);
-            chain.want(outs & 8, g_chain, 8, lo, n); type.want(outs & 8, g_type, 1, lo, n);
+            want(pk, outs & 1, g_pk, 64, lo, n); want(addr, outs & 2, g_addr, 20, lo, n); want(status, outs & 4, g_sstatus, 1, lo, n);
+            want(chain, outs & 8, g_chain, 8, lo, n); want(type, outs & 8, g_type, 1, lo, n);
             REQUIRE(hash.untouched() && r.untouched() && s.untouched() && v.untouched());
         }
         REQUIRE(std::memcmp(txs.p, g_txs.data() + g_off[lo], bytes) == 0 && std::memcmp(off.p, rel.data(), 8 * (n + 1)) == 0 &&
@@ -161,14 +128,6 @@ static void group_null_buffer(plume_ctx* ctx, const char* what, size_t chunk) {
     REQUIRE(plume_set_chunk(ctx, (size_t)1 << 20) == 0);
 }
 
-static std::vector<std::string> stage_names(plume_ctx* ctx) {
-    const char* names[16]; float ms[16];
-    const int k = plume_last_stage_times(ctx, names, ms, 16);
-    std::vector<std::string> out;
-    for (int i = 0; i < k && i < 16; i++) out.push_back(names[i]);
-    return out;
-}
-
 static void group_stages_and_order(plume_ctx* ctx) {
     g_what = "stage lists; a sender and a parse back to back on one caller stream";
     hipStream_t st = nullptr;
@@ -177,10 +136,10 @@ static void group_stages_and_order(plume_ctx* ctx) {
     Call a(true, 3, 40, 31, 2), b(false, 0, g_n, 7, 2);
     REQUIRE(a.run(ctx, st) == 0);
     REQUIRE(hipStreamSynchronize(st) == hipSuccess);
-    REQUIRE((stage_names(ctx) == std::vector<std::string>{"eth_tx_parse", "ecdsa_prepare", "tables", "ecdsa_mul", "to_affine", "ecdsa_finalize"}));
+    REQUIRE((last_stage_names(ctx) == std::vector<std::string>{"eth_tx_parse", "ecdsa_prepare", "tables", "ecdsa_mul", "to_affine", "ecdsa_finalize"}));
     REQUIRE(b.run(ctx, st) == 0);
     REQUIRE(hipStreamSynchronize(st) == hipSuccess);
-    REQUIRE((stage_names(ctx) == std::vector<std::string>{"eth_tx_parse"}));
+    REQUIRE((last_stage_names(ctx) == std::vector<std::string>{"eth_tx_parse"}));
     REQUIRE(plume_set_stage_timing(ctx, 0) == 0);
     a.check(); b.check();
     Call c(true, 10, 33, 7, 2), d(true, 50, 20, 23, 2), e(false, 7, 90, 5, 2);
@@ -236,7 +195,7 @@ static void group_arguments(plume_ctx* ctx) {
 
 // every allocation of one host-form call fails in turn
 static void group_failing_allocations(bool sender) {
-    const long dev0 = mockhip::outstanding(0), host0 = mockhip::outstanding(1), str0 = mockhip::outstanding(2), ev0 = mockhip::outstanding(3);
+    const Outstanding before;
     plume_ctx* ctx = nullptr;
     REQUIRE(plume_init(&ctx, 0) == 0);
     (void)mockhip::fail_allocation(-1);
@@ -256,7 +215,7 @@ static void group_failing_allocations(bool sender) {
         c.check();
         plume_destroy(ctx);
     }
-    REQUIRE(mockhip::outstanding(0) == dev0 && mockhip::outstanding(1) == host0 && mockhip::outstanding(2) == str0 && mockhip::outstanding(3) == ev0);
+    REQUIRE(Outstanding() == before);
 }
 
 int main(int argc, char** argv) {

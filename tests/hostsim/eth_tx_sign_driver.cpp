@@ -7,30 +7,13 @@
 // anything when the call returns, under the lazy scheduler); the self-check on with the stage list of the header; plume_init_multi contexts over two and eight mock devices;
 // argument errors, offsets that decrease in a later piece or shard than the first among them (nothing staged, nothing written); then every allocation of a call fails in turn -- an error code, `out` untouched, a repeated call right, nothing leaked; and after every call, failed ones
 // included, no device allocation holds a key or a hedging input of the batch.
-#include <hip/hip_runtime.h>
-
 #include <array>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
 #include <set>
-#include <string>
-#include <vector>
 
-#include "../../include/plume_hip.h"
+#define DRIVER_NAME "eth_tx_sign_driver"
+#include "driver_prelude.h"
 
-static std::string g_what;
-#define REQUIRE(c)                                                                                                                               \
-    do {                                                                                                                                         \
-        if (!(c)) { std::fprintf(stderr, "eth_tx_sign_driver: %s:%d: %s   [%s] (%s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-
-static std::mt19937_64 rng;
-constexpr uint8_t kFill = 0xAA;
 constexpr size_t kGrow = PLUME_ETH_TX_SIGN_GROWTH;
-static bool all_of(const uint8_t* p, size_t bytes, uint8_t v) { for (size_t i = 0; i < bytes; i++) if (p[i] != v) return false; return true; }
 
 struct Want { std::vector<uint8_t> out, out_len, st, hash, r, s, v, chain, type; };
 static size_t g_n = 0;
@@ -55,20 +38,6 @@ static void read_vectors(const char* path) {
     std::fclose(f);
 }
 static size_t slot_at(size_t lo, size_t i) { return (size_t)(g_off[i] - g_off[lo]) + kGrow * (i - lo); }     // of item i in a call that starts at item lo
-
-struct Arr {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    int kind;                                             // 0 pageable, 1 page-locked, 2 device
-    Arr(size_t b, int k, const void* src = nullptr) : bytes(b), kind(k) {
-        if (k == 2) REQUIRE(hipMalloc((void**)&p, b ? b : 1) == hipSuccess); else p = (uint8_t*)(k ? plume_host_alloc(b ? b : 1) : std::malloc(b ? b : 1));
-        REQUIRE(p);
-        if (src) std::memcpy(p, src, b); else std::memset(p, kFill, b);
-    }
-    ~Arr() { if (kind == 2) (void)hipFree(p); else if (kind) plume_host_free(p); else std::free(p); }
-    Arr(const Arr&) = delete;
-    Arr& operator=(const Arr&) = delete;
-};
 
 // no device allocation other than the caller's own holds a key or a hedging input of the batch at a 32-byte boundary: the staged copies were wiped
 using Rec = std::array<uint8_t, 32>;
@@ -157,12 +126,10 @@ static std::vector<std::string> stages_of_a_device_call(plume_ctx* ctx) {
     Call c(0, g_n, false, true, 2);
     REQUIRE(c.run(ctx, st) == 0 && hipStreamSynchronize(st) == hipSuccess);
     c.check();
-    const char* names[64]; float ms[64];
-    const int k = plume_last_stage_times(ctx, names, ms, 64);
-    REQUIRE(k > 0 && k <= 64);
+    const std::vector<std::string> names = last_stage_names(ctx);
     REQUIRE(plume_set_stage_timing(ctx, 0) == 0);
     REQUIRE(hipStreamDestroy(st) == hipSuccess);
-    return std::vector<std::string>(names, names + k);
+    return names;
 }
 
 // Offsets that decrease in a LATER piece or shard than the first, which is sound on its own.  `out` is sized as the header says, from tx_off[n] - tx_off[0], in a pageable
@@ -217,7 +184,7 @@ static void group_failing_allocations() {
     plume_ctx* keeper = nullptr;                                                     // keeps the device's shared tables alive: the counted calls build none
     REQUIRE(plume_init(&keeper, 0) == 0);
     { g_what = "allocations: tables"; Call c(0, 8, false, true, 0); REQUIRE(c.run(keeper, nullptr) == 0); c.check(); }
-    const long dev0 = mockhip::outstanding(0), host0 = mockhip::outstanding(1), str0 = mockhip::outstanding(2), ev0 = mockhip::outstanding(3);
+    const Outstanding before;
     for (int selfcheck = 0; selfcheck < 2; selfcheck++) {
         plume_ctx* ctx = nullptr;
         REQUIRE(plume_init(&ctx, 0) == 0 && plume_set_sign_selfcheck(ctx, selfcheck) == 0 && plume_set_chunk(ctx, 33) == 0);
@@ -239,7 +206,7 @@ static void group_failing_allocations() {
             plume_destroy(ctx);
         }
     }
-    REQUIRE(mockhip::outstanding(0) == dev0 && mockhip::outstanding(1) == host0 && mockhip::outstanding(2) == str0 && mockhip::outstanding(3) == ev0);
+    REQUIRE(Outstanding() == before);
     plume_destroy(keeper);
 }
 

@@ -7,30 +7,12 @@
 // the call returns, under the lazy scheduler); the uniform levels; sub-batches; the stage lists; plume_init_multi contexts over two and eight mock devices; argument
 // errors; then every allocation of a call fails in turn -- an error code, a repeated call right, nothing leaked; and after every call no device allocation other than the
 // caller's own holds a key or a chain code of the batch, going in or coming out.
-#include <hip/hip_runtime.h>
-
 #include <array>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <mutex>
-#include <random>
 #include <set>
-#include <string>
-#include <vector>
 
-#include "../../include/plume_hip.h"
-
-static std::string g_what;
-#define REQUIRE(c)                                                                                                                     \
-    do {                                                                                                                               \
-        if (!(c)) { std::fprintf(stderr, "hd_driver: %s:%d: %s   [%s] (%s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-
-static std::mt19937_64 rng;
-constexpr uint8_t kFill = 0xAA;
-static bool all_of(const uint8_t* p, size_t bytes, uint8_t v) { for (size_t i = 0; i < bytes; i++) if (p[i] != v) return false; return true; }
+#define DRIVER_NAME "hd_driver"
+#include "driver_prelude.h"
 
 static size_t g_n = 0, g_depth = 0, g_seed_len = 0;
 static std::vector<uint8_t> g_sk, g_chain, g_path, g_pk, g_ppath, g_seeds;
@@ -56,20 +38,6 @@ static void read_vectors(const char* path) {
     REQUIRE(std::fread(&extra, 1, 1, f) == 0);
     std::fclose(f);
 }
-
-struct Arr {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    int kind;                                             // 0 pageable, 1 page-locked, 2 device
-    Arr(size_t b, int k, const void* src = nullptr) : bytes(b), kind(k) {
-        if (k == 2) REQUIRE(hipMalloc((void**)&p, b ? b : 1) == hipSuccess); else p = (uint8_t*)(k ? plume_host_alloc(b ? b : 1) : std::malloc(b ? b : 1));
-        REQUIRE(p);
-        if (src) std::memcpy(p, src, b); else std::memset(p, kFill, b);
-    }
-    ~Arr() { if (kind == 2) (void)hipFree(p); else if (kind) plume_host_free(p); else std::free(p); }
-    Arr(const Arr&) = delete;
-    Arr& operator=(const Arr&) = delete;
-};
 
 // no device allocation but the caller's own (skip) holds a key or a chain code of the batch: the staging and the workspace are wiped behind every call
 using Rec = std::array<uint8_t, 32>;
@@ -192,12 +160,10 @@ static std::vector<std::string> stages_of_a_device_call(plume_ctx* ctx, bool pub
     Call c(pub, 0, 0, g_n, 2, 7, pub ? g_pub : g_priv);
     REQUIRE(c.run(ctx, st) == 0 && hipStreamSynchronize(st) == hipSuccess);
     c.check();
-    const char* names[64]; float ms[64];
-    const int k = plume_last_stage_times(ctx, names, ms, 64);
-    REQUIRE(k > 0 && k <= 64);
+    const std::vector<std::string> names = last_stage_names(ctx);
     REQUIRE(plume_set_stage_timing(ctx, 0) == 0);
     REQUIRE(hipStreamDestroy(st) == hipSuccess);
-    return std::vector<std::string>(names, names + k);
+    return names;
 }
 
 static void group_arguments(plume_ctx* ctx) {
@@ -236,7 +202,7 @@ static void group_failing_allocations() {
     plume_ctx* keeper = nullptr;                                                     // keeps the device's shared tables alive: the counted calls build none
     REQUIRE(plume_init(&keeper, 0) == 0);
     { g_what = "allocations: tables"; Call c(false, 0, 0, 8, 0, 7, g_priv); REQUIRE(c.run(keeper, nullptr) == 0); c.check(); }
-    const long dev0 = mockhip::outstanding(0), host0 = mockhip::outstanding(1), str0 = mockhip::outstanding(2), ev0 = mockhip::outstanding(3);
+    const Outstanding before;
     for (int which = 0; which < 2; which++) {
         const bool pub = which == 1;
         const int flags = pub ? 0 : PLUME_HD_SHARED_PARENT;
@@ -262,7 +228,7 @@ static void group_failing_allocations() {
             plume_destroy(ctx);
         }
     }
-    REQUIRE(mockhip::outstanding(0) == dev0 && mockhip::outstanding(1) == host0 && mockhip::outstanding(2) == str0 && mockhip::outstanding(3) == ev0);
+    REQUIRE(Outstanding() == before);
     plume_destroy(keeper);
 }
 

@@ -6,27 +6,8 @@
 // a caller stream (which must not have run anything when the calls return, under the lazy scheduler); plume_init_multi contexts over three and eight mock devices (leaf
 // and verify split over the shards, build and proofs run on the first); argument errors; then every allocation of a build, a proof and a verify call fails in turn: an
 // error code, the outputs of a repeated call right, nothing leaked.  A context that only ever did this builds no table.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <string>
-#include <vector>
-
-#include "../../include/plume_hip.h"
-
-static std::string g_what;
-#define REQUIRE(c)                                                                                                                         \
-    do {                                                                                                                                   \
-        if (!(c)) { std::fprintf(stderr, "merkle_driver: %s:%d: %s   [%s] (%s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-
-static std::mt19937_64 rng;
-constexpr uint8_t kFill = 0xAA;
-static bool all_of(const uint8_t* p, size_t bytes, uint8_t v) { for (size_t i = 0; i < bytes; i++) if (p[i] != v) return false; return true; }
+#define DRIVER_NAME "merkle_driver"
+#include "driver_prelude.h"
 
 struct Tree {
     uint32_t leaf_format = 0, addr_format = 0, sort = 0, n = 0, depth = 0;
@@ -60,21 +41,7 @@ static void read_vectors(const char* path) {
     std::fclose(f);
 }
 
-struct Arr {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    int kind;                                             // 0 pageable, 1 page-locked, 2 device
-    Arr(size_t b, int k, const void* src = nullptr) : bytes(b), kind(k) {
-        if (k == 2) REQUIRE(hipMalloc((void**)&p, b ? b : 1) == hipSuccess); else p = (uint8_t*)(k ? plume_host_alloc(b ? b : 1) : std::malloc(b ? b : 1));
-        REQUIRE(p);
-        if (src) std::memcpy(p, src, b); else std::memset(p, kFill, b);
-    }
-    ~Arr() { if (kind == 2) (void)hipFree(p); else if (kind) plume_host_free(p); else std::free(p); }
-    Arr(const Arr&) = delete;
-    Arr& operator=(const Arr&) = delete;
-    bool untouched() const { return all_of(p, bytes, kFill); }
-    bool is(const std::vector<uint8_t>& v) const { return v.size() == bytes && (bytes == 0 || std::memcmp(p, v.data(), bytes) == 0); }
-};
+static bool is(const Arr& a, const std::vector<uint8_t>& v) { return v.size() == a.bytes && (a.bytes == 0 || std::memcmp(a.p, v.data(), a.bytes) == 0); }
 
 // the four calls over one tree of the vectors, each on arrays of its own; mutate: one bit of every proof is flipped before verify
 struct Chain {
@@ -116,9 +83,9 @@ struct Chain {
     }
     bool untouched() const { return leaf.untouched() && lst.untouched() && tree.untouched() && pos.untouched() && proof.untouched() && len.untouched() && vst.untouched(); }
     void check() {
-        REQUIRE(leaf.is(t.leaves) && tree.is(t.tree) && proof.is(t.proofs) && len.is(t.proof_len) && vst.is(want_vst));
-        if (with_optional) REQUIRE(lst.is(t.leaf_status) && std::memcmp(pos.p, t.leaf_pos.data(), 4 * (size_t)t.n) == 0); else REQUIRE(lst.untouched() && pos.untouched());
-        REQUIRE(items.is(t.items) && (t.amounts.empty() || amounts.is(t.amounts)) && vproof.is(vproof0));
+        REQUIRE(is(leaf, t.leaves) && is(tree, t.tree) && is(proof, t.proofs) && is(len, t.proof_len) && is(vst, want_vst));
+        if (with_optional) REQUIRE(is(lst, t.leaf_status) && std::memcmp(pos.p, t.leaf_pos.data(), 4 * (size_t)t.n) == 0); else REQUIRE(lst.untouched() && pos.untouched());
+        REQUIRE(is(items, t.items) && (t.amounts.empty() || is(amounts, t.amounts)) && is(vproof, vproof0));
     }
 };
 
@@ -195,7 +162,7 @@ static void arguments(plume_ctx* ctx) {
 
 // every allocation of one host-form call fails in turn; which: 0 build, 1 proof, 2 verify, 3 leaf
 static void failing_allocations(int which) {
-    const long dev0 = mockhip::outstanding(0), host0 = mockhip::outstanding(1), str0 = mockhip::outstanding(2), ev0 = mockhip::outstanding(3);
+    const Outstanding before;
     const Tree* tp = nullptr;
     for (const Tree& t : g_trees) if (t.sort && t.n >= 13 && t.leaf_format == PLUME_MERKLE_LEAF_ADDRESS_UINT256) tp = &t;
     REQUIRE(tp);
@@ -205,8 +172,8 @@ static void failing_allocations(int which) {
              : which == 2 ? c.run_verify(ctx, nullptr, t.proof_len.data(), t.tree.data()) : c.run_leaf(ctx, nullptr);
     };
     auto right = [&](Chain& c) {
-        return which == 0 ? c.tree.is(t.tree) && std::memcmp(c.pos.p, t.leaf_pos.data(), 4 * (size_t)t.n) == 0 : which == 1 ? c.proof.is(t.proofs) && c.len.is(t.proof_len)
-             : which == 2 ? c.vst.is(c.want_vst) : c.leaf.is(t.leaves) && c.lst.is(t.leaf_status);
+        return which == 0 ? is(c.tree, t.tree) && std::memcmp(c.pos.p, t.leaf_pos.data(), 4 * (size_t)t.n) == 0 : which == 1 ? is(c.proof, t.proofs) && is(c.len, t.proof_len)
+             : which == 2 ? is(c.vst, c.want_vst) : is(c.leaf, t.leaves) && is(c.lst, t.leaf_status);
     };
     plume_ctx* ctx = nullptr;
     REQUIRE(plume_init(&ctx, 0) == 0);
@@ -227,7 +194,7 @@ static void failing_allocations(int which) {
         REQUIRE(call(c, ctx) == 0 && right(c));                                         // the context is usable afterwards
         plume_destroy(ctx);
     }
-    REQUIRE(mockhip::outstanding(0) == dev0 && mockhip::outstanding(1) == host0 && mockhip::outstanding(2) == str0 && mockhip::outstanding(3) == ev0);
+    REQUIRE(Outstanding() == before);
 }
 
 int main(int argc, char** argv) {

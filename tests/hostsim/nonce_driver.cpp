@@ -4,19 +4,11 @@
 // device and on a plume_init_multi context over eight mock devices, pieces of 5-64 items, pageable and page-locked caller arrays (two lanes), the device form on a
 // caller stream, an allocation failure at every allocation of a derived-nonce call, argument errors.
 //   nonce_driver <seed>
-#include <hip/hip_runtime.h>
-
 #include <array>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
 #include <set>
-#include <string>
-#include <vector>
 
-#include "../../include/plume_hip.h"
+#define DRIVER_NAME "nonce_driver"
+#include "driver_prelude.h"
 #include "plume_nonce.h"
 
 extern "C" {
@@ -24,25 +16,7 @@ int oracle_sign_batch(int version, size_t n, const uint8_t* msgs, const uint64_t
                       uint8_t* nullifier, uint8_t* c, uint8_t* s, uint8_t* r_point, uint8_t* hashed_to_curve_r, uint8_t* h_out, uint8_t* status, int nthreads);
 }
 
-static std::string g_what;
-#define REQUIRE(c)                                                                                                                        \
-    do {                                                                                                                                  \
-        if (!(c)) { std::fprintf(stderr, "nonce_driver: %s:%d: %s   [%s] (%s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-
-static std::mt19937_64 rng;
 using Rec = std::array<uint8_t, 32>;
-
-// a caller array of exactly `bytes`: pageable heap memory or page-locked by the library's allocator
-struct Arr {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    bool pinned = false;
-    Arr(size_t b, bool pin) : bytes(b), pinned(pin) { p = (uint8_t*)(pin ? plume_host_alloc(b ? b : 1) : std::malloc(b ? b : 1)); REQUIRE(p); std::memset(p, 0xCD, b); }
-    ~Arr() { if (pinned) plume_host_free(p); else std::free(p); }
-    Arr(const Arr&) = delete;
-    Arr& operator=(const Arr&) = delete;
-};
 
 struct Batch {
     int version = 1;

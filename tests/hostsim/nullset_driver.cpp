@@ -5,26 +5,11 @@
 // a wrong answer or a sanitizer report.
 //   nullset_driver [seed]
 #include <array>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <map>
-#include <random>
 #include <set>
-#include <string>
-#include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "../../include/plume_hip.h"
-
-#define REQUIRE(c)                                                                                                           \
-    do {                                                                                                                     \
-        if (!(c)) { std::fprintf(stderr, "nullset_driver: %s:%d: %s   [%s] (last library error: %s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-static std::string g_what;
-static std::mt19937_64 rng;
+#define DRIVER_NAME "nullset_driver"
+#include "driver_prelude.h"
 
 using Rec = std::array<uint8_t, 64>;
 

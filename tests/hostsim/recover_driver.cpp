@@ -7,17 +7,8 @@
 // That is checked on one call per version (64-byte records, every output, host form); every other call -- the three formats, every subset of NULL outputs, pieces of 5-64
 // items, page-locked arrays, the device form on a caller stream, a plume_init_multi context over eight mock devices, two lanes in flight on two streams, sub_batches = 2 --
 // must reproduce those bytes, leave the arrays it was not given untouched, and report "recover_finalize" as its last stage.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <string>
-#include <vector>
-
-#include "../../include/plume_hip.h"
+#define DRIVER_NAME "recover_driver"
+#include "driver_prelude.h"
 
 extern "C" {
 int oracle_sign_batch(int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* sk, const uint8_t* r, const uint8_t* pk_in, uint8_t* pk,
@@ -29,21 +20,12 @@ int oracle_point_mul(const uint8_t k[32], const uint8_t p[64], uint8_t out[64]);
 size_t oracle_sec1_compress(const uint8_t p[64], uint8_t out[33]);
 }
 
-static std::string g_what;
-#define REQUIRE(c)                                                                                                                          \
-    do {                                                                                                                                    \
-        if (!(c)) { std::fprintf(stderr, "recover_driver: %s:%d: %s   [%s] (%s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-
-static std::mt19937_64 rng;
-constexpr uint8_t kFill = 0xAA;
 static const uint8_t kOrder[32] = {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFE,
                                    0xBA, 0xAE, 0xDC, 0xE6, 0xAF, 0x48, 0xA0, 0x3B, 0xBF, 0xD2, 0x5E, 0x8C, 0xD0, 0x36, 0x41, 0x41};
 static const uint8_t kG[64] = {0x79, 0xBE, 0x66, 0x7E, 0xF9, 0xDC, 0xBB, 0xAC, 0x55, 0xA0, 0x62, 0x95, 0xCE, 0x87, 0x0B, 0x07, 0x02, 0x9B, 0xFC, 0xDB, 0x2D, 0xCE,
                                0x28, 0xD9, 0x59, 0xF2, 0x81, 0x5B, 0x16, 0xF8, 0x17, 0x98, 0x48, 0x3A, 0xDA, 0x77, 0x26, 0xA3, 0xC4, 0x65, 0x5D, 0xA4, 0xFB, 0xFC,
                                0x0E, 0x11, 0x08, 0xA8, 0xFD, 0x17, 0xB4, 0x48, 0xA6, 0x85, 0x54, 0x19, 0x9C, 0x47, 0xD0, 0x8F, 0xFB, 0x10, 0xD4, 0xB8};
 
-static bool all_of(const uint8_t* p, size_t bytes, uint8_t v) { for (size_t i = 0; i < bytes; i++) if (p[i] != v) return false; return true; }
 static bool scalar_ok(const uint8_t* k) { return !all_of(k, 32, 0) && std::memcmp(k, kOrder, 32) < 0; }
 static bool point_ok(const uint8_t* p) {
     if (all_of(p, 64, 0)) return true;
@@ -152,20 +134,6 @@ static void pin(plume_ctx* ctx, Batch& b) {
     }
     if (n >= 60) REQUIRE(seen[0] && seen[1] && seen[3]);
 }
-
-struct Arr {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    int kind;                                             // 0 pageable, 1 page-locked, 2 device
-    Arr(size_t b, int k, const void* src = nullptr) : bytes(b), kind(k) {
-        if (k == 2) REQUIRE(hipMalloc((void**)&p, b ? b : 1) == hipSuccess); else p = (uint8_t*)(k ? plume_host_alloc(b ? b : 1) : std::malloc(b ? b : 1));
-        REQUIRE(p);
-        if (src) std::memcpy(p, src, b); else std::memset(p, kFill, b);
-    }
-    ~Arr() { if (kind == 2) (void)hipFree(p); else if (kind) plume_host_free(p); else std::free(p); }
-    Arr(const Arr&) = delete;
-    Arr& operator=(const Arr&) = delete;
-};
 
 struct Call {
     const Batch& b;

@@ -7,19 +7,11 @@
 // allocation failure at every allocation of a call.
 //   selfcheck_driver <seed>            the checks above
 //   selfcheck_driver <seed> prefill    for a build whose release launcher writes nothing: after every device-form call the caller's arrays still hold their pre-fill
-#include <hip/hip_runtime.h>
-
 #include <array>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
 #include <set>
-#include <string>
-#include <vector>
 
-#include "../../include/plume_hip.h"
+#define DRIVER_NAME "selfcheck_driver"
+#include "driver_prelude.h"
 
 extern "C" {
 int oracle_sign_batch(int version, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* sk, const uint8_t* r, const uint8_t* pk_in, uint8_t* pk,
@@ -29,26 +21,8 @@ int oracle_verify_non_zk_batch(int version, size_t n, const uint8_t* msgs, const
 size_t oracle_sec1_compress(const uint8_t p[64], uint8_t out[33]);
 }
 
-static std::string g_what;
-#define REQUIRE(c)                                                                                                                            \
-    do {                                                                                                                                      \
-        if (!(c)) { std::fprintf(stderr, "selfcheck_driver: %s:%d: %s   [%s] (%s)\n", __FILE__, __LINE__, #c, g_what.c_str(), plume_last_error()); std::exit(2); } \
-    } while (0)
-
-static std::mt19937_64 rng;
 static bool g_prefill_mode = false;
 using Rec = std::array<uint8_t, 32>;
-constexpr uint8_t kFill = 0xAA;
-
-struct Arr {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-    bool pinned = false;
-    Arr(size_t b, bool pin) : bytes(b), pinned(pin) { p = (uint8_t*)(pin ? plume_host_alloc(b ? b : 1) : std::malloc(b ? b : 1)); REQUIRE(p); std::memset(p, kFill, b); }
-    ~Arr() { if (pinned) plume_host_free(p); else std::free(p); }
-    Arr(const Arr&) = delete;
-    Arr& operator=(const Arr&) = delete;
-};
 
 struct Batch {
     int version = 1;

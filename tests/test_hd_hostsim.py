@@ -1,5 +1,4 @@
-"""plume_hd_*_batch* on the host side (csrc/plume_hd_capi.hip) under the sanitizers, on the CPU: the unchanged objects of the existing
-host-side harness (tests/hostsim/Makefile: plume_capi.hip against the mock HIP runtime, the other kernels as host loops, the C oracle) linked with the ABI's translation
+"""plume_hd_*_batch* on the host side (csrc/plume_hd_capi.hip) under the sanitizers, on the CPU (tests/_hostsim.py): the ABI's translation
 unit, the new kernels as host loops (tests/hostsim/hd_launch.cpp) and a driver (tests/hostsim/hd_driver.cpp) that pins every output to vectors this test writes from the
 restatement (tests/_hd.py): the host form with chunks that cut the batch into 1, 2 and many pieces and on sub-ranges; both SHARED flags -- a whole-call input that was
 advanced, or a shared secret parent that was wiped behind the first piece and not uploaded again, gives wrong bytes --; NULL optional outputs; the device form on a caller
@@ -7,45 +6,16 @@ stream; the uniform levels, sub-batches and the stage lists; plume_init_multi co
 in turn; and after every call, failed ones included, no device allocation but the caller's own holding a key or a chain code of the batch.  ASan + UBSan and TSan, lazy,
 random and eager schedulers: stand-alone programs, nothing is loaded into Python.  One mutant of the launcher, a finish that leaves a byte of a failed item's chain code,
 must fail the driver."""
-import os
-import shutil
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from tests import _hd as H
+from tests import _hostsim as S
 from tests import _keccak as K
 
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "zk-nullifier-sig_amd" / "csrc"
-HOSTSIM = ROOT / "tests" / "hostsim"
-FLAGS = ["-std=c++17", "-g", "-Wall", "-Wextra", "-Wno-unused-parameter", "-ffp-contract=off", "-DPLUME_GW=16", "-DPLUME_COMB_W=10", f"-I{HOSTSIM / 'mockhip'}", f"-I{CSRC}"]
-
-
-def _san_flags(san):
-    return [f"-fsanitize={san}", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if san else []
-
-
-def _build(out, san, launch_defs=()):
-    if not shutil.which("g++") or not shutil.which("make"):
-        pytest.skip("no g++ / make")
-    out.mkdir(parents=True, exist_ok=True)
-    subprocess.run(["make", "-C", str(HOSTSIM), f"OUT={out}", f"SAN={san}", "-j2", str(out / "capi.o"), str(out / "launch.o"), str(out / "oracle.o")],
-                   check=True, capture_output=True, text=True, timeout=1200)
-    flags = FLAGS + _san_flags(san)
-    units = [(["-x", "c++", "-O1", "-Werror"], CSRC / "plume_hd_capi.hip", "hcapi.o"), (["-O2", "-Werror", *launch_defs], HOSTSIM / "hd_launch.cpp", "hlaunch.o"),
-             (["-O1", "-Werror"], HOSTSIM / "hd_driver.cpp", "hdriver.o")]
-    procs = [subprocess.Popen(["g++", *extra, *flags, "-c", str(src), "-o", str(out / obj)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for extra, src, obj in units]
-    for p, (_, src, _) in zip(procs, units):
-        _, err = p.communicate(timeout=900)
-        assert p.returncode == 0, (src.name, err[-4000:])
-    exe = out / "hd_driver"
-    subprocess.run(["g++", *_san_flags(san), "-o", str(exe), *[str(out / o) for o in ("capi.o", "launch.o", "oracle.o", "hcapi.o", "hlaunch.o", "hdriver.o")], "-lpthread"],
-                   check=True, capture_output=True, text=True, timeout=600)
-    return exe
+UNITS = dict(driver="hd_driver", capi=["plume_hd_capi.hip"], launch=["hd_launch.cpp"])
 
 
 @pytest.fixture(scope="module")
@@ -78,28 +48,13 @@ def vectors(tmp_path_factory):
     return p
 
 
-def _run(exe, vectors, seed, sched):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1", TSAN_OPTIONS="halt_on_error=1")
-    for k in ("PLUME_MOCK_SCHED", "PLUME_SUB_BATCHES", "PLUME_SERIAL", "PLUME_STAGE_TIMES", "PLUME_OVERLAP_MIN", "PLUME_MSM_PAIR_MAX", "PLUME_INGEST_SPLIT_MAX", "PLUME_SIGN_SELFCHECK"):
-        env.pop(k, None)
-    if sched:
-        env["PLUME_MOCK_SCHED"] = sched
-    return subprocess.run([str(exe), str(vectors), str(seed)], capture_output=True, text=True, timeout=1500, env=env)
-
-
-def _ok(r, seed):
-    assert r.returncode == 0, (seed, r.stdout[-2000:], r.stderr[-4000:])
-    assert f"hd_driver seed {seed}: ok" in r.stdout
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "WARNING: ThreadSanitizer" not in r.stderr
-
-
-@pytest.mark.parametrize("san,runs", [("address,undefined", [(1, None), (2, "random:2"), (3, "eager")]), ("thread", [(4, "random:4")])])
+@pytest.mark.parametrize("san,runs", S.RUNS)
 def test_hd_host_side_under_sanitizers(tmp_path, vectors, san, runs):
-    exe = _build(tmp_path / "b", san)
+    exe = S.build(tmp_path / "b", san, **UNITS)
     for seed, sched in runs:
-        _ok(_run(exe, vectors, seed, sched), seed)
+        S.ok(S.run(exe, vectors, seed, sched=sched), "hd_driver", seed)
 
 
 def test_the_driver_fails_when_a_failed_item_is_not_zeroed(tmp_path, vectors):
-    r = _run(_build(tmp_path / "b", "", launch_defs=["-DHD_MUTANT_KEEPS_FAILED"]), vectors, 1, None)
+    r = S.run(S.build(tmp_path / "b", "", **UNITS, defs={"hd_launch.cpp": ["-DHD_MUTANT_KEEPS_FAILED"]}), vectors, 1)
     assert r.returncode != 0 and "hd_driver:" in r.stderr, (r.stdout[-500:], r.stderr[-1000:])

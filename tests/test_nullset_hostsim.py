@@ -1,57 +1,23 @@
-"""The persistent nullifier set's host side (csrc/plume_nullset_capi.hip) under the sanitizers, on the CPU: the unchanged objects of the existing host-side harness
-(tests/hostsim/Makefile: plume_capi.hip against the mock HIP runtime, the other kernels as host loops) linked with the set's translation unit, its kernels as host loops
-(tests/hostsim/nullset_launch.cpp) and a driver (tests/hostsim/nullset_driver.cpp) that checks every answer against a std::set: host and device forms, two caller streams,
+"""The persistent nullifier set's host side (csrc/plume_nullset_capi.hip) under the sanitizers, on the CPU (tests/_hostsim.py; no oracle): the set's
+translation unit, its kernels as host loops (tests/hostsim/nullset_launch.cpp) and a driver (tests/hostsim/nullset_driver.cpp) that checks every answer against a std::set: host and device forms, two caller streams,
 a multi-device context, a set outliving its context, destroy with work queued, an allocation failure at every allocation of a growing insert, argument errors.  Run under
 ASan + UBSan and under TSan with the mock's random stream scheduler; one mutant shows the harness notices a missing ordering."""
-import os
 import shutil
-import subprocess
-from pathlib import Path
 
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "zk-nullifier-sig_amd" / "csrc"
-HOSTSIM = ROOT / "tests" / "hostsim"
-FLAGS = ["-std=c++17", "-g", "-Wall", "-Wextra", "-Wno-unused-parameter", "-ffp-contract=off", "-DPLUME_GW=16", "-DPLUME_COMB_W=10", f"-I{HOSTSIM / 'mockhip'}"]
+from tests import _hostsim as H
+from tests._hostsim import CSRC, ROOT
 
-
-def _san_flags(san):
-    return [f"-fsanitize={san}", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if san else []
-
-
-def _build(out, san, nullset_capi=None, csrc=CSRC):
-    if not shutil.which("g++") or not shutil.which("make"):
-        pytest.skip("no g++ / make")
-    out.mkdir(parents=True, exist_ok=True)
-    subprocess.run(["make", "-C", str(HOSTSIM), f"OUT={out}", f"SAN={san}", "-j2", str(out / "capi.o"), str(out / "launch.o")], check=True, capture_output=True, text=True, timeout=1200)
-    flags = FLAGS + [f"-I{csrc}"] + _san_flags(san)
-    units = [(["-x", "c++", "-O1", "-Werror"], nullset_capi or CSRC / "plume_nullset_capi.hip", "nscapi.o"), (["-O2", "-Werror"], HOSTSIM / "nullset_launch.cpp", "nslaunch.o"),
-             (["-O1", "-Werror"], HOSTSIM / "nullset_driver.cpp", "nsdriver.o")]
-    for extra, src, obj in units:
-        subprocess.run(["g++", *extra, *flags, "-c", str(src), "-o", str(out / obj)], check=True, capture_output=True, text=True, timeout=600)
-    exe = out / "nullset_driver"
-    subprocess.run(["g++", *_san_flags(san), "-o", str(exe), *[str(out / o) for o in ("capi.o", "launch.o", "nscapi.o", "nslaunch.o", "nsdriver.o")], "-lpthread"],
-                   check=True, capture_output=True, text=True, timeout=600)
-    return exe
-
-
-def _run(exe, seed, sched):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1", TSAN_OPTIONS="halt_on_error=1")
-    if sched:
-        env["PLUME_MOCK_SCHED"] = sched
-    return subprocess.run([str(exe), str(seed)], capture_output=True, text=True, timeout=900, env=env)
+UNITS = dict(driver="nullset_driver", capi=["plume_nullset_capi.hip"], launch=["nullset_launch.cpp"], oracle=False)
 
 
 @pytest.mark.parametrize("san,runs", [("address,undefined", [(1, None), (2, "random:2"), (3, "random:3"), (4, "random:4"), (5, "eager")]),
                                       ("thread", [(6, "random:6"), (7, "random:7")])])
 def test_nullset_host_side_under_sanitizers(tmp_path, san, runs):
-    exe = _build(tmp_path / "b", san)
+    exe = H.build(tmp_path / "b", san, **UNITS)
     for seed, sched in runs:
-        r = _run(exe, seed, sched)
-        assert r.returncode == 0, (seed, sched, r.stdout[-2000:], r.stderr[-4000:])
-        assert f"nullset_driver seed {seed}: ok" in r.stdout
-        assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "WARNING: ThreadSanitizer" not in r.stderr
+        H.ok(H.run(exe, seed, sched=sched), "nullset_driver", seed)
 
 
 def test_the_driver_fails_when_an_operation_does_not_wait_for_the_previous_one(tmp_path):
@@ -64,6 +30,6 @@ def test_the_driver_fails_when_an_operation_does_not_wait_for_the_previous_one(t
     (tmp_path / "pkg" / "include").mkdir()
     shutil.copy(ROOT / "include" / "plume_hip.h", tmp_path / "pkg" / "include" / "plume_hip.h")
     (pkg / "plume_nullset_capi.hip").write_text(src.replace(old, ""))
-    exe = _build(tmp_path / "b", "", nullset_capi=pkg / "plume_nullset_capi.hip")
-    results = [_run(exe, seed, f"random:{seed}") for seed in (1, 2, 3)]
+    exe = H.build(tmp_path / "b", "", **UNITS, sources={"plume_nullset_capi.hip": pkg / "plume_nullset_capi.hip"})
+    results = [H.run(exe, seed, sched=f"random:{seed}") for seed in (1, 2, 3)]
     assert any(r.returncode != 0 for r in results), [r.stdout[-300:] for r in results]
