@@ -33,6 +33,108 @@ def library_path() -> Path:
     return Path(alt).resolve() if alt else _HERE / "libplume_hip.so"
 
 
+# ---------------------------------------------------------------------- the prototypes of include/plume_hip.h (ctypes only: no library is loaded here)
+# GROUPS: group -> (since, what).  A group's entry points may be missing from an older build selected through PLUME_HIP_LIB (A/B runs against an earlier round): _load
+# prototypes them only where the symbol exists and Engine._fn refuses the call in words (NullifierSet for its group).  "later" has no version of its own.
+GROUPS = {
+    "later": (None, "later entry points"),
+    "nullset": ((0, 7), "persistent nullifier set"),
+    "rfc6979": ((0, 8), "derived-nonce signer"),
+    "selfcheck": ((0, 9), "signer self-check"),
+    "recover": ((0, 10), "point recovery"),
+    "eth": ((0, 11), "Ethereum addresses"),
+    "ecdsa": ((0, 12), "ECDSA recovery"),
+    "ecdsa_sign": ((0, 13), "ECDSA signing"),
+    "eth_tx": ((0, 14), "transaction parsing"),
+    "merkle": ((0, 15), "Merkle trees"),
+    "eth_tx_sign": ((0, 16), "transaction signing"),
+    "hd": ((0, 17), "key derivation"),
+}
+_VOID = "void"          # a row's restype for a function that returns nothing (None in a row means: not given, ctypes' default c_int)
+
+# PROTOTYPES: name -> (restype, argtypes, group).  group None = every supported build has it (a missing one is ctypes' AttributeError at load); argtypes None = left unset
+PROTOTYPES = {}
+
+
+def _rows(group, *rows):
+    for name, args, *res in rows:
+        PROTOTYPES[name] = (res[0] if res else None, args, group)
+
+
+vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
+_rows(None,
+      ("plume_last_error", None, C.c_char_p), ("plume_version", None, C.c_char_p),
+      ("plume_microbench", [vp, i, i], C.c_double), ("plume_microbench_last_ticks", [C.POINTER(C.c_float)], C.c_double),
+      ("plume_init", [C.POINTER(C.c_void_p), i]), ("plume_init_multi", [C.POINTER(C.c_void_p), C.POINTER(C.c_int), i]),
+      ("plume_num_shards", [vp]), ("plume_shard_numa_node", [vp, i]),
+      ("plume_set_host_first_piece", [vp, sz]), ("plume_set_host_register_min", [vp, sz]), ("plume_set_host_tail_piece", [vp, sz]),
+      ("plume_host_alloc", [sz], C.c_void_p), ("plume_host_free", [vp]), ("plume_host_register", [vp, sz]), ("plume_host_unregister", [vp]),
+      ("plume_destroy", [vp]), ("plume_set_chunk", [vp, sz]), ("plume_set_sub_batches", [vp, i]), ("plume_set_in_flight", [vp, i]))
+# later entry points: an older build selected through PLUME_HIP_LIB (A/B runs against an earlier round) may lack them; the in-tree library must have them all (_load checks)
+_rows("later",
+      ("plume_set_sign_uniform", [vp, i]), ("plume_get_sign_uniform", [vp]), ("plume_set_host_lanes", [vp, i]), ("plume_set_eq1_short", [vp, i]),
+      ("plume_set_stage_timing", [vp, i]))
+_rows(None,
+      ("plume_get_eq1_short", [vp, C.POINTER(C.c_size_t)]), ("plume_last_msm_clock", [vp, C.POINTER(C.c_double)]), ("plume_last_msm_kernel", [vp], C.c_char_p),
+      ("plume_set_host_piece", [vp, sz]), ("plume_last_redo_tasks", [vp, C.POINTER(C.c_uint64)]),
+      ("plume_last_stage_times", [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i]),
+      ("plume_verify_batch", [vp, i, sz] + [vp] * 9), ("plume_verify_batch_sec1", [vp, i, sz] + [vp] * 9), ("plume_verify_non_zk_batch", [vp, i, sz] + [vp] * 9),
+      ("plume_verify_non_zk_batch_device", [vp, i, sz, vp, vp, sz] + [vp] * 8), ("plume_verify_batch_sec1_device", [vp, i, sz, vp, vp, sz] + [vp] * 8),
+      ("plume_sign_batch", [vp, i, sz] + [vp] * 12), ("plume_sign_batch_sec1", [vp, i, sz] + [vp] * 12),
+      ("plume_sign_batch_sec1_device", [vp, i, sz, vp, vp, sz] + [vp] * 11),
+      ("plume_nullifier_first_occurrence", [vp, sz, vp, vp, vp, vp, C.POINTER(C.c_uint64)]), ("plume_nullifier_first_occurrence_device", [vp, sz, vp, vp, vp, vp, vp, vp]),
+      ("plume_hash_to_curve_batch", [vp, sz] + [vp] * 4),
+      ("plume_verify_batch_device", [vp, i, sz, vp, vp, sz] + [vp] * 8), ("plume_sign_batch_device", [vp, i, sz, vp, vp, sz] + [vp] * 11),
+      ("plume_hash_to_curve_batch_device", [vp, sz, vp, vp, sz, vp, vp, vp]),
+      ("plume_h2c_intermediates_batch", [vp, sz, vp, vp, vp, i, vp, vp, vp, vp]), ("plume_h2c_intermediates_batch_device", [vp, sz, vp, vp, sz, vp, i, vp, vp, vp, vp, vp]),
+      ("plume_h2c_hints_batch", [vp, sz, vp, vp, vp, i, vp]), ("plume_h2c_hints_batch_device", [vp, sz, vp, vp, sz, vp, i, vp, vp]),
+      ("plume_registers_from_be", [sz, vp, vp]), ("plume_registers_from_be_device", [vp, sz, vp, vp, vp]),
+      ("plume_scalars_to_sec1_der_batch", [vp, sz, vp, vp, vp]), ("plume_scalars_to_sec1_der_batch_device", [vp, sz, vp, vp, vp, vp]),
+      ("plume_sec1_der_to_scalars", [sz, vp, vp, vp]), ("plume_sec1_der_to_scalars_checked", [vp, sz, vp, vp, vp]),
+      ("plume_aggregate_check", [vp, i, i, sz] + [vp] * 11),
+      ("plume_aggregate_check_device", [vp, i, i, sz, vp, vp, sz] + [vp] * 7 + [C.c_uint64, vp, vp, vp]))
+# the persistent nullifier set (library 0.7; an older build selected through PLUME_HIP_LIB lacks it: NullifierSet raises PlumeHipError then)
+_rows("nullset",
+      ("plume_nullset_create", [vp, sz, C.POINTER(C.c_void_p)]), ("plume_nullset_destroy", [vp], _VOID), ("plume_nullset_reserve", [vp, sz]), ("plume_nullset_clear", [vp]),
+      ("plume_nullset_size", [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]), ("plume_nullset_insert", [vp, sz, vp, vp, vp, vp, C.POINTER(C.c_uint64)]),
+      ("plume_nullset_contains", [vp, sz, vp, vp]), ("plume_nullset_export", [vp, sz, vp, C.POINTER(C.c_uint64)]),
+      ("plume_nullset_insert_device", [vp, sz, vp, vp, vp, vp, vp, vp]), ("plume_nullset_contains_device", [vp, sz, vp, vp, vp]))
+# derived signing nonces (library 0.8; Engine.sign_batch_rfc6979* raise PlumeHipError on an older build)
+_rows("rfc6979", ("plume_sign_batch_rfc6979", [vp, i, sz] + [vp] * 12), ("plume_sign_batch_rfc6979_device", [vp, i, sz, vp, vp, sz] + [vp] * 11))
+# the signer's self-check (library 0.9; Engine.set_sign_selfcheck raises PlumeHipError on an older build selected through PLUME_HIP_LIB)
+_rows("selfcheck", ("plume_set_sign_selfcheck", [vp, i]), ("plume_get_sign_selfcheck", [vp]))
+# point recovery (library 0.10; Engine.recover_batch* raise PlumeHipError on an older build selected through PLUME_HIP_LIB)
+_rows("recover", ("plume_recover_batch", [vp, i, i, sz] + [vp] * 10), ("plume_recover_batch_device", [vp, i, i, sz, vp, vp, sz] + [vp] * 9))
+# Ethereum addresses (library 0.11; Engine.eth_address_batch* raise PlumeHipError on an older build selected through PLUME_HIP_LIB)
+_rows("eth", ("plume_eth_address_batch", [vp, i, i, sz] + [vp] * 4), ("plume_eth_address_batch_device", [vp, i, i, sz] + [vp] * 5))
+# ECDSA public-key recovery (library 0.12; Engine.ecdsa_recover_batch* raise PlumeHipError on an older build selected through PLUME_HIP_LIB)
+_rows("ecdsa", ("plume_ecdsa_recover_batch", [vp, i, i, i, sz] + [vp] * 8), ("plume_ecdsa_recover_batch_device", [vp, i, i, i, sz] + [vp] * 9))
+# the digest a wallet signs and deterministic ECDSA signatures (library 0.13; Engine.eth_message_hash_batch* / ecdsa_sign_batch* raise PlumeHipError on an older build)
+_rows("ecdsa_sign",
+      ("plume_eth_message_hash_batch", [vp, i, sz] + [vp] * 3), ("plume_eth_message_hash_batch_device", [vp, i, sz, vp, vp, sz, vp, vp]),
+      ("plume_ecdsa_sign_batch", [vp, i, sz] + [vp] * 7), ("plume_ecdsa_sign_batch_device", [vp, i, sz] + [vp] * 8))
+# the senders of raw transactions (library 0.14; Engine.eth_tx_parse_batch* / eth_tx_sender_batch* raise PlumeHipError on an older build)
+_rows("eth_tx",
+      ("plume_eth_tx_parse_batch", [vp, sz] + [vp] * 9), ("plume_eth_tx_parse_batch_device", [vp, sz, vp, vp, sz] + [vp] * 8),
+      ("plume_eth_tx_sender_batch", [vp, i, i, i, sz] + [vp] * 8), ("plume_eth_tx_sender_batch_device", [vp, i, i, i, sz, vp, vp, sz] + [vp] * 7))
+# Keccak Merkle allow-lists (library 0.15; Engine.merkle_* raise PlumeHipError on an older build)
+_rows("merkle",
+      ("plume_merkle_leaf_batch", [vp, i, i, sz] + [vp] * 4), ("plume_merkle_leaf_batch_device", [vp, i, i, sz] + [vp] * 5),
+      ("plume_merkle_tree_build", [vp, i, sz] + [vp] * 3), ("plume_merkle_tree_build_device", [vp, i, sz] + [vp] * 4),
+      ("plume_merkle_proof_batch", [vp, sz, vp, sz, vp, sz, vp, vp]), ("plume_merkle_proof_batch_device", [vp, sz, vp, sz, vp, sz, vp, vp, vp]),
+      ("plume_merkle_verify_batch", [vp, i, i, sz, vp, vp, sz] + [vp] * 4), ("plume_merkle_verify_batch_device", [vp, i, i, sz, vp, vp, sz] + [vp] * 5),
+      ("plume_merkle_max_proof_len", [sz], C.c_void_p))                            # (a size_t: ctypes hands back None for 0)
+# signing raw transactions (library 0.16; Engine.eth_tx_sign_batch* raise PlumeHipError on an older build)
+_rows("eth_tx_sign",
+      ("plume_eth_tx_sign_batch", [vp, i, sz] + [vp] * 13), ("plume_eth_tx_sign_batch_device", [vp, i, sz, vp, vp, sz, vp, vp, vp, sz] + [vp] * 9),
+      ("plume_eth_tx_sign_out_bytes", [sz, C.c_uint64], C.c_void_p))                # (a size_t)
+# BIP-32 key derivation (library 0.17; Engine.hd_* raise PlumeHipError on an older build)
+_rows("hd",
+      ("plume_hd_master_batch", [vp, sz, vp, sz, vp, vp, vp]), ("plume_hd_master_batch_device", [vp, sz, vp, sz, vp, vp, vp, vp]),
+      ("plume_hd_derive_priv_batch", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 5), ("plume_hd_derive_priv_batch_device", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 6),
+      ("plume_hd_derive_pub_batch", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 4), ("plume_hd_derive_pub_batch_device", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 5))
+del vp, sz, i
+
 _lib = None
 
 
@@ -56,140 +158,14 @@ def _load():
         except Exception:
             pass
     lib = C.CDLL(str(p))
-    lib.plume_last_error.restype = C.c_char_p
-    lib.plume_version.restype = C.c_char_p
-    lib.plume_microbench.restype = C.c_double
-    lib.plume_microbench.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.plume_microbench_last_ticks.restype = C.c_double
-    lib.plume_microbench_last_ticks.argtypes = [C.POINTER(C.c_float)]
-    lib.plume_init.argtypes = [C.POINTER(C.c_void_p), C.c_int]
-    lib.plume_init_multi.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]
-    lib.plume_num_shards.argtypes = [C.c_void_p]
-    lib.plume_shard_numa_node.argtypes = [C.c_void_p, C.c_int]
-    lib.plume_set_host_first_piece.argtypes = [C.c_void_p, C.c_size_t]
-    lib.plume_set_host_register_min.argtypes = [C.c_void_p, C.c_size_t]
-    lib.plume_set_host_tail_piece.argtypes = [C.c_void_p, C.c_size_t]
-    lib.plume_host_alloc.restype = C.c_void_p
-    lib.plume_host_alloc.argtypes = [C.c_size_t]
-    lib.plume_host_free.argtypes = [C.c_void_p]
-    lib.plume_host_register.argtypes = [C.c_void_p, C.c_size_t]
-    lib.plume_host_unregister.argtypes = [C.c_void_p]
-    lib.plume_destroy.argtypes = [C.c_void_p]
-    lib.plume_set_chunk.argtypes = [C.c_void_p, C.c_size_t]
-    lib.plume_set_sub_batches.argtypes = [C.c_void_p, C.c_int]
-    lib.plume_set_in_flight.argtypes = [C.c_void_p, C.c_int]
-    # later entry points: an older build selected through PLUME_HIP_LIB (A/B runs against an earlier round) may lack them; the in-tree library must have them all (checked below)
-    for name, args in (("plume_set_sign_uniform", [C.c_void_p, C.c_int]), ("plume_get_sign_uniform", [C.c_void_p]), ("plume_set_host_lanes", [C.c_void_p, C.c_int]),
-                       ("plume_set_eq1_short", [C.c_void_p, C.c_int]), ("plume_set_stage_timing", [C.c_void_p, C.c_int])):
-        fn = getattr(lib, name, None)
-        if fn is not None:
+    for name, (res, args, group) in PROTOTYPES.items():
+        fn = getattr(lib, name) if group is None else getattr(lib, name, None)
+        if fn is None:
+            continue
+        if args is not None:
             fn.argtypes = args
-    lib.plume_get_eq1_short.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
-    lib.plume_last_msm_clock.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    lib.plume_last_msm_kernel.restype = C.c_char_p
-    lib.plume_last_msm_kernel.argtypes = [C.c_void_p]
-    lib.plume_set_host_piece.argtypes = [C.c_void_p, C.c_size_t]
-    lib.plume_last_redo_tasks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.plume_last_stage_times.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
-    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
-    lib.plume_verify_batch.argtypes = [vp, i, sz] + [vp] * 9
-    lib.plume_verify_batch_sec1.argtypes = [vp, i, sz] + [vp] * 9
-    lib.plume_verify_non_zk_batch.argtypes = [vp, i, sz] + [vp] * 9
-    lib.plume_verify_non_zk_batch_device.argtypes = [vp, i, sz, vp, vp, sz] + [vp] * 8
-    lib.plume_verify_batch_sec1_device.argtypes = [vp, i, sz, vp, vp, sz] + [vp] * 8
-    lib.plume_sign_batch.argtypes = [vp, i, sz] + [vp] * 12
-    lib.plume_sign_batch_sec1.argtypes = [vp, i, sz] + [vp] * 12
-    lib.plume_sign_batch_sec1_device.argtypes = [vp, i, sz, vp, vp, sz] + [vp] * 11
-    lib.plume_nullifier_first_occurrence.argtypes = [vp, sz, vp, vp, vp, vp, C.POINTER(C.c_uint64)]
-    lib.plume_nullifier_first_occurrence_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
-    lib.plume_hash_to_curve_batch.argtypes = [vp, sz] + [vp] * 4
-    lib.plume_verify_batch_device.argtypes = [vp, i, sz, vp, vp, sz] + [vp] * 8
-    lib.plume_sign_batch_device.argtypes = [vp, i, sz, vp, vp, sz] + [vp] * 11
-    lib.plume_hash_to_curve_batch_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp]
-    lib.plume_h2c_intermediates_batch.argtypes = [vp, sz, vp, vp, vp, i, vp, vp, vp, vp]
-    lib.plume_h2c_intermediates_batch_device.argtypes = [vp, sz, vp, vp, sz, vp, i, vp, vp, vp, vp, vp]
-    lib.plume_h2c_hints_batch.argtypes = [vp, sz, vp, vp, vp, i, vp]
-    lib.plume_h2c_hints_batch_device.argtypes = [vp, sz, vp, vp, sz, vp, i, vp, vp]
-    lib.plume_registers_from_be.argtypes = [sz, vp, vp]
-    lib.plume_scalars_to_sec1_der_batch.argtypes = [vp, sz, vp, vp, vp]
-    lib.plume_scalars_to_sec1_der_batch_device.argtypes = [vp, sz, vp, vp, vp, vp]
-    lib.plume_sec1_der_to_scalars.argtypes = [sz, vp, vp, vp]
-    lib.plume_sec1_der_to_scalars_checked.argtypes = [vp, sz, vp, vp, vp]
-    lib.plume_registers_from_be_device.argtypes = [vp, sz, vp, vp, vp]
-    lib.plume_aggregate_check.argtypes = [vp, i, i, sz] + [vp] * 11
-    lib.plume_aggregate_check_device.argtypes = [vp, i, i, sz, vp, vp, sz] + [vp] * 7 + [C.c_uint64, vp, vp, vp]
-    # the persistent nullifier set (library 0.7; an older build selected through PLUME_HIP_LIB lacks it: NullifierSet raises PlumeHipError then)
-    for name, args, res in (("plume_nullset_create", [vp, sz, C.POINTER(C.c_void_p)], i), ("plume_nullset_destroy", [vp], None), ("plume_nullset_reserve", [vp, sz], i),
-                            ("plume_nullset_clear", [vp], i), ("plume_nullset_size", [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], i),
-                            ("plume_nullset_insert", [vp, sz, vp, vp, vp, vp, C.POINTER(C.c_uint64)], i), ("plume_nullset_contains", [vp, sz, vp, vp], i),
-                            ("plume_nullset_export", [vp, sz, vp, C.POINTER(C.c_uint64)], i), ("plume_nullset_insert_device", [vp, sz, vp, vp, vp, vp, vp, vp], i),
-                            ("plume_nullset_contains_device", [vp, sz, vp, vp, vp], i)):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = args, res
-    # derived signing nonces (library 0.8; Engine.sign_batch_rfc6979* raise PlumeHipError on an older build)
-    for name, args in (("plume_sign_batch_rfc6979", [vp, i, sz] + [vp] * 12), ("plume_sign_batch_rfc6979_device", [vp, i, sz, vp, vp, sz] + [vp] * 11)):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = args
-    # the signer's self-check (library 0.9; Engine.set_sign_selfcheck raises PlumeHipError on an older build selected through PLUME_HIP_LIB)
-    for name, args in (("plume_set_sign_selfcheck", [vp, i]), ("plume_get_sign_selfcheck", [vp])):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = args
-    # point recovery (library 0.10; Engine.recover_batch* raise PlumeHipError on an older build selected through PLUME_HIP_LIB)
-    for name, args in (("plume_recover_batch", [vp, i, i, sz] + [vp] * 10), ("plume_recover_batch_device", [vp, i, i, sz, vp, vp, sz] + [vp] * 9)):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = args
-    # Ethereum addresses (library 0.11; Engine.eth_address_batch* raise PlumeHipError on an older build selected through PLUME_HIP_LIB)
-    for name, args in (("plume_eth_address_batch", [vp, i, i, sz] + [vp] * 4), ("plume_eth_address_batch_device", [vp, i, i, sz] + [vp] * 5)):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = args
-    # ECDSA public-key recovery (library 0.12; Engine.ecdsa_recover_batch* raise PlumeHipError on an older build selected through PLUME_HIP_LIB)
-    for name, args in (("plume_ecdsa_recover_batch", [vp, i, i, i, sz] + [vp] * 8), ("plume_ecdsa_recover_batch_device", [vp, i, i, i, sz] + [vp] * 9)):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = args
-    # the digest a wallet signs and deterministic ECDSA signatures (library 0.13; Engine.eth_message_hash_batch* / ecdsa_sign_batch* raise PlumeHipError on an older build)
-    for name, args in (("plume_eth_message_hash_batch", [vp, i, sz] + [vp] * 3), ("plume_eth_message_hash_batch_device", [vp, i, sz, vp, vp, sz, vp, vp]),
-                       ("plume_ecdsa_sign_batch", [vp, i, sz] + [vp] * 7), ("plume_ecdsa_sign_batch_device", [vp, i, sz] + [vp] * 8)):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = args
-    # the senders of raw transactions (library 0.14; Engine.eth_tx_parse_batch* / eth_tx_sender_batch* raise PlumeHipError on an older build)
-    for name, args in (("plume_eth_tx_parse_batch", [vp, sz] + [vp] * 9), ("plume_eth_tx_parse_batch_device", [vp, sz, vp, vp, sz] + [vp] * 8),
-                       ("plume_eth_tx_sender_batch", [vp, i, i, i, sz] + [vp] * 8), ("plume_eth_tx_sender_batch_device", [vp, i, i, i, sz, vp, vp, sz] + [vp] * 7)):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = args
-    # Keccak Merkle allow-lists (library 0.15; Engine.merkle_* raise PlumeHipError on an older build)
-    for name, args in (("plume_merkle_leaf_batch", [vp, i, i, sz] + [vp] * 4), ("plume_merkle_leaf_batch_device", [vp, i, i, sz] + [vp] * 5),
-                       ("plume_merkle_tree_build", [vp, i, sz] + [vp] * 3), ("plume_merkle_tree_build_device", [vp, i, sz] + [vp] * 4),
-                       ("plume_merkle_proof_batch", [vp, sz, vp, sz, vp, sz, vp, vp]), ("plume_merkle_proof_batch_device", [vp, sz, vp, sz, vp, sz, vp, vp, vp]),
-                       ("plume_merkle_verify_batch", [vp, i, i, sz, vp, vp, sz] + [vp] * 4), ("plume_merkle_verify_batch_device", [vp, i, i, sz, vp, vp, sz] + [vp] * 5)):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = args
-    fn = getattr(lib, "plume_merkle_max_proof_len", None)
-    if fn is not None:
-        fn.argtypes, fn.restype = [sz], C.c_void_p                                 # (a size_t: ctypes hands back None for 0)
-    # signing raw transactions (library 0.16; Engine.eth_tx_sign_batch* raise PlumeHipError on an older build)
-    for name, args in (("plume_eth_tx_sign_batch", [vp, i, sz] + [vp] * 13), ("plume_eth_tx_sign_batch_device", [vp, i, sz, vp, vp, sz, vp, vp, vp, sz] + [vp] * 9)):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = args
-    fn = getattr(lib, "plume_eth_tx_sign_out_bytes", None)
-    if fn is not None:
-        fn.argtypes, fn.restype = [sz, C.c_uint64], C.c_void_p                     # (a size_t)
-    # BIP-32 key derivation (library 0.17; Engine.hd_* raise PlumeHipError on an older build)
-    for name, args in (("plume_hd_master_batch", [vp, sz, vp, sz, vp, vp, vp]), ("plume_hd_master_batch_device", [vp, sz, vp, sz, vp, vp, vp, vp]),
-                       ("plume_hd_derive_priv_batch", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 5), ("plume_hd_derive_priv_batch_device", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 6),
-                       ("plume_hd_derive_pub_batch", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 4), ("plume_hd_derive_pub_batch_device", [vp, i, i, i, sz, vp, vp, vp, sz] + [vp] * 5)):
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = args
+        if res is not None:
+            fn.restype = None if res is _VOID else res
     _lib = lib
     # (the 0.13 entry points are told by their symbols: plume_version() still begins "plume_hip 0.12")
     if (_version(lib) < (0, 12) or getattr(lib, "plume_ecdsa_sign_batch", None) is None) and not os.environ.get("PLUME_HIP_LIB"):
@@ -200,23 +176,7 @@ def _load():
 
 def exported_symbols():
     """every entry point include/plume_hip.h declares (used by the CPU-side ABI test)"""
-    return ["plume_set_stage_timing", "plume_set_in_flight", "plume_set_sign_uniform", "plume_get_sign_uniform", "plume_set_host_lanes", "plume_set_eq1_short", "plume_get_eq1_short", "plume_last_msm_kernel", "plume_last_msm_clock", "plume_last_redo_tasks", "plume_h2c_hints_batch", "plume_h2c_hints_batch_device", "plume_shard_numa_node", "plume_set_sub_batches", "plume_aggregate_check", "plume_aggregate_check_device", "plume_init_multi", "plume_num_shards", "plume_set_host_first_piece", "plume_set_host_register_min", "plume_set_host_tail_piece", "plume_host_alloc", "plume_host_free", "plume_host_register",
-            "plume_host_unregister", "plume_verify_non_zk_batch", "plume_verify_non_zk_batch_device", "plume_h2c_intermediates_batch", "plume_h2c_intermediates_batch_device",
-            "plume_registers_from_be", "plume_registers_from_be_device", "plume_scalars_to_sec1_der_batch", "plume_scalars_to_sec1_der_batch_device", "plume_sec1_der_to_scalars", "plume_sec1_der_to_scalars_checked",
-            "plume_init", "plume_destroy", "plume_last_error", "plume_version", "plume_set_chunk", "plume_set_host_piece", "plume_verify_batch", "plume_verify_batch_sec1", "plume_verify_batch_sec1_device", "plume_sign_batch", "plume_sign_batch_sec1", "plume_sign_batch_sec1_device",
-            "plume_hash_to_curve_batch", "plume_nullifier_first_occurrence", "plume_nullifier_first_occurrence_device", "plume_verify_batch_device", "plume_sign_batch_device", "plume_hash_to_curve_batch_device",
-            "plume_last_stage_times", "plume_microbench", "plume_microbench_last_ticks",
-            "plume_nullset_create", "plume_nullset_destroy", "plume_nullset_reserve", "plume_nullset_clear", "plume_nullset_size", "plume_nullset_insert", "plume_nullset_contains",
-            "plume_nullset_export", "plume_nullset_insert_device", "plume_nullset_contains_device", "plume_sign_batch_rfc6979", "plume_sign_batch_rfc6979_device",
-            "plume_set_sign_selfcheck", "plume_get_sign_selfcheck", "plume_recover_batch", "plume_recover_batch_device",
-            "plume_eth_address_batch", "plume_eth_address_batch_device", "plume_ecdsa_recover_batch", "plume_ecdsa_recover_batch_device",
-            "plume_eth_message_hash_batch", "plume_eth_message_hash_batch_device", "plume_ecdsa_sign_batch", "plume_ecdsa_sign_batch_device",
-            "plume_eth_tx_parse_batch", "plume_eth_tx_parse_batch_device", "plume_eth_tx_sender_batch", "plume_eth_tx_sender_batch_device",
-            "plume_merkle_max_proof_len", "plume_merkle_leaf_batch", "plume_merkle_leaf_batch_device", "plume_merkle_tree_build", "plume_merkle_tree_build_device",
-            "plume_merkle_proof_batch", "plume_merkle_proof_batch_device", "plume_merkle_verify_batch", "plume_merkle_verify_batch_device",
-            "plume_eth_tx_sign_out_bytes", "plume_eth_tx_sign_batch", "plume_eth_tx_sign_batch_device",
-            "plume_hd_master_batch", "plume_hd_master_batch_device", "plume_hd_derive_priv_batch", "plume_hd_derive_priv_batch_device",
-            "plume_hd_derive_pub_batch", "plume_hd_derive_pub_batch_device"]
+    return list(PROTOTYPES)
 
 
 def pack_messages(msgs):
@@ -237,6 +197,24 @@ def _np(a, width, n, name):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _ragged(msgs, msg_off):
+    """(n, msgs, msg_off) of a ragged input as pack_messages returns it: contiguous uint8 bytes and n + 1 uint64 offsets"""
+    msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+    return len(msg_off) - 1, np.ascontiguousarray(msgs, dtype=np.uint8), msg_off
+
+
+_SIGN_OUTPUTS = ("pk", "nullifier", "c", "s", "r_point", "hashed_to_curve_r", "status")      # in the order the sign calls take them
+
+
+def _sign_outputs(n, width, out=None):
+    """what a sign call writes: the caller's dict `out` as it is, or fresh arrays -- six records and the status; width: bytes per point record (64, or 33 for SEC1)"""
+    if out is not None:
+        return out
+    o = {k: np.zeros((n, 32 if k in ("c", "s") else width), dtype=np.uint8) for k in _SIGN_OUTPUTS[:6]}
+    o["status"] = np.zeros(n, dtype=np.uint8)
+    return o
 
 
 AGG_RESULT_BYTES = 72
@@ -380,6 +358,26 @@ class Engine:
         if rc != 0:
             raise PlumeHipError(f"{what} failed ({rc}): {self._lib.plume_last_error().decode()}")
 
+    def _fn(self, name):
+        """the entry point `name`, or PlumeHipError where this build lacks its group (GROUPS).  Up to 0.12 the version string counts too; the later groups are told by
+        their symbols alone: plume_version() still begins "plume_hip 0.12" """
+        since, what = GROUPS.get(PROTOTYPES[name][2], (None, None))
+        if since is None:
+            return getattr(self._lib, name)            # no group, or "later": a missing one is ctypes' AttributeError
+        fn = getattr(self._lib, name, None)
+        by_version = since <= (0, 12)
+        if fn is None or (by_version and _version(self._lib) < since):
+            how = f"needs plume_hip >= {since[0]}.{since[1]}" if by_version else f"came with library {since[0]}.{since[1]}"
+            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no {what}: {name} {how} (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        return fn
+
+    def _enqueue(self, name, stream, *args):
+        """a device-resident call: name(ctx, *args, stream handle) on `stream` (torch.cuda.Stream, or None = the current stream of this device); does not synchronise"""
+        import torch
+        fn = self._fn(name)
+        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
+        self._chk(fn(self._ctx, *args, C.c_void_p(st)), name)
+
     def version(self):
         return self._lib.plume_version().decode()
 
@@ -407,20 +405,14 @@ class Engine:
             self._chk(rc, "plume_get_sign_uniform")
         return rc
 
-    def _selfcheck_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None or _version(self._lib) < (0, 9):
-            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no signer self-check: {name} needs plume_hip >= 0.9 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
-        return fn
-
     def set_sign_selfcheck(self, mode):
         """the signer's self-check (plume_set_sign_selfcheck): 1 (or True) = every sign call verifies its own records on the GPU (verify_non_zk) before anything reaches
         the caller's arrays; an item that does not verify comes out all zero with status STATUS_SELFCHECK_FAILED (8).  0 (the default) = off"""
-        self._chk(self._selfcheck_fn("plume_set_sign_selfcheck")(self._ctx, int(mode)), "plume_set_sign_selfcheck")
+        self._chk(self._fn("plume_set_sign_selfcheck")(self._ctx, int(mode)), "plume_set_sign_selfcheck")
 
     def sign_selfcheck(self):
         """the mode this context signs with (plume_get_sign_selfcheck): 0 by default"""
-        rc = self._selfcheck_fn("plume_get_sign_selfcheck")(self._ctx)
+        rc = self._fn("plume_get_sign_selfcheck")(self._ctx)
         if rc < 0:
             self._chk(rc, "plume_get_sign_selfcheck")
         return rc
@@ -470,9 +462,7 @@ class Engine:
     # ------------------------------------------------------------------ host-pointer API (numpy in, numpy out)
     def verify_non_zk_batch(self, version, msgs, msg_off, pk, nullifier, s, r_point, hashed_to_curve_r, digest_private, out=None):
         """plume_arkworks' verify_non_zk (rust-arkworks/src/tests.rs:28-78), batched: 1 Ok(true), 0 Ok(false), 2 Err(HashToCurveError)"""
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         pk, nullifier, s = _np(pk, 64, n, "pk"), _np(nullifier, 64, n, "nullifier"), _np(s, 32, n, "s")
         r_point, hashed_to_curve_r = _np(r_point, 64, n, "r_point"), _np(hashed_to_curve_r, 64, n, "hashed_to_curve_r")
         digest_private = _np(digest_private, 32, n, "digest_private")
@@ -486,9 +476,7 @@ class Engine:
         probabilistic, never a replacement for verify_batch.  mode 0: PlumeSignature::verify of V1 signatures; mode 1: verify_non_zk (c = digest_private).
         seed: 32 bytes the producer of the batch cannot predict (default: os.urandom).  Returns dict(all_ok, identity, n_bad, point, hash_ok, seed)."""
         import os
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         pk, nullifier, c, s = _np(pk, 64, n, "pk"), _np(nullifier, 64, n, "nullifier"), _np(c, 32, n, "c"), _np(s, 32, n, "s")
         r_point, hashed_to_curve_r = _np(r_point, 64, n, "r_point"), _np(hashed_to_curve_r, 64, n, "hashed_to_curve_r")
         seed = os.urandom(32) if seed is None else bytes(seed)
@@ -505,9 +493,7 @@ class Engine:
         return out
 
     def verify_batch(self, version, msgs, msg_off, pk, nullifier, c, s, r_point=None, hashed_to_curve_r=None, out=None):
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         pk, nullifier, c, s = _np(pk, 64, n, "pk"), _np(nullifier, 64, n, "nullifier"), _np(c, 32, n, "c"), _np(s, 32, n, "s")
         if version == 1:
             if r_point is None or hashed_to_curve_r is None:
@@ -520,24 +506,16 @@ class Engine:
                                                _ptr(r_point), _ptr(hashed_to_curve_r), _ptr(ok)), "plume_verify_batch")
         return ok
 
-    def _recover_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None or _version(self._lib) < (0, 10):
-            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no point recovery: {name} needs plume_hip >= 0.10 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
-        return fn
-
     def recover_batch(self, version, msgs, msg_off, pk, nullifier, c, s, fmt=RECOVER_FMT_AFFINE64, want=RECOVER_OUTPUTS + ("status",)):
         """r_point = s G - c pk, hashed_to_curve_r = s H - c nullifier and H = hash_to_curve(msg, pk) of every item (plume_recover_batch): what a V2 signature leaves out.
         fmt: RECOVER_FMT_AFFINE64 (n x 64 bytes), RECOVER_FMT_SEC1 (n x 33) or RECOVER_FMT_REGISTERS (n x 2 x 4 uint64, the circuit's registers).  want: which of
         r_point, hashed_to_curve_r, hashed_to_curve, status to compute.  Returns a dict of those; status[i] is RECOVER_MATCH (c is version's hash of the points),
         RECOVER_MISMATCH (points written all the same) or RECOVER_INVALID (an input is no value of the reference's types: zero records)."""
-        fn = self._recover_fn("plume_recover_batch")
+        fn = self._fn("plume_recover_batch")
         want = tuple(want)
         if not want or any(k not in RECOVER_OUTPUTS + ("status",) for k in want):
             raise ValueError("want: a non-empty subset of r_point, hashed_to_curve_r, hashed_to_curve, status")
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         pk, nullifier, c, s = _np(pk, 64, n, "pk"), _np(nullifier, 64, n, "nullifier"), _np(c, 32, n, "c"), _np(s, 32, n, "s")
         shape, dt = {RECOVER_FMT_AFFINE64: ((n, 64), np.uint8), RECOVER_FMT_SEC1: ((n, 33), np.uint8), RECOVER_FMT_REGISTERS: ((n, 2, 4), np.uint64)}[int(fmt)]
         o = {k: np.zeros(shape, dtype=dt) for k in RECOVER_OUTPUTS if k in want}
@@ -547,18 +525,12 @@ class Engine:
                      _ptr(o.get("hashed_to_curve_r")), _ptr(o.get("hashed_to_curve")), _ptr(o.get("status"))), "plume_recover_batch")
         return o
 
-    def _eth_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None or _version(self._lib) < (0, 11):
-            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no Ethereum addresses: {name} needs plume_hip >= 0.11 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
-        return fn
-
     def eth_address_batch(self, pk, expect=None, pk_format="affine64", addr_format="raw20"):
         """The Ethereum address of every public key, Keccak-256(x || y)[12:] (plume_eth_address_batch).  pk: n x 64 bytes ("affine64") or n x 33 ("sec1"); expect:
         None or n x 20 raw bytes, the address each key is claimed to have.  Returns (address, status): address is n x 20 ("raw20"), n x 64 ("record64": 44 zero bytes
         then the address, a record Engine.nullifier_set() takes as is) or n x 42 ASCII ("eip55": "0x" + checksummed hex); status[i] is ETH_MATCH (expect is None or
         equals the address), ETH_MISMATCH, or ETH_INVALID (no non-identity curve point: a zero record)."""
-        fn = self._eth_fn("plume_eth_address_batch")
+        fn = self._fn("plume_eth_address_batch")
         pf, P = ETH_PK_FORMATS[pk_format]
         af, W = ETH_ADDR_FORMATS[addr_format]
         pk = np.ascontiguousarray(pk, dtype=np.uint8)
@@ -570,19 +542,13 @@ class Engine:
         self._chk(fn(self._ctx, pf, af, n, _ptr(pk), _ptr(expect), _ptr(address), _ptr(status)), "plume_eth_address_batch")
         return address, status
 
-    def _ecdsa_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None or _version(self._lib) < (0, 12):
-            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no ECDSA recovery: {name} needs plume_hip >= 0.12 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
-        return fn
-
     def ecdsa_recover_batch(self, hash, r, s, v, expect=None, pk_format="affine64", addr_format="raw20", low_s=False, want=("pk", "address", "status")):
         """The public key and the Ethereum address behind every ECDSA signature (plume_ecdsa_recover_batch): Ethereum's ecrecover with a one-byte v in {0, 1, 27, 28}.
         hash, r, s: n x 32 big-endian bytes; v: n bytes; expect: None or n x 20 raw bytes, the address each signer is claimed to have; low_s: s > (n - 1) / 2 is invalid
         (EIP-2).  Returns (pk, address, status) -- None for an output not named in `want`: pk is n x 64 ("affine64") or n x 33 ("sec1"), address as
         eth_address_batch writes it for addr_format, status[i] is ECDSA_MATCH (expect is None or equals the address), ECDSA_MISMATCH (pk and address are written all the
         same), or ECDSA_INVALID (v, r or s out of range, no point with x = r, or the key comes out as the identity: zero records)."""
-        fn = self._ecdsa_fn("plume_ecdsa_recover_batch")
+        fn = self._fn("plume_ecdsa_recover_batch")
         pf, P = ETH_PK_FORMATS[pk_format]
         af, W = ETH_ADDR_FORMATS[addr_format]
         v = np.ascontiguousarray(v, dtype=np.uint8).reshape(-1)
@@ -596,20 +562,12 @@ class Engine:
                   "plume_ecdsa_recover_batch")
         return pk, address, status
 
-    def _ecdsa_sign_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no ECDSA signing: {name} came with library 0.13 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
-        return fn
-
     def eth_message_hash_batch(self, msgs, msg_off, mode="eip191"):
         """The digest a wallet signs for every ragged message (plume_eth_message_hash_batch): Keccak-256(msg) for mode "keccak256", Keccak-256("\\x19Ethereum Signed
         Message:\\n" || decimal(len) || msg) for "eip191" (personal_sign).  msgs, msg_off as pack_messages returns them; a mode may also be given as its integer.
         Returns n x 32 bytes."""
-        fn = self._ecdsa_sign_fn("plume_eth_message_hash_batch")
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
+        fn = self._fn("plume_eth_message_hash_batch")
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         out = np.zeros((n, 32), dtype=np.uint8)
         self._chk(fn(self._ctx, int(ETH_HASH_MODES.get(mode, mode)), n, _ptr(msgs), _ptr(msg_off), _ptr(out)), "plume_eth_message_hash_batch")
         return out
@@ -619,7 +577,7 @@ class Engine:
         extra input), always low s.  hash, sk: n x 32 big-endian bytes.  Returns (r, s, v, status): r, s n x 32 bytes, v the parity of R's y behind the low-s flip (0 / 1,
         or 27 / 28 with v27), status[i] 0 (signed), 2 (sk outside [1, n - 1]), 4 (a degenerate outcome) or 8 (withheld by the self-check); r, s, v are zero unless
         status is 0.  flags: the raw flag word instead of v27."""
-        fn = self._ecdsa_sign_fn("plume_ecdsa_sign_batch")
+        fn = self._fn("plume_ecdsa_sign_batch")
         sk = np.ascontiguousarray(sk, dtype=np.uint8)
         if sk.size % 32:
             raise ValueError(f"sk: expected records of 32 bytes, got {sk.size} bytes")
@@ -632,22 +590,14 @@ class Engine:
         self._chk(fn(self._ctx, fl, n, _ptr(hash), _ptr(sk), _ptr(aux), _ptr(r), _ptr(s), _ptr(v), _ptr(status)), "plume_ecdsa_sign_batch")
         return r, s, v, status
 
-    def _eth_tx_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no transaction parsing: {name} came with library 0.14 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
-        return fn
-
     def eth_tx_parse_batch(self, txs, tx_off):
         """What plume_ecdsa_recover_batch takes, from raw signed transactions (plume_eth_tx_parse_batch): legacy (unprotected or EIP-155) and the typed envelopes 01 - 04.
         txs, tx_off as pack_messages returns them.  Returns a dict: hash (n x 32: what the sender signed), r, s (n x 32 big-endian), v (n: the parity, 0 or 1), chain_id
         (n uint64; 0 for an unprotected legacy item), tx_type (n) and status (n: ETH_TX_OK or ETH_TX_INVALID, every record of an invalid item being zero).  A sender
         recovery, not a consensus decoder: fields other than the envelope and the signature are not inspected.  The transaction id is
         eth_message_hash_batch(txs, tx_off, "keccak256")."""
-        fn = self._eth_tx_fn("plume_eth_tx_parse_batch")
-        tx_off = np.ascontiguousarray(tx_off, dtype=np.uint64)
-        n = len(tx_off) - 1
-        txs = np.ascontiguousarray(txs, dtype=np.uint8)
+        fn = self._fn("plume_eth_tx_parse_batch")
+        n, txs, tx_off = _ragged(txs, tx_off)
         out = {"hash": np.zeros((n, 32), np.uint8), "r": np.zeros((n, 32), np.uint8), "s": np.zeros((n, 32), np.uint8), "v": np.zeros(n, np.uint8),
                "chain_id": np.zeros(n, np.uint64), "tx_type": np.zeros(n, np.uint8), "status": np.zeros(n, np.uint8)}
         self._chk(fn(self._ctx, n, _ptr(txs), _ptr(tx_off), *(_ptr(out[k]) for k in ("hash", "r", "s", "v", "chain_id", "tx_type", "status"))), "plume_eth_tx_parse_batch")
@@ -658,12 +608,10 @@ class Engine:
         ecdsa_recover_batch.  expect, the formats, low_s (on by default: the rule for everything after Homestead) and `want` are that call's.  Returns (pk, address,
         status, chain_id, tx_type): status[i] is ECDSA_MATCH, ECDSA_MISMATCH or ECDSA_INVALID (the framing or the signature: zero records); chain_id and tx_type report
         the framing and are zero only for an item invalid there."""
-        fn = self._eth_tx_fn("plume_eth_tx_sender_batch")
+        fn = self._fn("plume_eth_tx_sender_batch")
         pf, P = ETH_PK_FORMATS[pk_format]
         af, W = ETH_ADDR_FORMATS[addr_format]
-        tx_off = np.ascontiguousarray(tx_off, dtype=np.uint64)
-        n = len(tx_off) - 1
-        txs = np.ascontiguousarray(txs, dtype=np.uint8)
+        n, txs, tx_off = _ragged(txs, tx_off)
         expect = None if expect is None else _np(expect, 20, n, "expect")
         pk = np.zeros((n, P), dtype=np.uint8) if "pk" in want else None
         address = np.zeros((n, W), dtype=np.uint8) if "address" in want else None
@@ -673,19 +621,11 @@ class Engine:
                      _ptr(status)), "plume_eth_tx_sender_batch")
         return pk, address, status, chain_id, tx_type
 
-    def _eth_tx_sign_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no transaction signing: {name} came with library 0.16 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
-        return fn
-
     def eth_tx_sign_slots(self, txs, tx_off, sk, aux=None, want=("hash", "r", "s", "v", "chain_id", "tx_type")):
         """plume_eth_tx_sign_batch as the library writes it: a dict with out (the slots: item i's at (tx_off[i] - tx_off[0]) + 68 i, len_i + 68 bytes, zero beyond
         out_len[i]), out_len (n uint32), status (n) and the records named in `want`.  txs, tx_off as pack_messages returns them: UNSIGNED transactions."""
-        fn = self._eth_tx_sign_fn("plume_eth_tx_sign_batch")
-        tx_off = np.ascontiguousarray(tx_off, dtype=np.uint64)
-        n = len(tx_off) - 1
-        txs = np.ascontiguousarray(txs, dtype=np.uint8)
+        fn = self._fn("plume_eth_tx_sign_batch")
+        n, txs, tx_off = _ragged(txs, tx_off)
         sk = _np(sk, 32, n, "sk")
         aux = None if aux is None else _np(aux, 32, n, "aux")
         nbytes = int(tx_off[n]) - int(tx_off[0]) if n else 0
@@ -712,16 +652,10 @@ class Engine:
             return raw, res["status"], {k: res[k] for k in ("hash", "r", "s", "v", "chain_id", "tx_type")}
         return raw, res["status"]
 
-    def _hd_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no key derivation: {name} came with library 0.17 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
-        return fn
-
     def hd_master_batch(self, seed, seed_len=None):
         """BIP-32 master nodes (plume_hd_master_batch).  seed: n x seed_len bytes (a 2-D array, or flat with seed_len given), 16 <= seed_len <= 64.  Returns
         (sk, chain, status): n x 32 bytes each and n status bytes -- 0, or STATUS_HD_NO_KEY (32) with both records all zero."""
-        fn = self._hd_fn("plume_hd_master_batch")
+        fn = self._fn("plume_hd_master_batch")
         seed = np.ascontiguousarray(seed, dtype=np.uint8)
         if seed_len is None:
             if seed.ndim != 2:
@@ -757,7 +691,7 @@ class Engine:
         only as torch does)."""
         if device:
             return self._hd_derive_torch(False, parent_sk, parent_chain, path, pk_format, addr_format, want)
-        fn = self._hd_fn("plume_hd_derive_priv_batch")
+        fn = self._fn("plume_hd_derive_priv_batch")
         flags, n, depth, parent_sk, parent_chain, path = self._hd_shape(parent_sk, 32, parent_chain, path, "hd_derive_priv_batch")
         res = {"sk": np.zeros((n, 32), np.uint8), "status": np.zeros(n, np.uint8)}
         shape = {"chain": 32, "pk": ETH_PK_FORMATS[pk_format][1], "address": ETH_ADDR_FORMATS[addr_format][1]}
@@ -772,7 +706,7 @@ class Engine:
         (pk_format), status (n: 0, 2, 32, 64) and the records named in `want` -- chain, address."""
         if device:
             return self._hd_derive_torch(True, parent_pk, parent_chain, path, pk_format, addr_format, want)
-        fn = self._hd_fn("plume_hd_derive_pub_batch")
+        fn = self._fn("plume_hd_derive_pub_batch")
         flags, n, depth, parent_pk, parent_chain, path = self._hd_shape(parent_pk, ETH_PK_FORMATS[pk_format][1], parent_chain, path, "hd_derive_pub_batch")
         res = {"pk": np.zeros((n, ETH_PK_FORMATS[pk_format][1]), np.uint8), "status": np.zeros(n, np.uint8)}
         shape = {"chain": 32, "address": ETH_ADDR_FORMATS[addr_format][1]}
@@ -819,12 +753,6 @@ class Engine:
             t.record_stream(st)
         return res
 
-    def _merkle_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no Merkle trees: {name} came with library 0.15 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
-        return fn
-
     @staticmethod
     def _merkle_items(leaf_format, addr_format, items, amounts):
         lf = MERKLE_LEAF_FORMATS[leaf_format]
@@ -849,14 +777,14 @@ class Engine:
 
     def merkle_max_proof_len(self, n):
         """floor(log2(2n - 1)): the longest proof of a tree of n leaves (plume_merkle_max_proof_len)"""
-        return int(self._merkle_fn("plume_merkle_max_proof_len")(int(n)) or 0)
+        return int(self._fn("plume_merkle_max_proof_len")(int(n)) or 0)
 
     def merkle_leaf_batch(self, items, amounts=None, leaf_format="address", addr_format="raw20"):
         """The leaves of an OpenZeppelin StandardMerkleTree (plume_merkle_leaf_batch).  leaf_format "address": Keccak(Keccak(abi.encode(address))), the tree of
         ["address"]; "address_uint256": with amounts (integers, or n x 32 big-endian bytes), the tree of ["address", "uint256"]; "hash32": the items are the leaves.
         items: n x 20 ("raw20") or n x 64 ("record64": what eth_address_batch, ecdsa_recover_batch and eth_tx_sender_batch write).  Returns (leaf n x 32, status):
         MERKLE_MATCH, or MERKLE_INVALID and a zero leaf for a record64 whose first 44 bytes are not zero."""
-        fn = self._merkle_fn("plume_merkle_leaf_batch")
+        fn = self._fn("plume_merkle_leaf_batch")
         lf, af, n, items, amounts = self._merkle_items(leaf_format, addr_format, items, amounts)
         leaf, status = np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
         self._chk(fn(self._ctx, lf, af, n, _ptr(items), _ptr(amounts), _ptr(leaf), _ptr(status)), "plume_merkle_leaf_batch")
@@ -865,7 +793,7 @@ class Engine:
     def merkle_tree_build(self, leaves, sort=True):
         """(tree (2n - 1) x 32, leaf_pos n uint32) of n >= 1 leaves of 32 bytes (plume_merkle_tree_build): tree[0] is the root, the leaves sit at the end in reverse,
         sorted by (bytes, input index) when sort is set; leaf_pos[j] is the tree index of input leaf j."""
-        fn = self._merkle_fn("plume_merkle_tree_build")
+        fn = self._fn("plume_merkle_tree_build")
         leaves = np.ascontiguousarray(leaves, dtype=np.uint8)
         if leaves.size % 32:
             raise ValueError(f"leaves: expected records of 32 bytes, got {leaves.size} bytes")
@@ -877,7 +805,7 @@ class Engine:
     def merkle_proof_batch(self, tree, pos, depth=None):
         """The proofs of the tree indices pos (plume_merkle_proof_batch): (proof m x depth x 32, proof_len m).  depth defaults to the longest proof of the tree; unused
         slots are zero; an index outside the tree, or a proof longer than depth, gives MERKLE_BAD_PROOF and zero slots."""
-        fn = self._merkle_fn("plume_merkle_proof_batch")
+        fn = self._fn("plume_merkle_proof_batch")
         tree = np.ascontiguousarray(tree, dtype=np.uint8)
         n = (tree.size // 32 + 1) // 2
         if tree.size % 32 or tree.size // 32 != 2 * n - 1:
@@ -891,7 +819,7 @@ class Engine:
     def merkle_verify_batch(self, items, proof, proof_len, root, amounts=None, leaf_format="address", addr_format="raw20"):
         """MerkleProof.verify for every item against one root (plume_merkle_verify_batch).  items and amounts as merkle_leaf_batch takes them (the leaf is computed on the
         GPU); proof: m x depth x 32, proof_len: m bytes.  Returns status: MERKLE_MATCH, MERKLE_MISMATCH, or MERKLE_INVALID (an invalid item, or proof_len above depth)."""
-        fn = self._merkle_fn("plume_merkle_verify_batch")
+        fn = self._fn("plume_merkle_verify_batch")
         lf, af, m, items, amounts = self._merkle_items(leaf_format, addr_format, items, amounts)
         proof = np.ascontiguousarray(proof, dtype=np.uint8)
         if m == 0 or proof.size % (32 * m):
@@ -923,9 +851,7 @@ class Engine:
 
     def verify_batch_sec1(self, version, msgs, msg_off, pk33, nullifier33, c, s, r_point33=None, hashed_to_curve_r33=None):
         """verify with 33-byte SEC1-compressed points (decompressed and validated on the GPU)"""
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         pk33, nullifier33, c, s = _np(pk33, 33, n, "pk33"), _np(nullifier33, 33, n, "nullifier33"), _np(c, 32, n, "c"), _np(s, 32, n, "s")
         if version == 1:
             if r_point33 is None or hashed_to_curve_r33 is None:
@@ -940,64 +866,38 @@ class Engine:
 
     def sign_batch(self, version, msgs, msg_off, sk, r, pk_in=None, out=None):
         """out: optional dict of preallocated arrays (pk, nullifier, c, s, r_point, hashed_to_curve_r, status), e.g. page-locked ones"""
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         sk, r = _np(sk, 32, n, "sk"), _np(r, 32, n, "r")
         pk_in = None if pk_in is None else _np(pk_in, 64, n, "pk_in")
-        o = out if out is not None else {k: np.zeros((n, w), dtype=np.uint8) for k, w in
-                                         [("pk", 64), ("nullifier", 64), ("c", 32), ("s", 32), ("r_point", 64), ("hashed_to_curve_r", 64)]}
-        status = o["status"] if out is not None else np.zeros(n, dtype=np.uint8)
-        self._chk(self._lib.plume_sign_batch(self._ctx, int(version), n, _ptr(msgs), _ptr(msg_off), _ptr(sk), _ptr(r), _ptr(pk_in), _ptr(o["pk"]),
-                                             _ptr(o["nullifier"]), _ptr(o["c"]), _ptr(o["s"]), _ptr(o["r_point"]), _ptr(o["hashed_to_curve_r"]),
-                                             _ptr(status)), "plume_sign_batch")
-        o["status"] = status
+        o = _sign_outputs(n, 64, out)
+        self._chk(self._lib.plume_sign_batch(self._ctx, int(version), n, _ptr(msgs), _ptr(msg_off), _ptr(sk), _ptr(r), _ptr(pk_in), *(_ptr(o[k]) for k in _SIGN_OUTPUTS)),
+                  "plume_sign_batch")
         return o
-
-    def _derived(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None or _version(self._lib) < (0, 8):
-            raise PlumeHipError(f"{self._lib.plume_version().decode()} has no derived-nonce signer: {name} needs plume_hip >= 0.8 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
-        return fn
 
     def sign_batch_rfc6979(self, version, msgs, msg_off, sk, aux=None, pk_in=None, out=None):
         """sign_batch with each nonce derived on the GPU by RFC 6979 (include/plume_hip.h, plume_sign_batch_rfc6979): h1 = SHA-256("PLUME-RFC6979" || version || mode ||
         pk_in || msg), x = sk; aux (n x 32 bytes, optional) is the hedging input of RFC 6979 section 3.6.  The nonces never reach host memory.  Same outputs as sign_batch."""
-        fn = self._derived("plume_sign_batch_rfc6979")
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        fn = self._fn("plume_sign_batch_rfc6979")
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         sk = _np(sk, 32, n, "sk")
         aux = None if aux is None else _np(aux, 32, n, "aux")
         pk_in = None if pk_in is None else _np(pk_in, 64, n, "pk_in")
-        o = out if out is not None else {k: np.zeros((n, w), dtype=np.uint8) for k, w in
-                                         [("pk", 64), ("nullifier", 64), ("c", 32), ("s", 32), ("r_point", 64), ("hashed_to_curve_r", 64)]}
-        status = o["status"] if out is not None else np.zeros(n, dtype=np.uint8)
-        self._chk(fn(self._ctx, int(version), n, _ptr(msgs), _ptr(msg_off), _ptr(sk), _ptr(aux), _ptr(pk_in), _ptr(o["pk"]), _ptr(o["nullifier"]), _ptr(o["c"]), _ptr(o["s"]),
-                     _ptr(o["r_point"]), _ptr(o["hashed_to_curve_r"]), _ptr(status)), "plume_sign_batch_rfc6979")
-        o["status"] = status
+        o = _sign_outputs(n, 64, out)
+        self._chk(fn(self._ctx, int(version), n, _ptr(msgs), _ptr(msg_off), _ptr(sk), _ptr(aux), _ptr(pk_in), *(_ptr(o[k]) for k in _SIGN_OUTPUTS)), "plume_sign_batch_rfc6979")
         return o
 
     def sign_batch_sec1(self, version, msgs, msg_off, sk, r, pk_in=None):
         """sign_batch with pk, nullifier, r_point, hashed_to_curve_r as 33-byte SEC1-compressed records"""
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         sk, r = _np(sk, 32, n, "sk"), _np(r, 32, n, "r")
         pk_in = None if pk_in is None else _np(pk_in, 64, n, "pk_in")
-        o = {k: np.zeros((n, w), dtype=np.uint8) for k, w in
-             [("pk", 33), ("nullifier", 33), ("c", 32), ("s", 32), ("r_point", 33), ("hashed_to_curve_r", 33)]}
-        status = np.zeros(n, dtype=np.uint8)
-        self._chk(self._lib.plume_sign_batch_sec1(self._ctx, int(version), n, _ptr(msgs), _ptr(msg_off), _ptr(sk), _ptr(r), _ptr(pk_in), _ptr(o["pk"]),
-                                                  _ptr(o["nullifier"]), _ptr(o["c"]), _ptr(o["s"]), _ptr(o["r_point"]), _ptr(o["hashed_to_curve_r"]),
-                                                  _ptr(status)), "plume_sign_batch_sec1")
-        o["status"] = status
+        o = _sign_outputs(n, 33)
+        self._chk(self._lib.plume_sign_batch_sec1(self._ctx, int(version), n, _ptr(msgs), _ptr(msg_off), _ptr(sk), _ptr(r), _ptr(pk_in), *(_ptr(o[k]) for k in _SIGN_OUTPUTS)),
+                  "plume_sign_batch_sec1")
         return o
 
     def hash_to_curve_batch(self, msgs, msg_off, pk=None):
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         pk = None if pk is None else _np(pk, 64, n, "pk")
         h = np.zeros((n, 64), dtype=np.uint8)
         self._chk(self._lib.plume_hash_to_curve_batch(self._ctx, n, _ptr(msgs), _ptr(msg_off), _ptr(pk), _ptr(h)), "plume_hash_to_curve_batch")
@@ -1006,9 +906,7 @@ class Engine:
     def h2c_intermediates_batch(self, msgs, msg_off, pk=None, registers=False):
         """circuit witness hints from the GPU hash_to_curve: dict u (n,2,·), mapped (n,4,·), q (n,4,·), h (n,2,·); values are 32
         big-endian bytes (uint8, last axis 32) or, with registers=True, 4 little-endian 64-bit registers (uint64, last axis 4)"""
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         pk = None if pk is None else _np(pk, 64, n, "pk")
         o = {k: np.zeros((n, w, 32), dtype=np.uint8) for k, w in [("u", 2), ("mapped", 4), ("q", 4), ("h", 2)]}
         self._chk(self._lib.plume_h2c_intermediates_batch(self._ctx, n, _ptr(msgs), _ptr(msg_off), _ptr(pk), 1 if registers else 0, _ptr(o["u"]), _ptr(o["mapped"]),
@@ -1019,9 +917,7 @@ class Engine:
 
     def h2c_hints_batch(self, msgs, msg_off, pk=None, registers=False):
         """the circuit's square-root hints (UNPINNED definitions, include/plume_hip.h): dict q0_gx1_sqrt, q0_gx2_sqrt, q0_y_pos, q1_... -> (n, 32) bytes or (n, 4) uint64 registers"""
-        msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
-        n = len(msg_off) - 1
-        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
+        n, msgs, msg_off = _ragged(msgs, msg_off)
         pk = None if pk is None else _np(pk, 64, n, "pk")
         out = np.zeros((n, 6, 32), dtype=np.uint8)
         self._chk(self._lib.plume_h2c_hints_batch(self._ctx, n, _ptr(msgs), _ptr(msg_off), _ptr(pk), 1 if registers else 0, _ptr(out)), "plume_h2c_hints_batch")
@@ -1064,200 +960,138 @@ class Engine:
 
     def verify_batch_device(self, version, n, msgs, msg_off, msgs_bytes, pk, nullifier, c, s, r_point, hashed_to_curve_r, ok, stream=None):
         """all tensors on cuda:<device_id>; enqueues on `stream` (torch.cuda.Stream or None = current stream); does not synchronise"""
-        import torch
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(self._lib.plume_verify_batch_device(self._ctx, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(c), d(s),
-                                                      d(r_point), d(hashed_to_curve_r), d(ok), C.c_void_p(st)), "plume_verify_batch_device")
+        self._enqueue("plume_verify_batch_device", stream, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(c), d(s),
+                      d(r_point), d(hashed_to_curve_r), d(ok))
 
     def recover_batch_device(self, version, n, msgs, msg_off, msgs_bytes, pk, nullifier, c, s, r_point, hashed_to_curve_r, hashed_to_curve, status,
                              fmt=RECOVER_FMT_AFFINE64, stream=None):
         """the device form of recover_batch on torch tensors; each of the four outputs may be None (at least one is not); enqueues on `stream` (None = current
         stream); does not synchronise"""
-        import torch
-        fn = self._recover_fn("plume_recover_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, int(version), int(fmt), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(c), d(s), d(r_point), d(hashed_to_curve_r),
-                     d(hashed_to_curve), d(status), C.c_void_p(st)), "plume_recover_batch_device")
+        self._enqueue("plume_recover_batch_device", stream, int(version), int(fmt), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(c), d(s),
+                      d(r_point), d(hashed_to_curve_r), d(hashed_to_curve), d(status))
 
     def eth_address_batch_device(self, n, pk, expect, address, status, pk_format="affine64", addr_format="raw20", stream=None):
         """the device form of eth_address_batch on torch tensors; expect may be None, and one of address and status; enqueues on `stream` (None = current stream); does
         not synchronise"""
-        import torch
-        fn = self._eth_fn("plume_eth_address_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(pk), d(expect), d(address), d(status), C.c_void_p(st)),
-                  "plume_eth_address_batch_device")
+        self._enqueue("plume_eth_address_batch_device", stream, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(pk), d(expect), d(address), d(status))
 
     def ecdsa_recover_batch_device(self, n, hash, r, s, v, expect, pk, address, status, pk_format="affine64", addr_format="raw20", low_s=False, stream=None):
         """the device form of ecdsa_recover_batch on torch tensors; expect may be None, and any two of pk, address and status; enqueues on `stream` (None = current
         stream); does not synchronise"""
-        import torch
-        fn = self._ecdsa_fn("plume_ecdsa_recover_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, ECDSA_LOW_S if low_s else 0, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(hash), d(r), d(s), d(v), d(expect),
-                     d(pk), d(address), d(status), C.c_void_p(st)), "plume_ecdsa_recover_batch_device")
+        self._enqueue("plume_ecdsa_recover_batch_device", stream, ECDSA_LOW_S if low_s else 0, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n),
+                      d(hash), d(r), d(s), d(v), d(expect), d(pk), d(address), d(status))
 
     def eth_message_hash_batch_device(self, n, msgs, msg_off, msgs_bytes, hash32, mode="eip191", stream=None):
         """the device form of eth_message_hash_batch on torch tensors (msg_off: n + 1 uint64 offsets; msgs and hash32 at any byte offset); one kernel on `stream`
         (None = current stream); does not synchronise"""
-        import torch
-        fn = self._ecdsa_sign_fn("plume_eth_message_hash_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, int(ETH_HASH_MODES.get(mode, mode)), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(hash32), C.c_void_p(st)),
-                  "plume_eth_message_hash_batch_device")
+        self._enqueue("plume_eth_message_hash_batch_device", stream, int(ETH_HASH_MODES.get(mode, mode)), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(hash32))
 
     def eth_tx_parse_batch_device(self, n, txs, tx_off, txs_bytes, hash32, r, s, v, chain_id=None, tx_type=None, status=None, stream=None):
         """the device form of eth_tx_parse_batch on torch tensors (tx_off: n + 1 uint64 offsets; chain_id: n 8-byte words; the byte arrays at any byte offset; chain_id,
         tx_type and status may be None); one kernel on `stream` (None = current stream); does not synchronise"""
-        import torch
-        fn = self._eth_tx_fn("plume_eth_tx_parse_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, int(n), d(txs), d(tx_off), int(txs_bytes), d(hash32), d(r), d(s), d(v), d(chain_id), d(tx_type), d(status), C.c_void_p(st)),
-                  "plume_eth_tx_parse_batch_device")
+        self._enqueue("plume_eth_tx_parse_batch_device", stream, int(n), d(txs), d(tx_off), int(txs_bytes), d(hash32), d(r), d(s), d(v), d(chain_id), d(tx_type), d(status))
 
     def eth_tx_sender_batch_device(self, n, txs, tx_off, txs_bytes, expect, pk, address, chain_id, tx_type, status, pk_format="affine64", addr_format="raw20", low_s=True,
                                    stream=None):
         """the device form of eth_tx_sender_batch on torch tensors; expect, chain_id and tx_type may be None, and any two of pk, address and status; enqueues on `stream`
         (None = current stream); does not synchronise"""
-        import torch
-        fn = self._eth_tx_fn("plume_eth_tx_sender_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, ECDSA_LOW_S if low_s else 0, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(txs), d(tx_off), int(txs_bytes),
-                     d(expect), d(pk), d(address), d(chain_id), d(tx_type), d(status), C.c_void_p(st)), "plume_eth_tx_sender_batch_device")
+        self._enqueue("plume_eth_tx_sender_batch_device", stream, ECDSA_LOW_S if low_s else 0, ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n),
+                      d(txs), d(tx_off), int(txs_bytes), d(expect), d(pk), d(address), d(chain_id), d(tx_type), d(status))
 
     def eth_tx_sign_batch_device(self, n, txs, tx_off, txs_bytes, sk, aux, out, out_bytes, out_len, status, hash32=None, r=None, s=None, v=None, chain_id=None, tx_type=None,
                                  stream=None):
         """the device form of eth_tx_sign_batch on torch tensors (tx_off: n + 1 uint64 offsets; out: the slots, out_bytes of them; out_len: n 4-byte words; chain_id: n
         8-byte words; the byte arrays at any byte offset; aux and the records may be None); enqueues on `stream` (None = current stream); does not synchronise"""
-        import torch
-        fn = self._eth_tx_sign_fn("plume_eth_tx_sign_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, 0, int(n), d(txs), d(tx_off), int(txs_bytes), d(sk), d(aux), d(out), int(out_bytes), d(out_len), d(hash32), d(r), d(s), d(v), d(chain_id),
-                     d(tx_type), d(status), C.c_void_p(st)), "plume_eth_tx_sign_batch_device")
+        self._enqueue("plume_eth_tx_sign_batch_device", stream, 0, int(n), d(txs), d(tx_off), int(txs_bytes), d(sk), d(aux), d(out), int(out_bytes), d(out_len),
+                      d(hash32), d(r), d(s), d(v), d(chain_id), d(tx_type), d(status))
 
     def hd_master_batch_device(self, n, seed, seed_len, sk, chain, status, stream=None):
         """the device form of hd_master_batch on torch tensors; one kernel on `stream` (None = current stream); does not synchronise"""
-        import torch
-        fn = self._hd_fn("plume_hd_master_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, int(n), d(seed), int(seed_len), d(sk), d(chain), d(status), C.c_void_p(st)), "plume_hd_master_batch_device")
+        self._enqueue("plume_hd_master_batch_device", stream, int(n), d(seed), int(seed_len), d(sk), d(chain), d(status))
 
     def hd_derive_batch_device(self, pub, flags, n, parent, parent_chain, path, depth, child_sk, child_chain, child_pk, address, status, pk_format="affine64",
                                addr_format="raw20", stream=None):
         """the device forms of hd_derive_priv_batch (pub False: parent is sk, child_sk required) and hd_derive_pub_batch (pub True: parent is pk, child_sk ignored, child_pk
         required) on torch tensors; path: n x depth 4-byte indices (one row with HD_SHARED_PATH); the optional records may be None; enqueues on `stream` (None = current
         stream); does not synchronise.  child_sk is what ecdsa_sign_batch_device and eth_tx_sign_batch_device take as sk."""
-        import torch
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        head = (self._ctx, int(flags), ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(parent), d(parent_chain), d(path), int(depth))
+        head = (int(flags), ETH_PK_FORMATS[pk_format][0], ETH_ADDR_FORMATS[addr_format][0], int(n), d(parent), d(parent_chain), d(path), int(depth))
         if pub:
-            self._chk(self._hd_fn("plume_hd_derive_pub_batch_device")(*head, d(child_pk), d(child_chain), d(address), d(status), C.c_void_p(st)), "plume_hd_derive_pub_batch_device")
+            self._enqueue("plume_hd_derive_pub_batch_device", stream, *head, d(child_pk), d(child_chain), d(address), d(status))
         else:
-            self._chk(self._hd_fn("plume_hd_derive_priv_batch_device")(*head, d(child_sk), d(child_chain), d(child_pk), d(address), d(status), C.c_void_p(st)),
-                      "plume_hd_derive_priv_batch_device")
+            self._enqueue("plume_hd_derive_priv_batch_device", stream, *head, d(child_sk), d(child_chain), d(child_pk), d(address), d(status))
 
     def merkle_leaf_batch_device(self, n, items, amounts, leaf32, status, leaf_format="address", addr_format="raw20", stream=None):
         """the device form of merkle_leaf_batch on torch tensors; amounts (n x 32 big-endian bytes) and status may be None; one kernel on `stream` (None = current
         stream); does not synchronise"""
-        import torch
-        fn = self._merkle_fn("plume_merkle_leaf_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, MERKLE_LEAF_FORMATS[leaf_format], ETH_ADDR_FORMATS[addr_format][0], int(n), d(items), d(amounts), d(leaf32), d(status), C.c_void_p(st)),
-                  "plume_merkle_leaf_batch_device")
+        self._enqueue("plume_merkle_leaf_batch_device", stream, MERKLE_LEAF_FORMATS[leaf_format], ETH_ADDR_FORMATS[addr_format][0], int(n), d(items), d(amounts), d(leaf32),
+                      d(status))
 
     def merkle_tree_build_device(self, n, leaf32, tree, leaf_pos, sort=True, stream=None):
         """the device form of merkle_tree_build on torch tensors (tree: (2n - 1) x 32 bytes; leaf_pos: n 4-byte words, or None); enqueues on `stream` (None = current
         stream); does not synchronise"""
-        import torch
-        fn = self._merkle_fn("plume_merkle_tree_build_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, MERKLE_SORT_LEAVES if sort else 0, int(n), d(leaf32), d(tree), d(leaf_pos), C.c_void_p(st)), "plume_merkle_tree_build_device")
+        self._enqueue("plume_merkle_tree_build_device", stream, MERKLE_SORT_LEAVES if sort else 0, int(n), d(leaf32), d(tree), d(leaf_pos))
 
     def merkle_proof_batch_device(self, n, tree, m, pos, depth, proof, proof_len, stream=None):
         """the device form of merkle_proof_batch on torch tensors (pos: m 4-byte words; proof: m x depth x 32 bytes; proof_len: m bytes); one kernel on `stream` (None =
         current stream); does not synchronise"""
-        import torch
-        fn = self._merkle_fn("plume_merkle_proof_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, int(n), d(tree), int(m), d(pos), int(depth), d(proof), d(proof_len), C.c_void_p(st)), "plume_merkle_proof_batch_device")
+        self._enqueue("plume_merkle_proof_batch_device", stream, int(n), d(tree), int(m), d(pos), int(depth), d(proof), d(proof_len))
 
     def merkle_verify_batch_device(self, m, items, amounts, depth, proof, proof_len, root32, status, leaf_format="address", addr_format="raw20", stream=None):
         """the device form of merkle_verify_batch on torch tensors; amounts may be None; one kernel on `stream` (None = current stream); does not synchronise"""
-        import torch
-        fn = self._merkle_fn("plume_merkle_verify_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, MERKLE_LEAF_FORMATS[leaf_format], ETH_ADDR_FORMATS[addr_format][0], int(m), d(items), d(amounts), int(depth), d(proof), d(proof_len),
-                     d(root32), d(status), C.c_void_p(st)), "plume_merkle_verify_batch_device")
+        self._enqueue("plume_merkle_verify_batch_device", stream, MERKLE_LEAF_FORMATS[leaf_format], ETH_ADDR_FORMATS[addr_format][0], int(m), d(items), d(amounts), int(depth),
+                      d(proof), d(proof_len), d(root32), d(status))
 
     def ecdsa_sign_batch_device(self, n, hash, sk, aux, r, s, v, status, v27=False, stream=None):
         """the device form of ecdsa_sign_batch on torch tensors; aux may be None; enqueues on `stream` (None = current stream); does not synchronise"""
-        import torch
-        fn = self._ecdsa_sign_fn("plume_ecdsa_sign_batch_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, ECDSA_SIGN_V27 if v27 else 0, int(n), d(hash), d(sk), d(aux), d(r), d(s), d(v), d(status), C.c_void_p(st)), "plume_ecdsa_sign_batch_device")
+        self._enqueue("plume_ecdsa_sign_batch_device", stream, ECDSA_SIGN_V27 if v27 else 0, int(n), d(hash), d(sk), d(aux), d(r), d(s), d(v), d(status))
 
     def verify_non_zk_batch_device(self, version, n, msgs, msg_off, msgs_bytes, pk, nullifier, s, r_point, hashed_to_curve_r, digest_private, ok, stream=None):
-        import torch
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(self._lib.plume_verify_non_zk_batch_device(self._ctx, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(s), d(r_point),
-                                                             d(hashed_to_curve_r), d(digest_private), d(ok), C.c_void_p(st)), "plume_verify_non_zk_batch_device")
+        self._enqueue("plume_verify_non_zk_batch_device", stream, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(s), d(r_point),
+                      d(hashed_to_curve_r), d(digest_private), d(ok))
 
     def aggregate_check_device(self, version, mode, n, msgs, msg_off, msgs_bytes, pk, nullifier, c, s, r_point, hashed_to_curve_r, seed, index_base, hash_ok, result, stream=None):
         """device tensors; seed: 32 host bytes; hash_ok: uint8[n] or None; result: uint8[72] (parse_aggregate_record after synchronising)"""
-        import torch
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
         sd = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
-        self._chk(self._lib.plume_aggregate_check_device(self._ctx, int(version), int(mode), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(c), d(s), d(r_point),
-                                                         d(hashed_to_curve_r), _ptr(sd), int(index_base), d(hash_ok), d(result), C.c_void_p(st)), "plume_aggregate_check_device")
+        self._enqueue("plume_aggregate_check_device", stream, int(version), int(mode), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk), d(nullifier), d(c), d(s), d(r_point),
+                      d(hashed_to_curve_r), _ptr(sd), int(index_base), d(hash_ok), d(result))
 
     def verify_batch_sec1_device(self, version, n, msgs, msg_off, msgs_bytes, pk33, nullifier33, c, s, r_point33, hashed_to_curve_r33, ok, stream=None):
-        import torch
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(self._lib.plume_verify_batch_sec1_device(self._ctx, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk33), d(nullifier33), d(c), d(s),
-                                                           d(r_point33), d(hashed_to_curve_r33), d(ok), C.c_void_p(st)), "plume_verify_batch_sec1_device")
+        self._enqueue("plume_verify_batch_sec1_device", stream, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(pk33), d(nullifier33), d(c), d(s),
+                      d(r_point33), d(hashed_to_curve_r33), d(ok))
 
     def sign_batch_device(self, version, n, msgs, msg_off, msgs_bytes, sk, r, pk_in, pk, nullifier, c, s, r_point, hashed_to_curve_r, status, stream=None):
-        import torch
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(self._lib.plume_sign_batch_device(self._ctx, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(sk), d(r), d(pk_in), d(pk),
-                                                    d(nullifier), d(c), d(s), d(r_point), d(hashed_to_curve_r), d(status), C.c_void_p(st)),
-                  "plume_sign_batch_device")
+        self._enqueue("plume_sign_batch_device", stream, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(sk), d(r), d(pk_in), d(pk),
+                      d(nullifier), d(c), d(s), d(r_point), d(hashed_to_curve_r), d(status))
 
     def sign_batch_rfc6979_device(self, version, n, msgs, msg_off, msgs_bytes, sk, aux, pk_in, pk, nullifier, c, s, r_point, hashed_to_curve_r, status, stream=None):
         """the device form of sign_batch_rfc6979 on torch tensors (aux, pk_in: None or tensors); enqueues on `stream` (None = current stream); does not synchronise"""
-        import torch
-        fn = self._derived("plume_sign_batch_rfc6979_device")
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(fn(self._ctx, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(sk), d(aux), d(pk_in), d(pk), d(nullifier), d(c), d(s), d(r_point),
-                     d(hashed_to_curve_r), d(status), C.c_void_p(st)), "plume_sign_batch_rfc6979_device")
+        self._enqueue("plume_sign_batch_rfc6979_device", stream, int(version), int(n), d(msgs), d(msg_off), int(msgs_bytes), d(sk), d(aux), d(pk_in), d(pk), d(nullifier),
+                      d(c), d(s), d(r_point), d(hashed_to_curve_r), d(status))
 
     def nullifier_first_occurrence_device(self, n, nullifier, live, ids, first, n_unique=None, stream=None):
         """tensors on cuda:<device_id> (nullifier n x 64 uint8, live / first uint8[n] or None, ids int64/uint64[n] or None, n_unique one 64-bit word or None)"""
-        import torch
-        st = (stream or torch.cuda.current_stream(self.device_id)).cuda_stream
         d = self._dp
-        self._chk(self._lib.plume_nullifier_first_occurrence_device(self._ctx, int(n), d(nullifier), d(live), d(ids), d(first), d(n_unique), C.c_void_p(st)),
-                  "plume_nullifier_first_occurrence_device")
+        self._enqueue("plume_nullifier_first_occurrence_device", stream, int(n), d(nullifier), d(live), d(ids), d(first), d(n_unique))
 
     # ------------------------------------------------------------------ persistent nullifier set
     def nullifier_set(self, reserve=0):
@@ -1335,8 +1169,9 @@ class NullifierSet:
 
     def __init__(self, engine, reserve=0):
         lib = engine._lib
-        if getattr(lib, "plume_nullset_create", None) is None or _version(lib) < (0, 7):
-            raise PlumeHipError(f"{lib.plume_version().decode()} has no persistent nullifier set: it needs plume_hip >= 0.7 (rebuild: make -C zk-nullifier-sig_amd/csrc)")
+        since, what = GROUPS["nullset"]
+        if getattr(lib, "plume_nullset_create", None) is None or _version(lib) < since:
+            raise PlumeHipError(f"{lib.plume_version().decode()} has no {what}: it needs plume_hip >= {since[0]}.{since[1]} (rebuild: make -C zk-nullifier-sig_amd/csrc)")
         self._lib = lib
         self.device_id = engine.device_id
         self._h = C.c_void_p()
