@@ -76,6 +76,11 @@ pub const PLUME_STATUS_BAD_TX: u8 = 16;
 pub const PLUME_STATUS_HD_NO_KEY: u8 = 32;
 pub const PLUME_STATUS_HD_HARDENED: u8 = 64;
 pub const PLUME_HD_MAX_DEPTH: usize = 8;
+pub const PLUME_STATUS_KDF_BAD_INPUT: u8 = 128;
+pub const PLUME_KDF_BIP39: c_int = 1;
+pub const PLUME_KDF_SHARED_SALT: c_int = 2;
+pub const PLUME_KDF_MAX_SALT: usize = 256;
+pub const PLUME_KDF_MAX_ITERATIONS: u32 = 1 << 24;
 pub const PLUME_RECOVER_MISMATCH: u8 = 0;
 pub const PLUME_RECOVER_MATCH: u8 = 1;
 pub const PLUME_RECOVER_INVALID: u8 = 3;
@@ -216,6 +221,10 @@ extern "C" {
         path: *const u32, depth: usize, child_pk: *mut u8, child_chain32: *mut u8, address: *mut u8, status: *mut u8) -> c_int;
     fn plume_hd_derive_pub_batch_device(ctx: *mut plume_ctx, flags: c_int, pk_format: c_int, addr_format: c_int, n: usize, parent_pk: *const u8, parent_chain32: *const u8,
         path: *const u32, depth: usize, child_pk: *mut u8, child_chain32: *mut u8, address: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
+    fn plume_pbkdf2_sha512_batch(ctx: *mut plume_ctx, flags: c_int, n: usize, pw: *const u8, pw_off: *const u64, salt: *const u8, salt_len: usize, iterations: u32,
+        dklen: usize, out: *mut u8, status: *mut u8) -> c_int;
+    fn plume_pbkdf2_sha512_batch_device(ctx: *mut plume_ctx, flags: c_int, n: usize, pw: *const u8, pw_off: *const u64, pw_bytes: usize, salt: *const u8, salt_len: usize,
+        iterations: u32, dklen: usize, out: *mut u8, status: *mut u8, stream: *mut c_void) -> c_int;
 }
 
 fn last_error() -> HipError { HipError(unsafe { std::ffi::CStr::from_ptr(plume_last_error()) }.to_string_lossy().into_owned()) }
@@ -498,6 +507,28 @@ impl HipEngine {
         if status[0] != 0 { return Err(HipError(format!("sign_tx: no signature (status {})", status[0]))); }
         out.truncate(out_len[0] as usize);
         Ok(out)
+    }
+    /// PBKDF2-HMAC-SHA512(password, salt, iterations), the first `dklen` bytes (1 ..= 64), on the GPU (`plume_pbkdf2_sha512_batch`); a salt of at most
+    /// `PLUME_KDF_MAX_SALT` bytes.  Over bytes: a caller with non-ASCII text normalises it (NFKD) first.
+    pub fn pbkdf2_sha512(&self, password: &[u8], salt: &[u8], iterations: u32, dklen: usize) -> Result<Vec<u8>, HipError> {
+        let off = [0u64, password.len() as u64];
+        let (mut out, mut status) = (vec![0u8; dklen.max(1)], [0u8; 1]);
+        let rc = unsafe { plume_pbkdf2_sha512_batch(self.0, PLUME_KDF_SHARED_SALT, 1, password.as_ptr(), off.as_ptr(), salt.as_ptr(), salt.len(), iterations, dklen,
+                                                    out.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        if status[0] != 0 { return Err(HipError(format!("pbkdf2_sha512: not derived (status {})", status[0]))); }
+        Ok(out)
+    }
+    /// The 64-byte BIP-39 seed of a mnemonic sentence, on the GPU: PBKDF2-HMAC-SHA512(sentence, "mnemonic" || passphrase, 2048).  Over bytes: a caller with non-ASCII
+    /// text normalises it (NFKD) first.  The word list is out of scope: the sentence is not checked against it.
+    pub fn mnemonic_to_seed(&self, mnemonic: &[u8], passphrase: &[u8]) -> Result<[u8; 64], HipError> {
+        let off = [0u64, mnemonic.len() as u64];
+        let (mut seed, mut status) = ([0u8; 64], [0u8; 1]);
+        let rc = unsafe { plume_pbkdf2_sha512_batch(self.0, PLUME_KDF_BIP39 | PLUME_KDF_SHARED_SALT, 1, mnemonic.as_ptr(), off.as_ptr(), passphrase.as_ptr(), passphrase.len(), 2048,
+                                                    64, seed.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 { return Err(last_error()); }
+        if status[0] != 0 { return Err(HipError(format!("mnemonic_to_seed: not derived (status {})", status[0]))); }
+        Ok(seed)
     }
     /// The BIP-32 master node `(sk, chain)` of a seed of 16 .. 64 bytes (`plume_hd_master_batch`): HMAC-SHA512("Bitcoin seed", seed), on the GPU.
     pub fn hd_master(&self, seed: &[u8]) -> Result<([u8; 32], [u8; 32]), HipError> {

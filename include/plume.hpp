@@ -522,6 +522,29 @@ inline std::array<uint8_t, 20> hd_address(const AffinePoint& pk, const Bytes32& 
     hd_check_status(st);
     return addr;
 }
+// ---- BIP-39 seeds (plume_hip.h, library 0.18): PBKDF2-HMAC-SHA512 on the GPU, over bytes.  A caller with non-ASCII text normalises it (NFKD) first; the word list is
+// out of scope, any bytes have a seed.
+// PBKDF2-HMAC-SHA512(password, salt, iterations)[0 .. dklen), 1 <= dklen <= 64, salt of at most PLUME_KDF_MAX_SALT bytes
+inline plume_hip::Bytes pbkdf2_sha512(const uint8_t* password, size_t password_len, const uint8_t* salt, size_t salt_len, uint32_t iterations, size_t dklen = 64,
+                                      Engine& eng = Engine::shared()) {
+    const uint64_t off[2] = {0, password_len};
+    plume_hip::Bytes out(dklen ? dklen : 1);
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_pbkdf2_sha512_batch(eng.ctx(), PLUME_KDF_SHARED_SALT, 1, password, off, salt, salt_len, iterations, dklen, out.data(), &st), "plume_pbkdf2_sha512_batch");
+    if (st) throw SignatureError();
+    return out;
+}
+// the 64-byte BIP-39 seed of a mnemonic sentence: PBKDF2-HMAC-SHA512(sentence, "mnemonic" || passphrase, 2048)
+inline std::array<uint8_t, 64> mnemonic_to_seed(const std::string& mnemonic, const std::string& passphrase = "", Engine& eng = Engine::shared()) {
+    const uint64_t off[2] = {0, mnemonic.size()};
+    std::array<uint8_t, 64> seed{};
+    uint8_t st = 0xFF;
+    plume_hip::check(plume_pbkdf2_sha512_batch(eng.ctx(), PLUME_KDF_BIP39 | PLUME_KDF_SHARED_SALT, 1, (const uint8_t*)mnemonic.data(), off, (const uint8_t*)passphrase.data(),
+                                               passphrase.size(), 2048, 64, seed.data(), &st),
+                     "plume_pbkdf2_sha512_batch");
+    if (st) throw SignatureError();
+    return seed;
+}
 // An extended key "xprv..." / "xpub..." (mainnet), base58check DECODE only: depth, child number, chain code and the key -- 32 bytes of sk in key[1 .. 33) behind a zero
 // byte, or the 33 SEC1 bytes of pk.  std::invalid_argument for a bad digit, length, checksum or version.
 struct ExtendedKey { uint8_t depth; uint32_t child_number; Bytes32 chain; std::array<uint8_t, 33> key; };

@@ -724,6 +724,42 @@ int plume_hd_derive_pub_batch(plume_ctx* ctx, int flags, int pk_format, int addr
 int plume_hd_derive_pub_batch_device(plume_ctx* ctx, int flags, int pk_format, int addr_format, size_t n, const uint8_t* parent_pk, const uint8_t* parent_chain32,
                                      const uint32_t* path, size_t depth, uint8_t* child_pk, uint8_t* child_chain32, uint8_t* address, uint8_t* status, void* stream);
 
+/* ---- BIP-39 seeds: PBKDF2-HMAC-SHA512, one output block, for a batch  (library 0.18) ----------------------------------
+ * A wallet holds a mnemonic sentence, not a seed: seed = PBKDF2-HMAC-SHA512(password = the sentence, salt = "mnemonic" || passphrase, 2048 iterations, 64 bytes), 4096
+ * compressions per item, where a BIP-32 step costs four.  This call makes the seeds where plume_hd_master_batch_device takes them, so that "mnemonic in, addresses and
+ * signed transactions out" is one chain of device calls and neither a seed nor a key is ever made in host memory.
+ *   U_1 = HMAC(P, S || 00000001), U_j = HMAC(P, U_(j-1)), T_1 = U_1 ^ .. ^ U_iterations (RFC 8018); out[i] = T_1[0 .. dklen), 1 <= dklen <= 64.  Only T_1 is computed:
+ *   a larger dklen returns PLUME_ERR_ARG, it is not truncated silently.
+ *   password  item i's is pw[pw_off[i] .. pw_off[i + 1]): n + 1 offsets, any length from 0 up.  HMAC's rule applies: up to 128 bytes zero-padded, a longer one replaced
+ *             by its SHA-512 (a 24-word sentence usually is longer).
+ *   salt      salt_len bytes per item, 0 .. PLUME_KDF_MAX_SALT, the same length for every item; NULL is allowed when salt_len is 0.  PLUME_KDF_SHARED_SALT: salt holds
+ *             ONE record, used for every item.  PLUME_KDF_BIP39: the eight bytes "mnemonic" are put in front of every item's salt on the device.  There is no ragged
+ *             per-item salt: a passphrase is absent or one per batch in practice.
+ *   status    (required) 0: derived.  PLUME_STATUS_KDF_BAD_INPUT (device form only): pw_off[i + 1] < pw_off[i] or pw_off[i + 1] > pw_bytes; that item reads no byte of
+ *             pw and its record is all zero, its neighbours are derived.  The host form returns PLUME_ERR_ARG for decreasing offsets anywhere, before anything is
+ *             staged or written.
+ * Argument errors return PLUME_ERR_ARG with nothing written: iterations outside 1 .. PLUME_KDF_MAX_ITERATIONS (a guard against a typo that queues hours of work, not a
+ * measured figure), dklen or salt_len out of range, unknown flag bits, a null required array.  n = 0 is a successful no-op.  Arrays may sit at any byte offset, pw_off
+ * 8-byte aligned.  No byte outside [pw, pw + pw_bytes) and outside the salt and out arrays is read or written.
+ * Device side, one lane per item: "kdf_key" (the password read once and hashed if long, the two HMAC midstates, U_1), "kdf_iter" (the remaining iterations, two
+ * compressions each, enqueued in slices of 256 so that no dispatch of a large call runs for the whole derivation: once per slice in the stage list) and "kdf_finish".
+ * Between them the midstates, U and T live in staging the context owns, 256 bytes per item, wiped on the call's stream behind the last kernel, on failure paths too.
+ * Lengths are public: the lanes branch on and address by offsets, lengths, salt_len and the iteration count only, never by a byte of a password, a salt, a midstate or
+ * U / T; a wavefront takes as long as its longest password needs to be read.  The device form needs a single-device context and n <= the chunk size, waits for and leaves
+ * the workspace event, needs no table and does not synchronise.  The host form is a serial call: pieces of at most plume_set_chunk items, the shards of a plume_init_multi
+ * context; the passwords, the salt and the output are wiped from the staging behind their use or their download.
+ * Out of scope: the BIP-39 word list (sentence <-> entropy, checksum validation -- the seed derivation does not need it), dklen > 64, other PRFs.  A caller with non-ASCII
+ * text normalises it (NFKD) before it hands over the bytes. */
+#define PLUME_KDF_BIP39        1   /* flags bit 0: the salt of every item is "mnemonic" || salt (8 bytes put in front on the device) */
+#define PLUME_KDF_SHARED_SALT  2   /* flags bit 1: salt holds ONE record of salt_len bytes, used for every item */
+#define PLUME_KDF_MAX_SALT     256
+#define PLUME_KDF_MAX_ITERATIONS (1u << 24)
+#define PLUME_STATUS_KDF_BAD_INPUT 128
+int plume_pbkdf2_sha512_batch(plume_ctx* ctx, int flags, size_t n, const uint8_t* pw, const uint64_t* pw_off, const uint8_t* salt, size_t salt_len, uint32_t iterations,
+                              size_t dklen, uint8_t* out, uint8_t* status);
+int plume_pbkdf2_sha512_batch_device(plume_ctx* ctx, int flags, size_t n, const uint8_t* pw, const uint64_t* pw_off, size_t pw_bytes, const uint8_t* salt, size_t salt_len,
+                                     uint32_t iterations, size_t dklen, uint8_t* out, uint8_t* status, void* stream);
+
 /* ---- Keccak Merkle allow-lists of addresses  (library 0.15) -------------------------------------------------------
  * An application that gates on a list of accounts usually publishes ONE 32-byte root and lets every claimant bring a proof.  These calls build that tree, hand out proofs
  * and check proofs against a root, in the form OpenZeppelin's StandardMerkleTree (@openzeppelin/merkle-tree) builds and MerkleProof.verify checks on chain.

@@ -73,7 +73,10 @@ _rows(None,
 # later entry points: an older build selected through PLUME_HIP_LIB (A/B runs against an earlier round) may lack them; the in-tree library must have them all (_load checks)
 _rows("later",
       ("plume_set_sign_uniform", [vp, i]), ("plume_get_sign_uniform", [vp]), ("plume_set_host_lanes", [vp, i]), ("plume_set_eq1_short", [vp, i]),
-      ("plume_set_stage_timing", [vp, i]))
+      ("plume_set_stage_timing", [vp, i]),
+      # BIP-39 seeds (library 0.18): PBKDF2-HMAC-SHA512 for a batch
+      ("plume_pbkdf2_sha512_batch", [vp, i, sz, vp, vp, vp, sz, C.c_uint32, sz, vp, vp]),
+      ("plume_pbkdf2_sha512_batch_device", [vp, i, sz, vp, vp, sz, vp, sz, C.c_uint32, sz, vp, vp, vp]))
 _rows(None,
       ("plume_get_eq1_short", [vp, C.POINTER(C.c_size_t)]), ("plume_last_msm_clock", [vp, C.POINTER(C.c_double)]), ("plume_last_msm_kernel", [vp], C.c_char_p),
       ("plume_set_host_piece", [vp, sz]), ("plume_last_redo_tasks", [vp, C.POINTER(C.c_uint64)]),
@@ -188,6 +191,14 @@ def pack_messages(msgs):
     return buf, off
 
 
+def bip39_bytes(text):
+    """what BIP-39 hashes of a sentence or a passphrase: a str NFKD-normalised and UTF-8 encoded; bytes are taken as given"""
+    if isinstance(text, str):
+        import unicodedata
+        return unicodedata.normalize("NFKD", text).encode("utf-8")
+    return bytes(text)
+
+
 def _np(a, width, n, name):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.size != width * n:
@@ -242,6 +253,11 @@ HD_MAX_DEPTH = 8
 HD_SHARED_PARENT, HD_SHARED_PATH = 1, 2
 STATUS_HD_NO_KEY, STATUS_HD_HARDENED = 32, 64
 HD_HARDENED = 2**31
+# plume_pbkdf2_sha512_batch (include/plume_hip.h): the flag bits, the longest salt, the most iterations, the status of an item whose offsets are unsound (device form)
+KDF_BIP39, KDF_SHARED_SALT = 1, 2
+KDF_MAX_SALT = 256
+KDF_MAX_ITERATIONS = 1 << 24
+STATUS_KDF_BAD_INPUT = 128
 # plume_merkle_* (include/plume_hip.h): leaf formats -> (PLUME_MERKLE_LEAF_*), the sort flag, the status of an item, the proof length of a refused index
 MERKLE_LEAF_FORMATS = {"hash32": 0, "address": 1, "address_uint256": 2}
 MERKLE_SORT_LEAVES = 1
@@ -754,6 +770,86 @@ class Engine:
         return res
 
     @staticmethod
+    def _kdf_shape(passwords, salt, bip39):
+        """(n, pw, pw_off, flags, salt, salt_len) of a PBKDF2 call.  passwords: a list of bytes (str: NFKD, UTF-8), or (buf, off) as pack_messages returns them; salt:
+        None or bytes -- ONE record shared by every item -- or an n x salt_len array"""
+        pw, off = passwords if isinstance(passwords, tuple) else pack_messages([bip39_bytes(p) for p in passwords])
+        n, pw, off = _ragged(pw, off)
+        flags = KDF_BIP39 if bip39 else 0
+        if salt is None or isinstance(salt, (str, bytes, bytearray, memoryview)):
+            salt = np.frombuffer(bip39_bytes(salt or b""), dtype=np.uint8)
+            return n, pw, off, flags | KDF_SHARED_SALT, salt, len(salt)
+        salt = np.ascontiguousarray(salt, dtype=np.uint8)
+        if salt.ndim != 2 or len(salt) != n:
+            raise ValueError(f"salt: bytes shared by every item, or an n x salt_len array for the {n} items")
+        return n, pw, off, flags, salt, salt.shape[1]
+
+    def pbkdf2_sha512_batch(self, passwords, salt=None, iterations=2048, dklen=64, bip39=False, device=False):
+        """PBKDF2-HMAC-SHA512, one output block, for a batch (plume_pbkdf2_sha512_batch).  passwords: a list of bytes of any length, or (buf, off) as pack_messages
+        returns them; salt: None or bytes -- one record shared by every item -- or an n x salt_len array (salt_len <= 256); bip39: "mnemonic" goes in front of every
+        salt on the device; 1 <= dklen <= 64.  Returns (out, status): n x dklen bytes and n status bytes, all 0 (the host form refuses unsound offsets as a whole).
+        device=True: the device form on torch tensors of the engine's device, which the pair then holds -- an item of a caller's (buf, off) whose offsets decrease or
+        reach past buf reports STATUS_KDF_BAD_INPUT (128) and an all-zero record; out goes into hd_master_batch_device as it is (synchronises only as torch does)."""
+        n, pw, off, flags, salt, salt_len = self._kdf_shape(passwords, salt, bip39)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device_id)
+            up = lambda a: torch.from_numpy(np.array(a.view(np.int64) if a.dtype == np.uint64 else a)).to(dev)  # noqa: E731  (a copy: the caller's array may be read-only)
+            pw, off, salt = up(pw), up(off), up(salt) if salt_len else None
+            out, status = torch.zeros((n, int(dklen)), dtype=torch.uint8, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev)
+            self._on_own_stream(dev, (pw, off, salt, out, status), lambda st: self.pbkdf2_sha512_batch_device(
+                n, pw, off, pw.numel(), salt, salt_len, iterations, dklen, out, status, flags=flags, stream=st))
+            return out, status
+        fn = self._fn("plume_pbkdf2_sha512_batch")
+        out, status = np.zeros((n, int(dklen)), np.uint8), np.zeros(n, np.uint8)
+        self._chk(fn(self._ctx, flags, n, _ptr(pw), _ptr(off), _ptr(salt) if salt_len else None, int(salt_len), int(iterations), int(dklen), _ptr(out), _ptr(status)),
+                  "plume_pbkdf2_sha512_batch")
+        return out, status
+
+    def bip39_seed_batch(self, mnemonics, passphrase="", device=False):
+        """The BIP-39 seeds of mnemonic sentences: pbkdf2_sha512_batch with bip39=True, the passphrase as the one shared salt, 2048 iterations, 64 bytes.  str arguments
+        are NFKD-normalised and UTF-8 encoded, bytes taken as given.  The word list is out of scope: a sentence is not checked against it.  Returns (seed, status)."""
+        return self.pbkdf2_sha512_batch(mnemonics, bip39_bytes(passphrase), 2048, 64, bip39=True, device=device)
+
+    def bip39_accounts(self, mnemonics, passphrase="", path="m/44'/60'/0'/0/0", device=False, want=("chain", "pk", "address"), pk_format="affine64", addr_format="raw20"):
+        """Mnemonic sentences to account keys in one chain of device calls: bip39_seed_batch -> hd_master_batch_device -> hd_derive_priv_batch, with no host copy of a
+        seed or a master key in between.  path: a BIP-32 path ("m/44'/60'/0'/0/0") or a row of indices shared by every item, or a list of n of either; ONE sentence with
+        n paths gives n accounts of that wallet.  Returns the dict of hd_derive_priv_batch (sk, status, the records in `want`) as torch tensors on the device
+        (device=True: sk goes into ecdsa_sign_batch_device / eth_tx_sign_batch_device as it is) or as numpy arrays.  status[i] is the first non-zero status of the three
+        steps -- STATUS_KDF_BAD_INPUT (128), STATUS_HD_NO_KEY (32), 2 -- and every record of such an item is all zero: a zero seed would otherwise derive a
+        real-looking key."""
+        import torch
+        from .plume import parse_path
+        rows = [path] if isinstance(path, str) or (len(path) and isinstance(path[0], (int, np.integer))) else list(path)
+        idx = np.array([parse_path(p) if isinstance(p, str) else [int(i) for i in p] for p in rows], dtype=np.uint32)
+        seed, st0 = self.bip39_seed_batch(mnemonics, passphrase, device=True)
+        n0, dev = len(st0), seed.device
+        msk, mchain = torch.zeros((n0, 32), dtype=torch.uint8, device=dev), torch.zeros((n0, 32), dtype=torch.uint8, device=dev)
+        st1 = torch.zeros(n0, dtype=torch.uint8, device=dev)
+        if n0:
+            self._on_own_stream(dev, (seed, msk, mchain, st1), lambda st: self.hd_master_batch_device(n0, seed, 64, msk, mchain, st1, stream=st))
+        res = self._hd_derive_torch(False, msk, mchain, idx, pk_format, addr_format, want)
+        before = torch.where(st0 != 0, st0, st1)                                # one row for a shared parent: it broadcasts over the items
+        status = torch.where(before != 0, before, res["status"])
+        keep = (status == 0).to(torch.uint8).reshape(-1, 1)
+        res = {k: status if k == "status" else v * keep for k, v in res.items()}
+        seed.zero_(); msk.zero_(); mchain.zero_()
+        return res if device else {k: v.cpu().numpy() for k, v in res.items()}
+
+    def _on_own_stream(self, dev, tensors, enqueue):
+        """enqueue(stream) on a stream of its own between two waits: torch's default stream is the null stream, which the library takes to mean the context's stream --
+        and that one is not ordered against the fills of `tensors` or the caller's next use of them"""
+        import torch
+        cur = torch.cuda.current_stream(dev)
+        st = torch.cuda.Stream(dev)
+        st.wait_stream(cur)
+        enqueue(st)
+        cur.wait_stream(st)
+        for t in tensors:
+            if t is not None:
+                t.record_stream(st)
+
+    @staticmethod
     def _merkle_items(leaf_format, addr_format, items, amounts):
         lf = MERKLE_LEAF_FORMATS[leaf_format]
         if addr_format == "eip55":
@@ -1029,6 +1125,14 @@ class Engine:
             self._enqueue("plume_hd_derive_pub_batch_device", stream, *head, d(child_pk), d(child_chain), d(address), d(status))
         else:
             self._enqueue("plume_hd_derive_priv_batch_device", stream, *head, d(child_sk), d(child_chain), d(child_pk), d(address), d(status))
+
+    def pbkdf2_sha512_batch_device(self, n, pw, pw_off, pw_bytes, salt, salt_len, iterations, dklen, out, status, flags=0, stream=None):
+        """the device form of pbkdf2_sha512_batch on torch tensors (pw_off: n + 1 uint64 offsets into the pw_bytes bytes of pw; salt: salt_len bytes per item, one record
+        with KDF_SHARED_SALT, None when salt_len is 0; out: n x dklen bytes; flags: KDF_BIP39 | KDF_SHARED_SALT); enqueues on `stream` (None = current stream); does not
+        synchronise"""
+        d = self._dp
+        self._enqueue("plume_pbkdf2_sha512_batch_device", stream, int(flags), int(n), d(pw), d(pw_off), int(pw_bytes), d(salt), int(salt_len), int(iterations), int(dklen),
+                      d(out), d(status))
 
     def merkle_leaf_batch_device(self, n, items, amounts, leaf32, status, leaf_format="address", addr_format="raw20", stream=None):
         """the device form of merkle_leaf_batch on torch tensors; amounts (n x 32 big-endian bytes) and status may be None; one kernel on `stream` (None = current

@@ -117,7 +117,7 @@ static void destroy_single(plume_ctx* ctx) {
     if (ctx->ws_used && ctx->ws_free) (void)hipEventSynchronize(ctx->ws_free);
     for (hipStream_t q : {ctx->stream, ctx->up, ctx->down, ctx->side, ctx->pre}) if (q) (void)hipStreamSynchronize(q);
     for (DevBuf* b : {&ctx->bases, &ctx->jobflags, &ctx->itemflags, &ctx->tab, &ctx->tabscr, &ctx->res, &ctx->resinf, &ctx->res2, &ctx->res2inf, &ctx->pkaff,
-                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->scstage, &ctx->txstage, &ctx->txsign, &ctx->hdws, &ctx->mrksort, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
+                      &ctx->sink, &ctx->redo, &ctx->digs, &ctx->eq1fall, &ctx->eq1k, &ctx->clk, &ctx->nonce, &ctx->scstage, &ctx->txstage, &ctx->txsign, &ctx->hdws, &ctx->kdfws, &ctx->mrksort, &ctx->dec[0], &ctx->dec[1], &ctx->dec[2], &ctx->dec[3], &ctx->preflags, &ctx->agg_record, &ctx->dslots, &ctx->dminid, &ctx->dmyslot, &ctx->dcount, &ctx->dblockcnt})
         b->release();
     for (DevBuf& b : ctx->agg) b.release();
     if (ctx->fixed) {
@@ -1376,7 +1376,7 @@ static int host_call_any(plume_ctx* ctx, size_t n, const HostCall& call, Run run
 // ------------------------------------------------------------------------------------- serial host-pointer calls
 // One piece of a serial call (see the block comment above): items [i0, i0 + cnt) through ctx->slot[0] on ctx->stream, and the wait for it.  In queue order: the whole-call
 // inputs (first piece only), the messages, the inputs that are given, run(slot, cnt, ctx) -- the caller's lambda picks the slot's buffers and calls the *_device body --,
-// the wipe of the secret inputs, the downloads of the outputs that are given, the wipe of the secret outputs.  Whatever fails, the stream is synchronised before the
+// the wipe of the secret inputs (and of the messages of a call that marks them secret), the downloads of the outputs that are given, the wipe of the secret outputs.  Whatever fails, the stream is synchronised before the
 // piece returns -- no copy stays queued on the caller's arrays, the slot is free for the next call -- and every secret staging buffer is wiped in front of that wait.
 // The result is the first failure: an argument or an allocation (DevBuf::ensure's text), run's, a copy's, the wait's.
 template <class Run>
@@ -1408,6 +1408,7 @@ static int serial_host_piece(plume_ctx* ctx, const HostCall& call, size_t i0, si
         if (rag_bytes && sl.ragged.ensure(rag_bytes)) return PLUME_ERR_HIP;
         if (int rc = run(sl, cnt, ctx)) return rc;
         for (size_t k = 0; k < std::size(call.in); k++) if (call.in[k].secret && call.in[k].p) HIPCHK(hipMemsetAsync(sl.in[k].p, 0, bytes(call.in[k]), st));
+        if (call.msgs_secret && call.msg_off && sl.rel[cnt]) HIPCHK(hipMemsetAsync(sl.msgs.p, 0, (size_t)sl.rel[cnt], st));
         for (size_t k = 0; k < std::size(call.out); k++) {
             const HostArray& a = call.out[k];
             if (a.p) { if (int rc = copy(at(a), sl.out[k].p, bytes(a), hipMemcpyDeviceToHost)) return rc; }
@@ -1420,6 +1421,7 @@ static int serial_host_piece(plume_ctx* ctx, const HostCall& call, size_t i0, si
     if (rc) {   // staged secrets that no kernel read, or that no wipe followed
         for (size_t k = 0; k < std::size(call.in); k++) if (call.in[k].secret && sl.in[k].p) (void)hipMemsetAsync(sl.in[k].p, 0, sl.in[k].cap, st);
         for (size_t k = 0; k < std::size(call.out); k++) if (call.out[k].secret && sl.out[k].p) (void)hipMemsetAsync(sl.out[k].p, 0, sl.out[k].cap, st);
+        if (call.msgs_secret && sl.msgs.p) (void)hipMemsetAsync(sl.msgs.p, 0, sl.msgs.cap, st);
     }
     const hipError_t es = hipStreamSynchronize(st);
     if (rc) return rc;

@@ -1,5 +1,5 @@
 // What the call families' translation units (plume_eth_capi.hip, plume_eth_hash_capi.hip, plume_ecdsa_capi.hip, plume_eth_tx_capi.hip, plume_merkle_capi.hip,
-// plume_ecdsa_sign_capi.hip, plume_eth_tx_sign_capi.hip, plume_hd_capi.hip) share with plume_capi.hip: the context and its buffers, routing, the workspace chain, the tables
+// plume_ecdsa_sign_capi.hip, plume_eth_tx_sign_capi.hip, plume_hd_capi.hip, plume_kdf_capi.hip) share with plume_capi.hip: the context and its buffers, routing, the workspace chain, the tables
 // and the host-call machinery -- all defined once, in plume_capi.hip -- and the stages one family lends another.  Internal: not part of the ABI, every function hidden in
 // the shared object.  The three launcher hooks that remain (nonce, release, recover) are plume_capi_internal.h's.
 #pragma once
@@ -148,6 +148,7 @@ struct plume_ctx {
     DevBuf txstage;                                                // plume_eth_tx_sender_batch: what k_eth_tx_parse hands the recover stages -- hash, r, s, v, 97 B / item (public data: not wiped)
     DevBuf txsign;                                                 // plume_eth_tx_sign_batch: the framing (chain id, packed frame word), the signing hash and what the sign stages make of it -- 114 B / item; r, s, v and status wiped behind the assemble
     DevBuf hdws;                                                   // plume_hd_derive_*_batch: k, the chain code and the status of every item between the levels, 65 B / item; wiped behind finish
+    DevBuf kdfws;                                                  // plume_pbkdf2_sha512_batch: the midstates, U and T of every item between the kernels, 256 B / item; wiped behind finish
     DevBuf mrksort;                                                // plume_merkle_tree_build: the sort's records, nine word arrays of npad words, 36 B / padded leaf (public data: not wiped)
     DevBuf nonce;                                                  // the derived-nonce signer: r of the call in flight, 32 B / item, wiped on the call's stream after sign_final
     int eq1_short = 1;                                             // verify calls that give R: equation 1 in its short form (plume_eis.h).  0 = long form always (A/B), 2 = test: every item takes the fallback
@@ -176,6 +177,7 @@ struct HostCall {
     const uint64_t* msg_off;   // null (serial calls only): the call has no messages and stages none
     HostArray in[6], out[8];
     bool out_heavy = false, may_use_two_lanes = false;
+    bool msgs_secret = false;                                         // serial calls only: the staged message bytes are wiped behind the kernels, as an input marked secret is
     const char *off_name = "msg_off", *msgs_name = "message";         // what the argument errors of the message staging call the two
     // serial calls only: a ragged output tied to the messages.  Item i owns the ragged_growth i + (msg_off[i] - msg_off[0]) .. bytes of it, its message's length plus
     // ragged_growth of them; a piece's share is contiguous, staged in HostSlot::ragged and downloaded in one copy behind the fixed-stride outputs

@@ -4,6 +4,8 @@
 // manner of HmacKey in plume_nonce.h); the data is one block too -- 37 bytes for a child key, 16 .. 64 bytes for a master seed -- and the outer hash is one block over the
 // 64-byte inner digest: four compressions per HMAC.
 // Compiles as plain C++ for the host (tests/hd), like the other headers.
+// Library 0.18 adds, for PBKDF2 (plume_kdf.h), a smaller form of the same compression (sha512_compress_grouped, rotations on 32-bit halves) and the multi-block tail
+// with padding for data of any length (sha512_absorb); what BIP-32 uses is unchanged.
 #pragma once
 #include "plume_field.h"
 
@@ -56,6 +58,69 @@ PLUME_HD void sha512_compress(uint64_t st[8], uint64_t w[16]) {
         h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
     }
     st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
+}
+
+// A rotation by a literal count on the 32-bit halves: two funnel shifts (v_alignbit_b32) on the device, where the compiler makes of the plain form two 64-bit shifts
+// and two ORs.  N is 1 .. 63
+template <int N>
+PLUME_HD uint64_t rotr64_halves(uint64_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+    if (N == 32) return ((uint64_t)lo << 32) | hi;
+    const uint32_t a = N < 32 ? lo : hi, b = N < 32 ? hi : lo;      // the value rotated by 32 first when N > 32
+    return ((uint64_t)__builtin_amdgcn_alignbit(a, b, N & 31) << 32) | __builtin_amdgcn_alignbit(b, a, N & 31);
+#else
+    return rotr64(x, N);
+#endif
+}
+// One round on the eight working words as a[0 .. 7] = a .. h; the rotation of the roles is the caller's (literal indices once unrolled)
+PLUME_HD void sha512_round(uint64_t& a, uint64_t& b, uint64_t& c, uint64_t& d, uint64_t& e, uint64_t& f, uint64_t& g, uint64_t& h, uint64_t kw) {
+    const uint64_t S1 = rotr64_halves<14>(e) ^ rotr64_halves<18>(e) ^ rotr64_halves<41>(e);
+    const uint64_t ch = (e & f) ^ (~e & g);
+    const uint64_t t1 = h + S1 + ch + kw;
+    const uint64_t S0 = rotr64_halves<28>(a) ^ rotr64_halves<34>(a) ^ rotr64_halves<39>(a);
+    const uint64_t mj = (a & b) ^ (a & c) ^ (b & c);
+    h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + S0 + mj;
+}
+// The same compression in a fifth of the code (plume_kdf.h: a loop body of two compressions has to leave room for two waves per SIMD): sixteen unrolled rounds over
+// w as it comes, then four trips of sixteen unrolled rounds that roll the schedule, the round constants read from the table at 16 grp + i -- grp is uniform, so the
+// table reads are scalar loads from constant memory and every index into w stays a literal.  w[16] is consumed
+PLUME_HD void sha512_compress_grouped(uint64_t st[8], uint64_t w[16]) {
+    uint64_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
+    PLUME_UNROLL for (int i = 0; i < 16; i++) sha512_round(a, b, c, d, e, f, g, h, sha512_k(i) + w[i]);
+    PLUME_NOUNROLL for (int grp = 1; grp < 5; grp++) {
+        PLUME_UNROLL for (int i = 0; i < 16; i++) {
+            const uint64_t w15 = w[(i + 1) & 15], w2 = w[(i + 14) & 15];
+            const uint64_t s0 = rotr64_halves<1>(w15) ^ rotr64_halves<8>(w15) ^ (w15 >> 7);
+            const uint64_t s1 = rotr64_halves<19>(w2) ^ rotr64_halves<61>(w2) ^ (w2 >> 6);
+            w[i] += s0 + w[(i + 9) & 15] + s1;
+            sha512_round(a, b, c, d, e, f, g, h, sha512_k(16 * grp + i) + w[i]);
+        }
+    }
+    st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
+}
+
+// SHA-512's tail over `len` bytes of any length given by byte(pos), 0 <= pos < len, padding included: `prefix` bytes (a multiple of 128) are already absorbed into st.
+// One trip per 128-byte block, the block count a function of len alone; byte() is never asked for a position at or beyond len
+template <class ByteFn>
+PLUME_HD void sha512_absorb(uint64_t st[8], uint64_t prefix, uint64_t len, ByteFn byte) {
+    const uint64_t nblk = (len + 17 + 127) / 128;          // the 0x80 byte and the 16-byte length field
+    PLUME_NOUNROLL for (uint64_t b = 0; b < nblk; b++) {
+        uint64_t w[16];
+        PLUME_UNROLL for (int k = 0; k < 16; k++) {
+            uint64_t word = 0;
+            PLUME_UNROLL for (int q = 0; q < 8; q++) {
+                const uint64_t pos = 128 * b + (uint64_t)(8 * k + q);
+                uint64_t v = 0;
+                if (pos < len) v = byte(pos);
+                else if (pos == len) v = 0x80;
+                word = (word << 8) | v;
+            }
+            w[k] = word;
+        }
+        if (b + 1 == nblk) w[15] = (prefix + len) << 3;    // (w[14], the length's upper half, is zero: lengths stay below 2^61)
+        sha512_compress_grouped(st, w);
+    }
 }
 
 // SHA-512 of `len` <= 111 bytes (one block) given by byte(pos), 0 <= pos < len; len is the same for every lane of a launch.  prefix_blocks 128-byte blocks are

@@ -22,7 +22,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from .capi import (ECDSA_INVALID, ETH_INVALID, ETH_MATCH, ETH_TX_OK, HD_HARDENED, HD_MAX_DEPTH, MERKLE_MATCH, RECOVER_INVALID, RECOVER_MATCH, STATUS_BAD_TX, STATUS_HD_HARDENED,
-                   STATUS_HD_NO_KEY, Engine, default_engine, pack_messages)
+                   STATUS_HD_NO_KEY, Engine, bip39_bytes, default_engine, pack_messages)
 
 DST = b"QUUX-V01-CS02-with-secp256k1_XMD:SHA-256_SSWU_RO_"  # rust-k256/src/lib.rs:61
 _P = 2**256 - 2**32 - 977
@@ -447,7 +447,7 @@ def _hd_path(path):
 
 def hd_master(seed: bytes, engine: Optional[Engine] = None) -> Tuple[bytes, bytes]:
     """The BIP-32 master node (sk, chain) of a seed of 16 .. 64 bytes, made on the GPU (include/plume_hip.h, plume_hd_master_batch): HMAC-SHA512("Bitcoin seed", seed).
-    The seed of a BIP-39 mnemonic is hashlib.pbkdf2_hmac("sha512", mnemonic, b"mnemonic" + passphrase, 2048)."""
+    The seed of a BIP-39 mnemonic is mnemonic_to_seed(mnemonic, passphrase), made on the GPU too; Engine.bip39_accounts chains both without a host copy of the seed."""
     seed = bytes(seed)
     if not 16 <= len(seed) <= 64:
         raise ValueError("hd_master: a seed is 16 .. 64 bytes")
@@ -499,6 +499,33 @@ def hd_address(key, chain: bytes, path, engine: Optional[Engine] = None) -> byte
             raise ValueError("hd_address: key is a 32-byte sk, or a pk of 64 bytes x || y or 33 SEC1 bytes")
         res = eng.hd_derive_pub_batch(a(pk), a(_b32("hd_address", "chain", chain)), _hd_path(path), pk_format="sec1" if len(pk) == 33 else "affine64", want=("address",))
     _hd_status("hd_address", int(res["status"][0]))
+    return res["address"][0].tobytes()
+
+
+# ------------------------------------------------------------------------------------------------ BIP-39 seeds (library 0.18)
+def pbkdf2_sha512(password, salt, iterations: int, dklen: int = 64, engine: Optional[Engine] = None) -> bytes:
+    """PBKDF2-HMAC-SHA512(password, salt, iterations)[:dklen] on the GPU (plume_pbkdf2_sha512_batch): hashlib.pbkdf2_hmac("sha512", ...) for 1 <= dklen <= 64, a salt of
+    at most 256 bytes and at most 2^24 iterations.  str arguments are NFKD-normalised and UTF-8 encoded, bytes taken as given."""
+    out, status = (engine or default_engine()).pbkdf2_sha512_batch([bip39_bytes(password)], bip39_bytes(salt), iterations, dklen)
+    if int(status[0]):
+        raise SignatureError(f"pbkdf2_sha512: not derived (status {int(status[0])})")
+    return out[0].tobytes()
+
+
+def mnemonic_to_seed(mnemonic, passphrase="", engine: Optional[Engine] = None) -> bytes:
+    """The 64-byte BIP-39 seed of a mnemonic sentence, made on the GPU: PBKDF2-HMAC-SHA512(sentence, "mnemonic" || passphrase, 2048).  str arguments are
+    NFKD-normalised and UTF-8 encoded as BIP-39 says, bytes taken as given.  The sentence is not checked against the word list (out of scope: any bytes have a seed)."""
+    seed, status = (engine or default_engine()).bip39_seed_batch([bip39_bytes(mnemonic)], bip39_bytes(passphrase))
+    if int(status[0]):
+        raise SignatureError(f"mnemonic_to_seed: not derived (status {int(status[0])})")
+    return seed[0].tobytes()
+
+
+def mnemonic_to_address(mnemonic, path="m/44'/60'/0'/0/0", passphrase="", engine: Optional[Engine] = None) -> bytes:
+    """The 20-byte Ethereum address of the account at `path` of a mnemonic sentence: seed, master node and the derivation chained on the GPU (Engine.bip39_accounts);
+    neither the seed nor a key comes to the host.  Raises SignatureError for a path that has no key."""
+    res = (engine or default_engine()).bip39_accounts([bip39_bytes(mnemonic)], bip39_bytes(passphrase), path, want=("address",))
+    _hd_status("mnemonic_to_address", int(res["status"][0]))
     return res["address"][0].tobytes()
 
 

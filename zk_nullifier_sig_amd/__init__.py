@@ -4,7 +4,7 @@ from pathlib import Path as _Path
 
 __path__.append(str(_Path(__file__).resolve().parent.parent / "zk-nullifier-sig_amd"))
 
-from .capi import ECDSA_INVALID, ECDSA_LOW_S, ECDSA_MATCH, ECDSA_MISMATCH, ECDSA_SIGN_V27, ETH_HASH_MODES, ETH_INVALID, ETH_MATCH, ETH_MISMATCH, ETH_TX_INVALID, ETH_TX_OK, ETH_TX_SIGN_GROWTH, HD_HARDENED, HD_MAX_DEPTH, HD_SHARED_PARENT, HD_SHARED_PATH, MERKLE_BAD_PROOF, MERKLE_INVALID, MERKLE_MATCH, MERKLE_MISMATCH, Engine, MerkleTree, NullifierSet, PlumeHipError, STATUS_BAD_TX, STATUS_HD_HARDENED, STATUS_HD_NO_KEY, default_engine, library_path  # noqa: E402,F401
+from .capi import ECDSA_INVALID, ECDSA_LOW_S, ECDSA_MATCH, ECDSA_MISMATCH, ECDSA_SIGN_V27, ETH_HASH_MODES, ETH_INVALID, ETH_MATCH, ETH_MISMATCH, ETH_TX_INVALID, ETH_TX_OK, ETH_TX_SIGN_GROWTH, HD_HARDENED, HD_MAX_DEPTH, HD_SHARED_PARENT, HD_SHARED_PATH, KDF_BIP39, KDF_MAX_ITERATIONS, KDF_MAX_SALT, KDF_SHARED_SALT, MERKLE_BAD_PROOF, MERKLE_INVALID, MERKLE_MATCH, MERKLE_MISMATCH, Engine, MerkleTree, NullifierSet, PlumeHipError, STATUS_BAD_TX, STATUS_HD_HARDENED, STATUS_HD_NO_KEY, STATUS_KDF_BAD_INPUT, bip39_bytes, default_engine, library_path  # noqa: E402,F401
 from .plume import (  # noqa: E402,F401
     DST,
     AffinePoint,
@@ -37,6 +37,9 @@ from .plume import (  # noqa: E402,F401
     hd_derive,
     hd_derive_pub,
     hd_master,
+    mnemonic_to_address,
+    mnemonic_to_seed,
+    pbkdf2_sha512,
     parse_path,
     parse_xprv,
     parse_xpub,
