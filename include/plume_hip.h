@@ -857,7 +857,10 @@ int plume_set_stage_timing(plume_ctx* ctx, int on);
 /* Measurement / test hook: the number of multi-scalar tasks (two per item) of the last verify call on this context whose unchecked addition chain met p == +-q and that
  * the second, dense launch redid with checked additions (k_verify_msm_redo).  Honest batches: 0.  Crafted items (pk = +-k G for small k with s = +-c, ...) file one or two
  * tasks each: that is all they cost -- their wavefront neighbours no longer wait for them.  Counts the last device-resident call (for a host-pointer call: its last piece;
- * for a multi-device context: the first shard).  A sign call with the self-check on (plume_set_sign_selfcheck) counts as a verify call here: its check's.  Synchronises with the device. */
+ * for a multi-device context: the first shard).  A sign call with the self-check on (plume_set_sign_selfcheck) counts as a verify call here: its check's.  Synchronises with the device.
+ * The redo list is scratch that the ECDSA recovery shares (plume_ecdsa_recover_batch*, and through it plume_eth_tx_sender_batch* and a self-checked plume_ecdsa_sign_batch* /
+ * plume_eth_tx_sign_batch*): once such a call has run on the context (or lane) this hook would read, the verifier's counters are gone and the hook returns PLUME_ERR_ARG,
+ * with a message that says so, instead of a count taken from another family's list.  The next verify call there re-arms it. */
 int plume_last_redo_tasks(plume_ctx* ctx, uint64_t* count);
 /* Measurement hook: the multi-scalar kernel the last verify call served by this context launched -- "k_verify_msm" (both equations in the long form), "k_verify_msm_s"
  * (equation 1 in the short form) or "k_verify_msm_pair" (half chains: small calls); NULL before the first verify.  Reports the same call as plume_last_stage_times; after a sign call with the self-check on, the kernel of its check.  A static string. */

@@ -1223,7 +1223,9 @@ class Engine:
         return [(names[i].decode(), float(ms[i])) for i in range(min(k, cap))]
 
     def last_redo_tasks(self):
-        """multi-scalar tasks of the last verify call that met p == +-q in an unchecked addition and were redone with checked additions (0 for honest batches)"""
+        """multi-scalar tasks of the last verify call that met p == +-q in an unchecked addition and were redone with checked additions (0 for honest batches).
+        Raises PlumeHipError once an ECDSA-family call (ecdsa_recover_batch, eth_tx_sender_batch, a self-checked ecdsa_sign_batch / eth_tx_sign_batch) has reused the redo
+        list on the context or lane this reads: the count would be another family's.  The next verify call re-arms it."""
         c = C.c_uint64(0)
         self._chk(self._lib.plume_last_redo_tasks(self._ctx, C.byref(c)), "plume_last_redo_tasks")
         return int(c.value)

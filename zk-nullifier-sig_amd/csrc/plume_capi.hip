@@ -660,7 +660,7 @@ static int verify_device(plume_ctx* ctx, int version, int mode, size_t n, const 
             a.eq1fall = ctx->eq1fall.as<uint8_t>() + lo; a.eq1k = ctx->eq1k.as<uint32_t>() + 8 * lo; a.gcomb = ctx->fixed->gcomb.as<uint32_t>();
             a.eq1force = ctx->eq1_short == 2 ? 1 : 0;
         }
-        if (k == 0) ctx->redo_counters.clear();
+        if (k == 0) { ctx->redo_counters.clear(); ctx->redo_foreign = false; }
         ctx->redo_counters.push_back(2 * lo + k);
         const bool two_roles = cnt <= ctx->ingest_split_max;
         a.msm_pair = (!eq1short && cnt <= ctx->msm_pair_max) ? 1 : 0;             // a few thousand items: a chain's latency is the kernel's time, so each long-form chain runs as two halves on two lanes
@@ -1749,6 +1749,9 @@ extern "C" int plume_last_redo_tasks(plume_ctx* ctx, uint64_t* count) {
     if (ctx && ctx->lane_last) ctx = ctx->lane_last;
     if (int rc = bind(ctx)) return rc;
     if (!count) return fail(PLUME_ERR_ARG, "null argument");
+    if (ctx->redo_foreign)
+        return fail(PLUME_ERR_ARG, "plume_last_redo_tasks: the redo list of this context was last used by a call of another family (an ECDSA recovery, a transaction "
+                                   "sender or a self-checked ECDSA sign call), not by a verify call: run a verify call first");
     HIPCHK(hipDeviceSynchronize());
     uint64_t total = 0;
     for (size_t off : ctx->redo_counters) {

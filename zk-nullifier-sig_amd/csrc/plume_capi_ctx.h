@@ -108,6 +108,8 @@ struct plume_ctx {
     const char* last_msm_kernel = nullptr;                         // the multi-scalar kernel the last verify call on this context launched (plume_last_msm_kernel)
     bool last_msm_sampled = false;                                 // ... and whether that launch sampled its clocks (plume_last_msm_clock: stage timing was on for the call)
     std::vector<size_t> redo_counters;                            // word offsets (in `redo`) of the last verify call's redo counters, one per sub-batch (plume_last_redo_tasks)
+    bool redo_foreign = false;                                    // ... the last call that laid out `redo` on this context was not a verify call (ecdsa_device: one counter per slice at lo + k),
+                                                                  // so those offsets hold another family's list: plume_last_redo_tasks refuses until a verify call has run here
     int sub_batches = 1;                                          // device-resident verify / sign: number of sub-batches; 1 = strictly serial launch order (the default: measured on the MI355X, r03, kernels of two
                                                                   // streams sharing the CUs cost MORE than the table kernel's idle issue slots give back -- 21.85 ms serial vs 22.1-22.4 ms for 2..16 sub-batches, LABNOTES.md §6)
     size_t overlap_min = (size_t)1 << 17;                         // ... batches below this many items always run serial (a sub-batch must still fill the chip)

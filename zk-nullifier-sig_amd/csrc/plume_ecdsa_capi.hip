@@ -39,6 +39,7 @@ int plume::ecdsa_device(plume_ctx* ctx, int flags, int pk_format, int addr_forma
         ctx->tabscr.ensure(scr_bytes) || ctx->res.ensure((size_t)PLUME_JAC_WORDS * 4 * n) || ctx->resinf.ensure(n) || ctx->redo.ensure((n + nsub) * 4) ||
         ctx->digs.ensure((size_t)PLUME_NPOS * n) || ctx->eq1k.ensure(32 * n))
         return PLUME_ERR_HIP;
+    ctx->redo_foreign = true;                                                 // the verifier's redo counters are no longer where plume_last_redo_tasks would read them
     const size_t P = eth_pk_width(pk_format), W = eth_address_width(addr_format);
     StageTimer& t = ctx->timer;
     if (!continue_timer) t.begin(st);
